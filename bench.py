@@ -2,7 +2,18 @@
 """bench.py -- throughput of the MI355X commitment engine on BASELINE.json's metric, one rank per GPU.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bn254_msm|kzg_commit|secp256k1_msm|icc|config3|crebuild|audit_combine|kzg_audit]
+                  [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run (no --full) does only what the headline figure needs: it sets up, warms up, times the K steps, writes the last step's
+outputs when --dump-outputs is given and prints the line (`metric`, `value`, `unit`, `ms_per_step`, ...; the dominant kernel's
+roofline from the HIP events of the timed region).  Everything else described below -- the other legs, the CPU baselines and oracle
+checks, the blocking-call, audit-size and host-boundary figures, the per-kernel breakdown passes, the in-run counter passes and the
+multiplier peak -- runs with --full, as the --no-* options select.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float32; the bytes of the 64-byte
+affine points / 32-byte scalars the caller receives, a fixed seeded sample of rows where the output is large, with the sampled
+row indices beside it).  The inputs depend only on the arguments, so two builds can be compared output for output.
 
 Default workload (the headline metric): a "step" is ONE 2^20-pair BN254 G1 MSM per GPU (BASELINE.json config 2, "KZG
 scheme, single 2^20-point BN254 G1 MSM on 1 MI355X"), inputs resident in HBM in the reference's wire format (32-B
@@ -15,7 +26,7 @@ additions on every host: the whole job is one N*2^20-pair MSM pe
 one MSM (bucket reduction, host fold) overlaps the bucket accumulation of the next; every step is still one complete MSM whose
 result is produced and checked, and K steps = K results inside the timed region (`--in-flight 1` = blocking calls).
 
-The same JSON line carries every other BASELINE.json configuration as a LEG -- an object with its own value, roofline,
+With --full the same JSON line carries every other BASELINE.json configuration as a LEG -- an object with its own value, roofline,
 cpu_baseline and bit_exact_vs_oracle, timed separately after the headline region, never as `value`:
   kzg_commits     2^17 rows x 128 coefficients per GPU against the resident SRS (the second half of the metric, "KZG commits/s";
                   compute_digest_from_srs hoisted over rows), with the per-call figures of the real symbol from a plain-C caller
@@ -34,7 +45,7 @@ cpu_baseline and bit_exact_vs_oracle, timed separately after the headline region
   server_mix      Server::mix in one call (data rows + MAC commitments + MAC alignments of two 2^12-row blocks), both curves; N = 1 only
   client_mac_batch  the block MACs of Client::initialize (digest + complement + add_point per block) for 2^17 blocks resident in
                   HBM behind porla_kzg_mac_batch_device; blocks/s, three blocks checked on the oracle's arithmetic; N = 1 only (s8 a4)
-and, for the headline MSM: `blocking_ms_per_step` + `blocking_kernels_ms` (one MSM in flight: what a caller that waits for
+and, for the headline MSM (--full): `blocking_ms_per_step` + `blocking_kernels_ms` (one MSM in flight: what a caller that waits for
 every result sees, with its own per-kernel breakdown), `audit_size_msm` (128 / 1 408 / 3 200 pairs: the sizes the reference
 issues), `host_boundary` (compute_multi_exp on caller-owned pageable host buffers, PCIe included).
 `--workload X` prints leg X alone as the line (`crebuild`: the device-resident last encode stage, tools/bench_crebuild.py).
@@ -89,6 +100,8 @@ KERNEL_SYMBOL = {  # profile slot -> substring of the kernel symbol in the rocpr
 LINE_LIMIT = 6000             # bytes: the driver keeps an 8 KB tail of stdout; the LAST line must fit in it whole
 LEG_KEYS = ("kzg_commits", "secp256k1_msm", "icc", "config3", "strong_2p20", "audit_combine", "kzg_audit", "client_mac_batch",
             "ipa_commits", "mac_encode", "server_mix")
+DUMPABLE = ("bn254_msm", "strong_2p20", "config3", "secp256k1_msm", "kzg_commit", "icc")     # workloads with --dump-outputs
+DUMP_LIMIT = 64 * 10**6       # bytes of .npy data per run at most
 
 
 def _short(s, n=80):
@@ -99,7 +112,8 @@ def _compact_roofline(rl):
     if not isinstance(rl, dict):
         return None
     out = {k: rl.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "kernel_ms")}
-    out["traffic_in_run"] = "collected in this run" in (rl.get("traffic_source") or "")
+    src = rl.get("traffic_source") or ""
+    out["traffic_in_run"] = "collected in this run" in src and "not collected in this run" not in src
     im = rl.get("int_multiplier")
     if isinstance(im, dict):
         out["int_multiplier"] = {"achieved": im.get("achieved"), "peak": im.get("peak"), "unit": "G fe_mul/s", "frac": im.get("frac")}
@@ -386,7 +400,18 @@ def main():
     ap.add_argument("--legs-out", default=os.path.join(ROOT, "bench_legs.json"),
                     help="where the FULL result (every leg's per-kernel breakdown, notes, samples) is written; the last stdout line is "
                          "the compact headline object (<= %d bytes)" % LINE_LIMIT)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the other legs, CPU baselines and oracle checks, blocking-call / audit-size / "
+                         "host-boundary figures, per-kernel breakdowns, in-run counter passes and the multiplier peak (off: the "
+                         "headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload not in DUMPABLE:
+        ap.error("--dump-outputs: workload %s has no output dump (supported: %s)" % (args.workload, ", ".join(DUMPABLE)))
+    if not args.full:
+        # a plain run: set up, warm up, time the K steps, dump, print the line -- every other figure and check is --full's
+        args.no_cpu = args.no_commits = args.no_legs = args.no_host_boundary = args.no_pmc = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started by hand with --gpus N: this process becomes the launcher of the N ranks (nothing below runs in it)
@@ -407,7 +432,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # the multiplier's rate on this box, before this process has any work on the GPU (rank 0 measures, one device)
-    fe_peak = measure_fe_mul_peak() if rank == 0 else None
+    fe_peak = measure_fe_mul_peak() if rank == 0 and args.full else None
 
     import torch
     import torch.distributed as dist
@@ -546,6 +571,32 @@ def main():
     def to_dev(b):
         return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
 
+    def dump_outputs(arrays):
+        """--dump-outputs DIR: `arrays` (name -> bytes / uint8 tensor / array, already shaped by the caller) as DIR/<name>.npy in
+        float32 -- every byte of a result is exact there; rank 0 writes (the folded results are the same on every rank)"""
+        if not args.dump_outputs or rank != 0:
+            return
+        import numpy as np
+        out = {}
+        for name, (a, shape) in arrays.items():
+            if isinstance(a, torch.Tensor):
+                a = a.cpu().numpy()
+            elif isinstance(a, (bytes, bytearray)):
+                a = np.frombuffer(a, dtype=np.uint8)
+            out[name] = np.asarray(a, dtype=np.float32).reshape(shape)
+        total = sum(a.nbytes for a in out.values())
+        if total > DUMP_LIMIT:
+            raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
+    def seeded_rows(n, k, seed=0):
+        """a fixed, seeded sample of k of n rows (all of them when n <= k), ascending, as a long tensor on the device"""
+        import numpy as np
+        idx = np.arange(n) if n <= k else np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+        return torch.from_numpy(idx.astype(np.int64)).to(dev)
+
     def sync():
         torch.cuda.synchronize()
         if world > 1:
@@ -593,19 +644,23 @@ def main():
         sync()
         el = time.perf_counter() - t0
         prof = mx.profile_get()
-        mx.profile_enable(True)
-        for _ in range(3):
-            step()
-        if drain:
-            drain()
-        sync()
-        prof_all = mx.profile_get()
+        if args.full:
+            mx.profile_enable(True)
+            for _ in range(3):
+                step()
+            if drain:
+                drain()
+            sync()
+            prof_all = mx.profile_get()
+            timed.totals = {name: ms / 3 for name, ms, cnt in prof_all}   # per step, all launches of the kernel (breakdown pass)
+        else:
+            prof_all = prof                                               # a plain run: the dominant kernel of the timed region only
+            timed.totals = None                                           # (no breakdown pass: no whole-step kernel totals)
         mx.profile_enable(False)
         if world > 1:
             t = torch.tensor([el], dtype=torch.float64, device=coll_dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        timed.totals = {name: ms / 3 for name, ms, cnt in prof_all}   # per step, all launches of the kernel (breakdown pass)
         kern = {name: ms / max(cnt, 1) for name, ms, cnt in prof_all}
         kern.update({name: ms / max(cnt, 1) for name, ms, cnt in prof})  # the dominant kernel: timed region's own average
         timed.dominant = [name for name, ms, cnt in prof]
@@ -721,6 +776,9 @@ def main():
         torch.cuda.synchronize()
         build_s = time.perf_counter() - t_build
         el, kern, _ = timed(step, min_warm_s=leg_warm_s)
+        if args.workload == "kzg_commit":
+            idx = seeded_rows(rows_n, 1 << 16)
+            dump_outputs({"kzg_commits_xy": (d_out.view(rows_n, 64)[idx], (-1, 2, 32)), "kzg_commits_rows": (idx, (-1,))})
         # the reference's own call pattern through the real symbol (one row per compute_digest_from_srs call, 1 and 8 pool threads,
         # Server.hpp:550-560, 1054-1078): the plain-C harness in a child process, linked with -lmultiexp like the reference
         per_call = None
@@ -833,12 +891,13 @@ def main():
 
         el, kern, result = timed(step, drain, min_warm_s=head_warm_s)
         warm_steps_run = timed.warm_steps
+        dump_outputs({"bn254_msm_xy": (result, (2, 32))})      # the job's 64-byte affine result X || Y, big-endian bytes
         fe_mults = msm_fe_mults(n)        # read now: the audit-size MSMs below run with another (window, GLV) shape
         # the same MSM as blocking calls (one in flight): what a caller that waits for every result sees, and ITS per-kernel
         # breakdown (the one above is taken with `depth` MSMs contending for the chip)
         blocking_ms = None
         blocking_kern = None
-        if depth > 1:
+        if depth > 1 and args.full:
             def blocking_step():
                 return mx.msm_device("bn254", d_sc.data_ptr(), d_pt.data_ptr(), n, stream, partial=world > 1)
             reps = max(3, args.steps // 4)
@@ -985,20 +1044,24 @@ def main():
             return fold_across_ranks("bn254", mx.msm_device("bn254", d_sc.data_ptr(), d_pt.data_ptr(), n_local, stream, partial=True))
 
         el, kern, result = timed(step, drain, min_warm_s=leg_warm_s)
+        if args.workload == "strong_2p20":
+            dump_outputs({"strong_2p20_xy": (result, (2, 32))})
         fe_mults = msm_fe_mults(n_local)
-        # blocking calls: the same number of steps on every rank (each one contains the collective)
-        for _ in range(2):
-            blocking_step()
-        sync()
-        t_b = time.perf_counter()
-        for _ in range(args.steps):
-            r_b = blocking_step()
-        sync()
-        blocking_el = time.perf_counter() - t_b
-        if world > 1:
-            t = torch.tensor([blocking_el], dtype=torch.float64, device=coll_dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            blocking_el = float(t.item())
+        blocking_el = None
+        if args.full:
+            # blocking calls: the same number of steps on every rank (each one contains the collective)
+            for _ in range(2):
+                blocking_step()
+            sync()
+            t_b = time.perf_counter()
+            for _ in range(args.steps):
+                r_b = blocking_step()
+            sync()
+            blocking_el = time.perf_counter() - t_b
+            if world > 1:
+                t = torch.tensor([blocking_el], dtype=torch.float64, device=coll_dev)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                blocking_el = float(t.item())
         verified = None
         if rank == 0 and not args.no_cpu:
             verified = common.oracle_msm(sc, pt, total, threads=common.ncpu()) == result == r_b
@@ -1012,8 +1075,8 @@ def main():
                                  "folded on every host; %d MSMs in flight per rank" % (args.log2n, depth),
                      "pairs_total": total, "pairs_per_gpu": n_local, "msm_in_flight": depth, "collective": collective},
                     rl, None, verified, result=result.hex() if result else None,
-                    blocking_ms_per_step=round(blocking_el / args.steps * 1e3, 4),
-                    blocking_Mmul_s=round(total * args.steps / blocking_el / 1e6, 1))
+                    blocking_ms_per_step=round(blocking_el / args.steps * 1e3, 4) if blocking_el else None,
+                    blocking_Mmul_s=round(total * args.steps / blocking_el / 1e6, 1) if blocking_el else None)
 
     # ---------------------------------------------------------------- config 3: ONE 2^24-pair MSM over all ranks
     def leg_config3():
@@ -1062,6 +1125,8 @@ def main():
             return fold_across_ranks("bn254", mx.msm_device("bn254", d_sc.data_ptr(), d_pt.data_ptr(), n_local, stream, partial=True))
 
         el, kern, result = timed(step, min_warm_s=leg_warm_s)
+        if args.workload == "config3":
+            dump_outputs({"config3_xy": (result, (2, 32))})
         launches = max(1, (n_local + (1 << 22) - 1) >> 22)    # an input above 2^22 pairs runs as ranges of 2^22 into one bucket set
         fe_mults = msm_fe_mults(n_local)
         cpu = None
@@ -1117,6 +1182,8 @@ def main():
             return fold_across_ranks("secp256k1", mx.msm_device("secp256k1", d_sc.data_ptr(), d_pt.data_ptr(), n, stream, partial=True))
 
         el, kern, result = timed(step, min_warm_s=leg_warm_s)
+        if args.workload == "secp256k1_msm":
+            dump_outputs({"secp256k1_msm_xy": (result, (2, 32))})
         fe_mults = msm_fe_mults(n)
         cpu = None
         verified = None
@@ -1180,7 +1247,11 @@ def main():
             return None
 
         el, kern, _ = timed(step, min_warm_s=leg_warm_s)
-        total_ms = sum(timed.totals.values())
+        if args.workload == "icc":
+            idx = seeded_rows(n_rows * n_cols, 1 << 14)
+            dump_outputs({"icc_alignment": (d_al.view(-1, 32)[idx], (-1, 32)), "icc_scalars": (d_sc.view(-1, 32)[idx], (-1, 32)),
+                          "icc_elements": (idx, (-1,))})
+        total_ms = sum(timed.totals.values()) if timed.totals else None
         cpu = None
         verified = None
         if rank == 0 and not args.no_cpu and world == 1:
@@ -1212,9 +1283,11 @@ def main():
             rl["note"] = ("an encode is %d launches of the dominant kernel; `achieved` prices the encode's algorithmic bytes / %d "
                           "per launch, `traffic` is the per-launch average of the counters; the kernel is bound by VALU issue "
                           "(profiles/r03_b_icc_stall_counters.txt)" % (passes, passes))
-            rl["launches_per_encode"] = {k: round(timed.totals[k] / v) for k, v in kern.items() if v > 0}
-            rl["whole_encode_kernels_ms"] = round(total_ms, 4)
-            rl["whole_encode_achieved_GBps"] = round(ICC_BYTES_PER_ELEMENT * n_rows * n_cols / (total_ms * 1e-3) / 1e9, 2)
+            # whole-encode figures need the breakdown pass of a --full run; a plain run states none rather than one kernel's
+            rl["launches_per_encode"] = {k: round(timed.totals[k] / v) for k, v in kern.items() if v > 0} if total_ms else None
+            rl["whole_encode_kernels_ms"] = round(total_ms, 4) if total_ms else None
+            rl["whole_encode_achieved_GBps"] = (round(ICC_BYTES_PER_ELEMENT * n_rows * n_cols / (total_ms * 1e-3) / 1e9, 2)
+                                                if total_ms else None)
         return line("ICC encode Melements/s (2^22 Fp elements)", round(world * n_rows * n_cols * args.steps / el / 1e6, 3),
                     "Melements/s", el, "weak", "u32x9 residue pair (mod p_icc, mod q), 30-bit limbs",
                     {"workload": "ICC encode (CRebuild_Cached X part + align_MAC scalars), %d rows x 128 columns per GPU, "
@@ -1553,8 +1626,8 @@ def main():
                  ("data", "synthetic")):
         out.setdefault(k, v)               # (a leg printed alone as the line: the contract's keys it leaves to the line)
     legs_failed = []
-    if args.workload == "bn254_msm":
-        # every other BASELINE.json configuration rides on the default line
+    if args.workload == "bn254_msm" and args.full:
+        # every other BASELINE.json configuration rides on the default line (--full)
         extra = []
         if not args.no_commits:
             extra.append(("kzg_commits", leg_kzg_commit))

@@ -159,3 +159,14 @@ def test_counter_pass_children_do_not_extend_their_warmup():
     assert '"--min-warm-s", "0"' in child and '"--no-pmc"' in child
     timed = src[src.index("    def timed("):src.index("    def breakdown(")]
     assert timed.index("torch.cuda.synchronize()") < timed.index("per = max(")
+
+
+def test_plain_run_options_are_checked_before_any_device_call(tmp_path):
+    """`--full` and `--dump-outputs DIR` are options of every run; a workload without an output dump is refused by the argument
+    check itself (exit 2, no line), before anything touches a device"""
+    r = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, timeout=120, env=_env(), cwd=common.ROOT)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, BENCH, "--workload", "mac_encode", "--dump-outputs", str(tmp_path / "out")], capture_output=True,
+                       text=True, timeout=120, env=_env(), cwd=common.ROOT)
+    assert r.returncode == 2 and "has no output dump" in r.stderr, r.stderr[-1000:]
+    assert not [l for l in r.stdout.splitlines() if l.startswith("{")] and not (tmp_path / "out").exists()

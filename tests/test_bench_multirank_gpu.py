@@ -53,7 +53,7 @@ def test_bench_gpus_2_launches_its_own_ranks(tmp_path):
     env.update(PORLA_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     legs = str(tmp_path / "legs.json")
     cmd = [sys.executable, os.path.join(common.ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-commits",
-           "--legs-out", legs]
+           "--full", "--legs-out", legs]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=common.ROOT)
     d, full = _check_two_rank_line(r, legs)
     c3 = d["config3"]
@@ -71,7 +71,7 @@ def test_two_rank_bench_line_under_an_external_torchrun(tmp_path):
     env = dict(os.environ, PORLA_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(common.ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-commits", "--no-legs", "--legs-out", str(tmp_path / "legs.json")]
+           "--no-commits", "--no-legs", "--full", "--legs-out", str(tmp_path / "legs.json")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=common.ROOT)
     _check_two_rank_line(r, str(tmp_path / "legs.json"))
 
@@ -93,7 +93,7 @@ def test_a_failed_baseline_leg_fails_the_run(tmp_path):
     """a BASELINE-config leg that throws is named in `legs_failed` and the run exits non-zero -- the line is still printed"""
     env = dict(os.environ, PORLA_BENCH_FAIL_LEG="icc")
     r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-commits", "--no-config3",
-                        "--no-cpu", "--no-host-boundary", "--legs-out", str(tmp_path / "legs.json")],
+                        "--no-cpu", "--no-host-boundary", "--full", "--legs-out", str(tmp_path / "legs.json")],
                        capture_output=True, text=True, timeout=600, env=env, cwd=common.ROOT)
     d = _the_line(r, rc=3)
     assert d["legs_failed"] == ["icc"] and "injected" in d["icc"]["error"] and d["value"] > 0
@@ -105,7 +105,7 @@ def test_single_rank_bench_line_prices_the_kernel_it_timed(tmp_path):
     and every leg bit-exact"""
     legs = str(tmp_path / "legs.json")
     r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-commits", "--log2job", "22",
-                        "--legs-out", legs], capture_output=True, text=True, timeout=600, cwd=common.ROOT)
+                        "--full", "--legs-out", legs], capture_output=True, text=True, timeout=600, cwd=common.ROOT)
     c = _the_line(r)
     # the compact line (what the driver parses): the contract's keys, roofline + cpu_baseline, every leg summarised
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -155,7 +155,7 @@ def test_client_mac_batch_and_host_rows_lines(tmp_path):
     """the two figures outside the BASELINE configurations that ride on the default line: the client's block MACs in one batch
     (checked on the oracle's arithmetic, roofline of the evaluation kernel with the committed counter traffic) and the commit
     batch from pageable host rows (same bytes as from device rows)"""
-    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--workload", "client_mac_batch", "--legs-out",
+    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--workload", "client_mac_batch", "--full", "--legs-out",
                         str(tmp_path / "a.json")], capture_output=True, text=True, timeout=600, cwd=common.ROOT)
     d = _the_line(r)
     assert d["bit_exact_vs_oracle"] is True and d["unit"] == "blocks/s" and d["value"] > 1e6
@@ -164,9 +164,85 @@ def test_client_mac_batch_and_host_rows_lines(tmp_path):
     assert rf["traffic"] is None or 0.9 < rf["traffic"] / rf["algorithmic_bytes_per_launch"] < 1.5
     assert d["separate_batches_ms"]["digest_batch"] > 0 and d["kernels_ms"]["fb_commit"] > 0
     r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--workload", "kzg_commit", "--log2rows", "15", "--steps", "3",
-                        "--warmup", "1", "--legs-out", str(tmp_path / "b.json")], capture_output=True, text=True, timeout=600,
+                        "--warmup", "1", "--full", "--legs-out", str(tmp_path / "b.json")], capture_output=True, text=True, timeout=600,
                        cwd=common.ROOT)
     _the_line(r)
     d = json.load(open(str(tmp_path / "b.json")))
     assert d["bit_exact_vs_oracle"] is True
     assert d["host_rows"]["same_bytes_as_device_rows"] is True and d["host_rows"]["commits_per_s"] > 1e5
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_result(tmp_path):
+    """a plain run (no --full): the headline's contract keys, exactly the K timed steps, none of --full's legs or checks, and
+    --dump-outputs writes the last step's 64-byte affine result, which must be the oracle's MSM of the same inputs"""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log2n", "12",
+                        "--dump-outputs", str(out), "--legs-out", str(tmp_path / "legs.json")],
+                       capture_output=True, text=True, timeout=600, cwd=common.ROOT)
+    d = _the_line(r)
+    assert d["metric"].startswith("BN254 G1 MSM") and d["unit"] == "Mmul/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "u32x8 (256-bit modular integer)" and d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert abs(d["value"] - (1 << 12) / d["ms_per_step"] / 1e3) < 0.01 * d["value"]
+    assert d["cpu_baseline"] is None and d["bit_exact_vs_oracle"] is None and d["legs_failed"] == []
+    assert not any(k in d for k in ("kzg_commits", "secp256k1_msm", "icc", "config3", "host_boundary"))
+    xy = np.load(str(out / "bn254_msm_xy.npy"))
+    assert xy.dtype == np.float32 and xy.shape == (2, 32)
+    sc, pt = common.cached_inputs(1 << 12)
+    assert bytes(xy.astype(np.uint8).reshape(-1)) == common.oracle_msm(sc, pt, 1 << 12)
+
+
+def _plain_dump(tmp_path, workload, log2rows):
+    out = tmp_path / workload
+    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--workload", workload, "--log2rows", str(log2rows),
+                        "--steps", "2", "--warmup", "1", "--dump-outputs", str(out), "--legs-out", str(tmp_path / (workload + ".json"))],
+                       capture_output=True, text=True, timeout=600, cwd=common.ROOT)
+    d = _the_line(r)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["cpu_baseline"] is None and d["bit_exact_vs_oracle"] is None
+    return d, out
+
+
+def _device_bytes(seed, n):
+    """the bytes bench.py draws on cuda:0 for its rows (torch.Generator on the device, same seed)"""
+    import torch
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return bytes(torch.randint(0, 256, (n,), dtype=torch.uint8, device="cuda", generator=g).cpu().numpy())
+
+
+def test_plain_kzg_commit_run_dumps_the_oracle_commitments(tmp_path):
+    """--workload kzg_commit --dump-outputs: the last step's commitments of the sampled rows (all rows at this size) are the
+    oracle's compute_digest_from_srs of the same rows against the same SRS"""
+    import ctypes
+    import numpy as np
+    _, out = _plain_dump(tmp_path, "kzg_commit", 11)
+    rows_n = 1 << 11
+    xy, idx = np.load(str(out / "kzg_commits_xy.npy")), np.load(str(out / "kzg_commits_rows.npy"))
+    assert xy.dtype == np.float32 and xy.shape == (rows_n, 2, 32) and (idx == np.arange(rows_n)).all()
+    o = common.oracle()
+    o.oracle_kzg_init_key(bytes.fromhex("ffeeddccbbaa99887766554433221100"), ctypes.c_size_t(16),
+                          bytes.fromhex("00112233445566778899aabbccddeeff"), ctypes.c_size_t(16))
+    o.oracle_kzg_init_srs(ctypes.c_size_t(128), (1).to_bytes(32, "big"))
+    srs = ctypes.create_string_buffer(64 * 128)
+    o.oracle_kzg_srs_g1_raw(srs)
+    want = common.oracle_commit_batch("bn254", _device_bytes(1234, rows_n * 4096), rows_n, 128, srs.raw)
+    assert bytes(xy.astype(np.uint8).reshape(-1)) == want
+
+
+def test_plain_icc_run_dumps_the_oracle_encode(tmp_path):
+    """--workload icc --dump-outputs: the seeded sample of the last step's alignment / scalar outputs equals the oracle's encode
+    of the same rows; a plain run states no whole-encode figures (those need --full's breakdown pass)"""
+    import ctypes
+    import numpy as np
+    d, out = _plain_dump(tmp_path, "icc", 12)
+    n_rows, n_cols = 1 << 10, 128
+    al, sc, idx = (np.load(str(out / (n + ".npy"))) for n in ("icc_alignment", "icc_scalars", "icc_elements"))
+    assert al.shape == sc.shape == (1 << 14, 32) and idx.shape == (1 << 14,) and (np.diff(idx) > 0).all() and idx[-1] < n_rows * n_cols
+    x = ctypes.create_string_buffer(64 * n_rows * n_cols)
+    w_al = ctypes.create_string_buffer(32 * n_rows * n_cols)
+    w_sc = ctypes.create_string_buffer(32 * n_rows * n_cols)
+    common.oracle().oracle_icc_crebuild(_device_bytes(99, n_rows * n_cols * 32), ctypes.c_size_t(n_rows), ctypes.c_size_t(n_cols), 0, 0,
+                                        ctypes.c_uint64(0), x, w_al, w_sc, common.ncpu())
+    pick = idx.astype(np.int64)
+    assert (al.astype(np.uint8) == np.frombuffer(w_al.raw, dtype=np.uint8).reshape(-1, 32)[pick]).all()
+    assert (sc.astype(np.uint8) == np.frombuffer(w_sc.raw, dtype=np.uint8).reshape(-1, 32)[pick]).all()
+    assert d["roofline"].get("whole_encode_kernels_ms") is None and d["roofline"].get("launches_per_encode") is None

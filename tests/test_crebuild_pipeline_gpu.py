@@ -79,7 +79,8 @@ def test_chain_matches_the_oracle_chain(log2rows, write_step):
 
 def test_bench_line_of_the_crebuild_workload():
     """bench.py --workload crebuild: one JSON line in the bench contract, the sample chain bit-exact, the per-kernel split present"""
-    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--workload", "crebuild", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--workload", "crebuild", "--steps", "2", "--warmup", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, cwd=common.ROOT,
                        env=dict(os.environ, PORLA_CREBUILD_LOG2ROWS="12"))
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
