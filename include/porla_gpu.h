@@ -169,6 +169,36 @@ int porla_secp256k1_msm_host_multi(const uint8_t *scalars, const uint8_t *points
 int porla_secp256k1_jac_sum(const uint8_t *jacobians, size_t count, uint8_t out_affine[64]);
 int porla_secp256k1_tree_fold(const uint8_t *sums_affine, int windows, int window_bits, uint8_t out_affine[64]);
 
+/* ---- batched MSM: many independent small MSMs in one call (both curves) ----
+ * K independent MSMs.  Entry k covers pairs [offsets[k], offsets[k+1]) of the concatenated arrays:
+ *   out[k] = sum scalars[i] * points[i] over that range.
+ * Encodings as porla_bn254_msm_device / porla_secp256k1_msm_device: scalars 32-byte big-endian (values >= r allowed, reduced),
+ * points 64-byte X||Y big-endian (64 zero bytes = infinity), each output 64 bytes affine (64 zero bytes = infinity; an empty entry
+ * gives infinity) -- byte for byte what porla_*_msm_device returns for that entry.
+ * offsets is a HOST array of k+1 non-decreasing values with offsets[0] = 0.  Each entry holds at most 32 768 pairs (SMALL_MAX_N);
+ * larger MSMs go through porla_*_msm_device.  d_scalars, d_points and d_out are device pointers; only d_out[0 .. k*64) is written.
+ * Asynchronous: the call enqueues on hip_stream and returns without waiting for this call's work.  The work waits for whatever the
+ * caller had enqueued on hip_stream when it called; d_out is complete when hip_stream is.  The call
+ * never waits on the host for earlier work.
+ * PORLA_ERR_ARG (message in porla_gpu_last_error), checked before the device is touched: offsets not non-decreasing or
+ * offsets[0] != 0, an entry of more than 32 768 pairs, offsets NULL or d_out NULL while k > 0, d_scalars or d_points NULL while
+ * there is at least one pair, a total whose byte size overflows (unreachable within the entry limit, checked all the same).  k = 0 returns 0 and writes nothing.  Without a device, valid
+ * arguments return PORLA_ERR_NO_DEVICE.
+ * Any k and any total that fit in memory: the library cuts the batch into launch rounds of at most 2^18 entries, 2^24 pairs,
+ * 32 768 bucket blocks and 2^20 quads of the tiny-entry kernel; a round is a fixed sequence of launches whatever its K (work-list
+ * upload, counter clear, k_batch_tiny, k_batch_bucket, k_batch_fold, k_fb_finish).  Workspace slots and locking as
+ * porla_*_msm_device; porla_gpu_release_msm_workspaces frees the batch scratch.  porla_gpu_set_msm_glv(0) and the window
+ * override of porla_gpu_set_msm_small apply to the bucket-path entries (> 64 pairs) as to the single-launch MSM; entries of up
+ * to 64 pairs always use the endomorphism-split ladder. */
+int porla_bn254_msm_batch_device(const void *d_scalars, const void *d_points, const uint64_t *offsets, size_t k,
+                                 void *d_out, void *hip_stream);
+int porla_bn254_msm_batch_host(const uint8_t *scalars, const uint8_t *points, const uint64_t *offsets, size_t k,
+                               uint8_t *out);   /* blocking; host buffers; out: k * 64 bytes */
+int porla_secp256k1_msm_batch_device(const void *d_scalars, const void *d_points, const uint64_t *offsets, size_t k,
+                                     void *d_out, void *hip_stream);
+int porla_secp256k1_msm_batch_host(const uint8_t *scalars, const uint8_t *points, const uint64_t *offsets, size_t k,
+                                   uint8_t *out);
+
 /* ---- one process per GPU: the range-sharded MSM across processes (BASELINE config 3) ----
  * Every rank owns a pair range resident in its GPU's HBM, runs a full MSM over it and contributes ONE 96-byte partial
  * Jacobian sum; the only exchange step is one ncclAllGather of world x 96 bytes (RCCL over xGMI, issued from C++ on the

@@ -187,6 +187,35 @@ static int abi_audit_msm_pair(const void* d_store_a, const void* d_store_b, cons
     h_affine_to_bytes<M>(out_b, h_xyzz_to_affine64<M>(tb));
     return PORLA_OK;
 }
+// the batched MSM's argument checks, before anything touches the device
+static int batch_check(const char* curve, const void* scalars, const void* points, const uint64_t* offsets, size_t k, const void* out) {
+    if (k == 0) return PORLA_OK;
+    if (!offsets || !out) { set_last_error("porla: null argument (offsets / output of a batched MSM)"); return PORLA_ERR_ARG; }
+    if (offsets[0] != 0) { set_last_error("porla: batched MSM offsets must start at 0"); return PORLA_ERR_ARG; }
+    for (size_t e = 0; e < k; e++) {
+        if (offsets[e + 1] < offsets[e]) { set_last_error("porla: batched MSM offsets must be non-decreasing"); return PORLA_ERR_ARG; }
+        if (offsets[e + 1] - offsets[e] > SMALL_MAX_N) {
+            set_last_error(std::string("porla: a batched MSM entry holds at most 32768 pairs (entry ") + std::to_string(e) + " has " +
+                           std::to_string(offsets[e + 1] - offsets[e]) + "): use porla_" + curve + "_msm_device for large MSMs");
+            return PORLA_ERR_ARG;
+        }
+    }
+    const uint64_t total = offsets[k];
+    if (total > (uint64_t)(SIZE_MAX / 64) || k > SIZE_MAX / 64) { set_last_error("porla: batched MSM total overflows"); return PORLA_ERR_ARG; }
+    if (total && (!scalars || !points)) { set_last_error("porla: null argument (scalars / points of a batched MSM)"); return PORLA_ERR_ARG; }
+    return PORLA_OK;
+}
+template <class C>
+static int abi_msm_batch(const char* curve, const void* scalars, const void* points, const uint64_t* offsets, size_t k, void* out,
+                         void* stream, bool device) {
+    int rc = batch_check(curve, scalars, points, offsets, k, out);
+    if (rc) return rc;
+    if (k == 0) return PORLA_OK;
+    if (device) {
+        return msm_batch_device<C>((const uint8_t*)scalars, (const uint8_t*)points, offsets, k, (uint8_t*)out, (hipStream_t)stream);
+    }
+    return msm_batch_host<C>((const uint8_t*)scalars, (const uint8_t*)points, offsets, k, (uint8_t*)out);
+}
 template <class C>
 static int abi_msm_host_multi(const uint8_t* scalars, const uint8_t* points, size_t n, int shards, int devices, uint8_t* out) {
     using M = typename C::Fp;
@@ -302,8 +331,24 @@ int porla_gpu_release_msm_workspaces(void) {
         (void)hipSetDevice(w->device);
         Buf* bufs[] = {&w->pts, &w->keys, &w->entries, &w->counts, &w->starts, &w->fill, &w->cursor, &w->buckets, &w->in_scalars,
                        &w->in_points, &w->order, &w->blk_hist, &w->blk_off, &w->tile_off, &w->heavy, &w->chunk_out, &w->tree_s,
-                       &w->tree_m, &w->tree_mt, &w->small_part, &w->multi_acc};
+                       &w->tree_m, &w->tree_mt, &w->small_part, &w->multi_acc, &w->batch_list, &w->batch_part, &w->batch_sums,
+                       &w->batch_ctrl, &w->batch_out};
         for (Buf* b : bufs) b->release();
+        if (w->batch_upload) {
+            (void)hipEventSynchronize(w->batch_upload);
+            (void)hipEventDestroy(w->batch_upload);
+            w->batch_upload = nullptr;
+        }
+        if (w->h_batch) (void)hipHostFree(w->h_batch);
+        w->h_batch = nullptr;
+        w->h_batch_cap = 0;
+        for (auto& rb : w->batch_retired) {
+            (void)hipEventSynchronize(rb.second);
+            (void)hipHostFree(rb.first);
+            (void)hipEventDestroy(rb.second);
+        }
+        w->batch_retired.clear();
+        w->batch_fence.reset();
     }
     (void)hipSetDevice(cur);
     unlock_all();
@@ -382,6 +427,18 @@ int porla_diag_fe_op(int op, int modulus, const uint8_t a_le[32], const uint8_t 
 
 int porla_bn254_msm_device(const void* d_scalars, const void* d_points, size_t n, uint8_t out_affine[64], void* s) {
     return abi_msm_device<Bn254G1>(d_scalars, d_points, n, out_affine, s, false);
+}
+int porla_bn254_msm_batch_device(const void* d_scalars, const void* d_points, const uint64_t* offsets, size_t k, void* d_out, void* s) {
+    return abi_msm_batch<Bn254G1>("bn254", d_scalars, d_points, offsets, k, d_out, s, true);
+}
+int porla_bn254_msm_batch_host(const uint8_t* scalars, const uint8_t* points, const uint64_t* offsets, size_t k, uint8_t* out) {
+    return abi_msm_batch<Bn254G1>("bn254", scalars, points, offsets, k, out, nullptr, false);
+}
+int porla_secp256k1_msm_batch_device(const void* d_scalars, const void* d_points, const uint64_t* offsets, size_t k, void* d_out, void* s) {
+    return abi_msm_batch<Secp256k1G>("secp256k1", d_scalars, d_points, offsets, k, d_out, s, true);
+}
+int porla_secp256k1_msm_batch_host(const uint8_t* scalars, const uint8_t* points, const uint64_t* offsets, size_t k, uint8_t* out) {
+    return abi_msm_batch<Secp256k1G>("secp256k1", scalars, points, offsets, k, out, nullptr, false);
 }
 int porla_bn254_msm_device_partial(const void* d_scalars, const void* d_points, size_t n, uint8_t out_jac[96], void* s) {
     return abi_msm_device<Bn254G1>(d_scalars, d_points, n, out_jac, s, true);

@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <mutex>
 #include <string>
+#include <utility>
+#include <vector>
 #include "../../include/porla_gpu.h"
 #include "host_curve.hpp"
 #include "msm.hip.h"
@@ -55,6 +57,12 @@ int msm_pair_end(int slot, XYZZ<typename C::Fp>* total_a, XYZZ<typename C::Fp>* 
 template <class C>
 int msm_pair_host(const uint8_t* scalars, const uint8_t* points_a, const uint8_t* points_b, size_t n, XYZZ<typename C::Fp>* total_a,
                   XYZZ<typename C::Fp>* total_b);
+// K independent MSMs over concatenated arrays, entry e = pairs [offsets[e], offsets[e + 1]) (<= SMALL_MAX_N each), affine
+// big-endian results into d_out (msm_batch_impl.hip.h); arguments checked by the caller
+template <class C>
+int msm_batch_device(const uint8_t* d_scalars, const uint8_t* d_points, const uint64_t* offsets, size_t k, uint8_t* d_out, hipStream_t stream);
+template <class C>
+int msm_batch_host(const uint8_t* scalars, const uint8_t* points, const uint64_t* offsets, size_t k, uint8_t* out);
 template <class C>
 int msm_device_begin(int slot, const uint8_t* d_scalars, const uint8_t* d_points, size_t n, hipStream_t stream);
 template <class C>
@@ -137,6 +145,16 @@ struct Workspace {
     bool lone = false;          // the caller waits for this MSM (blocking entry points): the reduction tree may use two streams
     bool pair_pending = false;  // the begun launch is a pair (msm_pair_gather_begin): two result regions, msm_pair_end collects them
     bool begun = false;         // two-phase API: a begin without its end (also set for n == 0, where pend_W stays 0)
+    // batched MSM (msm_batch_impl.hip.h): work list, the bucket blocks' partial + window sums, the entries' sums, counters +
+    // shapes, the host form's output; the pinned work list and the event of its upload (a call that finds that copy still queued
+    // retires the buffer -- freed once the copy is done -- and takes a new one); the fence orders the scratch between calls on
+    // different streams
+    Buf batch_list, batch_part, batch_sums, batch_ctrl, batch_out;
+    void* h_batch = nullptr;
+    size_t h_batch_cap = 0;
+    hipEvent_t batch_upload = nullptr;
+    std::vector<std::pair<void*, hipEvent_t>> batch_retired;
+    UseFence batch_fence;
 };
 // workspace slots per device -- 0: blocking calls, 1..3: the two-phase C ABI, 4..7: msm_host_multi's pipeline,
 // 8..15: taken by blocking calls that find slot 0 busy (the reference issues its IPA MSMs from 8 pool threads at once,

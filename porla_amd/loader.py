@@ -75,6 +75,9 @@ def _declare(L):
         f = getattr(L, "porla_%s_audit_msm_pair_begin" % curve); f.argtypes = [ctypes.c_int, vp, vp, vp, vp, sz, vp]; f.restype = ctypes.c_int
         f = getattr(L, "porla_%s_audit_msm_pair_end" % curve); f.argtypes = [ctypes.c_int, u8p, u8p]; f.restype = ctypes.c_int
         f = getattr(L, "porla_%s_msm_pair_host" % curve); f.argtypes = [u8p, u8p, u8p, sz, u8p, u8p]; f.restype = ctypes.c_int
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        f = getattr(L, "porla_%s_msm_batch_device" % curve); f.argtypes = [vp, vp, u64p, sz, vp, vp]; f.restype = ctypes.c_int
+        f = getattr(L, "porla_%s_msm_batch_host" % curve); f.argtypes = [u8p, u8p, u64p, sz, u8p]; f.restype = ctypes.c_int
         f = getattr(L, "porla_%s_msm_host_multi" % curve); f.argtypes = [u8p, u8p, sz, ctypes.c_int, ctypes.c_int, u8p]; f.restype = ctypes.c_int
         f = getattr(L, "porla_%s_dist_fold" % curve); f.argtypes = [u8p, u8p]; f.restype = ctypes.c_int
         f = getattr(L, "porla_%s_msm_device_dist" % curve); f.argtypes = [vp, vp, sz, u8p, vp]; f.restype = ctypes.c_int

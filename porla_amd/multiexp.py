@@ -200,6 +200,48 @@ def msm_pair_host(curve, scalars, points_a, points_b, n):
     return oa.raw, ob.raw
 
 
+def batch_offsets(sizes):
+    """the offsets array of a batched MSM from its entries' sizes: [0, s0, s0 + s1, ...]"""
+    offs = [0]
+    for s in sizes:
+        if s < 0:
+            raise ValueError("a batched MSM entry cannot have %d pairs" % s)
+        offs.append(offs[-1] + int(s))
+    return offs
+
+
+def _offsets_array(offsets):
+    import array
+    a = array.array("Q", offsets)           # one C-level conversion (a batch of 32 842 entries: well under a millisecond)
+    if not len(a):
+        raise ValueError("offsets holds k + 1 values (at least [0])")
+    return (ctypes.c_uint64 * len(a)).from_buffer(a), len(a) - 1
+
+
+def split_outputs(raw, k):
+    """k 64-byte affine outputs from one k * 64-byte buffer"""
+    raw = bytes(raw)
+    if len(raw) < 64 * k:
+        raise ValueError("%d bytes hold fewer than %d outputs" % (len(raw), k))
+    return [raw[64 * i:64 * (i + 1)] for i in range(k)]
+
+
+def msm_batch_device(curve, d_scalars, d_points, offsets, d_out, stream=0):
+    """K independent MSMs in one call (include/porla_gpu.h): entry k = pairs [offsets[k], offsets[k+1]) of the device arrays,
+    its 64-byte affine result written to d_out + 64 k.  Asynchronous on `stream`: d_out is complete when the stream is."""
+    arr, k = _offsets_array(offsets)
+    _check(getattr(lib, "porla_%s_msm_batch_device" % curve)(ctypes.c_void_p(d_scalars), ctypes.c_void_p(d_points), arr, k,
+                                                             ctypes.c_void_p(d_out), ctypes.c_void_p(stream)))
+
+
+def msm_batch_host(curve, scalars, points, offsets):
+    """the same from host bytes, blocking: a list of k 64-byte outputs"""
+    arr, k = _offsets_array(offsets)
+    out = ctypes.create_string_buffer(64 * k if k else 1)
+    _check(getattr(lib, "porla_%s_msm_batch_host" % curve)(bytes(scalars), bytes(points), arr, k, out))
+    return split_outputs(out.raw, k)
+
+
 def msm_host_multi(curve, scalars, points, n, shards=0, devices=0):
     """range-sharded over `shards` pair ranges and `devices` GPUs of this process (0 = automatic), behind the C ABI"""
     out = ctypes.create_string_buffer(64)
