@@ -341,7 +341,8 @@ k_mac_stage30(XYZZ<typename C::Fp>* __restrict__ work, const uint32_t* __restric
 // Below N = 2^16 rows a stage is one lone wave per SIMD walking a ladder of ~200 dependent group operations: its time is the
 // latency of those operations (1.08 ms with one lane per butterfly).  Here every group operation runs on the four lanes of a
 // quad (ec30.hip.h: 4 rounds of products per addition, 3 per doubling, instead of 14 / 9 in sequence).  The ladder is the same
-// (endomorphism split, 33 signed 4-bit windows, one table of multiples 1 .. 8 of P).
+// (endomorphism split, 33 signed 4-bit windows, one table of multiples 1 .. 8 of P): quad30.hip.h:macq_ladder, shared with the
+// batched MSM's tiny entries.
 // Round 5: the ACCUMULATOR LIVES IN REGISTERS (lane r of the quad holds coordinate r: xyzz30_dbl_quadreg / xyzz30_add_quadreg);
 // LDS holds only what is read at random: the table of multiples (memory form) and, beside it, the table's X coordinates times
 // beta -- the endomorphism's half reads its X there, so phi(d P) costs no product per addition (8 products once instead of one
@@ -383,62 +384,6 @@ __device__ __forceinline__ void macq_copy_coord(XYZZ<M>* dst, const XYZZ<M>* src
     uint4* d = reinterpret_cast<uint4*>(reinterpret_cast<uint32_t*>(dst) + 8 * r);
     const uint4 v0 = a[0], v1 = a[1];
     d[0] = v0; d[1] = v1;
-}
-// (c, inf) = sc * P on the four lanes of quad q; P = L.qd[q].tbl[0] (memory form, written by this quad's lanes, macq_sync or a
-// block barrier passed).  Lane r ends with coordinate r of the product; `inf` is the same on the four lanes.
-template <class C>
-__device__ __forceinline__ void macq_ladder(MacQuadLds<typename C::Fp>& L, uint32_t q, uint32_t r, uint32_t lane, const uint32_t sc[8],
-                                            F30<typename C::Fp>& c, bool& inf) {
-    using M = typename C::Fp;
-    using G = typename C::Glv;
-    typename MacQuadLds<M>::Quad& Q = L.qd[q];
-    inf = true;
-    bool z;
-    c = macq_load_residue<M>(reinterpret_cast<const uint32_t*>(&Q.tbl[0]) + 8 * r, &z);
-    if (macq_quad_any(z && r == 2u, lane)) return;                         // P is infinity: so is every multiple
-    uint32_t m0[4], m1[4];
-    bool ng0, ng1;
-    glv_split<G>(sc, m0, ng0, m1, ng1);
-    // tbl[i] = (i + 1) P: one doubling, six additions of P
-    bool tinf = false;
-    xyzz30_dbl_quadreg<M>(c, r);
-    macq_store_residue<M>(reinterpret_cast<uint32_t*>(&Q.tbl[1]) + 8 * r, c);
-#pragma unroll 1
-    for (int i = 2; i < 8; i++) {
-        macq_add<M>(c, tinf, &Q.tbl[0], reinterpret_cast<const uint32_t*>(&Q.tbl[0]), false, &L.acc[q], &L.tmp[q], r, lane);
-        macq_store_residue<M>(reinterpret_cast<uint32_t*>(&Q.tbl[i]) + 8 * r, c);
-    }
-    macq_sync();
-    // beta * X of the eight entries: two per lane
-    {
-        const F30<M> beta30 = f30_const<M>(G::BETA_30);
-#pragma unroll 1
-        for (int t = 0; t < 2; t++) {
-            const uint32_t e = r + 4u * (uint32_t)t;
-            const F30<M> x = macq_load_residue<M>(reinterpret_cast<const uint32_t*>(&Q.tbl[e]), &z);
-            macq_store_residue<M>(&Q.bx[e][0], f30_mul<M>(x, beta30));
-        }
-    }
-    macq_sync();
-#pragma unroll 1
-    for (int i = 32; i >= 0; i--) {
-        if (!inf) {
-#pragma unroll 1
-            for (int d = 0; d < 4; d++) xyzz30_dbl_quadreg<M>(c, r);
-        }
-#pragma unroll 1
-        for (int h = 0; h < 2; h++) {
-            uint32_t mh[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) mh[j] = h ? m1[j] : m0[j];
-            const int dg = mac_signed_digit(mh, i);
-            if (dg == 0) continue;
-            const uint32_t mag = (uint32_t)(dg < 0 ? -dg : dg) - 1u;
-            const XYZZ<M>* e = &Q.tbl[mag];
-            macq_add<M>(c, inf, e, h ? &Q.bx[mag][0] : reinterpret_cast<const uint32_t*>(e), (dg < 0) != (h ? ng1 : ng0), &L.acc[q],
-                        &L.tmp[q], r, lane);
-        }
-    }
 }
 // ---- the ladder when all 16 quads of a wave multiply by the SAME scalar (stages with >= 16 butterflies per twiddle: all but the
 // last four of a network).  Control flow is then the wave's, so a zero digit really costs nothing and the recoding can be sparse:
@@ -590,7 +535,7 @@ k_mac_stage30_quad(XYZZ<typename C::Fp>* __restrict__ work, const uint32_t* __re
     bool inf;
     if constexpr (UNIFORM) macq_ladder_uniform<C>(L, q, r, lane, threadIdx.x >> 6, sc, c, inf,
                                                    codes + (size_t)(e >> MACQ_CODES_EXP_SHIFT) * MACQ_CODES_STRIDE);
-    else macq_ladder<C>(L, q, r, lane, sc, c, inf);
+    else macq_ladder<C>(L.qd[q], &L.acc[q], &L.tmp[q], r, lane, sc, c, inf);
     // MAC[k] = um + tm, MAC[k + m2] = um - tm
     macq_butterfly_out<M>(&L.um[q], &L.acc[q], &L.tmp[q], c, inf, work + k, work + k + m2, valid, r, lane);
 }
@@ -924,7 +869,7 @@ k_mac_mix_quad(const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1, u
     macq_sync();
     F30<M> c;
     bool inf;
-    macq_ladder<C>(L, q, r, lane, sc, c, inf);
+    macq_ladder<C>(L.qd[q], &L.acc[q], &L.tmp[q], r, lane, sc, c, inf);
     macq_butterfly_out<M>(&L.um[q], &L.acc[q], &L.tmp[q], c, inf, &L.qd[q].tbl[1], &L.qd[q].tbl[2], true, r, lane);      // sum, difference (the table is done with)
     macq_sync();
     if (valid && r < 2u)                                                           // the two inversions side by side

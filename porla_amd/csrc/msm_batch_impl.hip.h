@@ -18,7 +18,7 @@ struct BatchRound {
 // bucket blocks of an entry of n pairs: `lone` = what a lone k_small_msm takes (msm_impl.hip.h), else ceil(n / 64) and at least
 // bmin (> the windows' count of every shape small_cfg can pick, so that every window has a block)
 static inline uint32_t batch_blocks(uint64_t n, bool lone, uint32_t bmin) {
-    const uint32_t cap = n <= 4096 ? 192u : (uint32_t)SMALL_BLOCKS;
+    const uint32_t cap = small_lone_blocks(n);
     if (lone) return cap;
     uint32_t b = (uint32_t)((n + 63) / 64);
     if (b < bmin) b = bmin;

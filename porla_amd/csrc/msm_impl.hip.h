@@ -95,14 +95,21 @@ static inline int choose_window(size_t m, int bits) {
     return best;
 }
 
-// the single-launch path of msm_small.hip.h (n <= SMALL_MAX_N): one kernel, results + shape written to pinned memory
+// The single-launch path of msm_small.hip.h (n <= SMALL_MAX_N): one kernel, results + shape written to pinned memory.
+// The audit's pair of MSMs -- ONE scalar array over TWO point arrays (bn254_multi_exp(combined_MAC, ptc, sc, n) and
+// bn254_multi_exp(combined_align, pta, sc, n), porla/Server/Server.hpp:900-901; the IPA twins :842-848) -- is one launch of it
+// (d_points_b non-null): half of the chip's blocks per point set.  Both are chains of ~15 dependent additions, so side by side
+// they take little longer than one alone.  Results: one region of the slot's pinned area per set, PAIR_STRIDE bytes apart.
+constexpr uint32_t SMALL_PAIR_STRIDE = 64 * 1024;
 template <class C>
-static int msm_small_launch(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_points_be, size_t n, hipStream_t stream) {
+static int msm_small_pair_launch(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_points_a, const uint8_t* d_points_b, size_t n,
+                                 hipStream_t stream, int bits_hint = 0) {
     using M = typename C::Fp;
     int rc;
-    if (ws->h_windows_cap < 64 * 1024) {
+    const uint32_t sets = d_points_b ? 2u : 1u;
+    if (ws->h_windows_cap < sets * SMALL_PAIR_STRIDE) {
         if (ws->h_windows) PORLA_HIP(hipHostFree(ws->h_windows));
-        ws->h_windows_cap = 64 * 1024;
+        ws->h_windows_cap = sets * SMALL_PAIR_STRIDE;
         PORLA_HIP(hipHostMalloc(&ws->h_windows, ws->h_windows_cap, hipHostMallocMapped | hipHostMallocCoherent));
     }
     const size_t part_bytes = (size_t)SMALL_BLOCKS * SMALL_MAX_C * sizeof(XYZZ<M>);
@@ -115,66 +122,30 @@ static int msm_small_launch(Workspace* ws, const uint8_t* d_scalars, const uint8
     uint32_t* counters = (uint32_t*)((uint8_t*)ws->small_part.p + part_bytes);
     ws->small_seq++;
     if (ws->small_seq == 0) ws->small_seq = 1;
-    ((volatile uint32_t*)ws->h_windows)[0] = 0;
+    for (uint32_t set = 0; set < sets; set++) ((volatile uint32_t*)((uint8_t*)ws->h_windows + set * SMALL_PAIR_STRIDE))[0] = 0;
     {
         ProfScope ps("small_msm", stream, true);
-        // up to 4 096 pairs 192 blocks are as fast as 256 (3 200 pairs: 0.1045 / 0.1046 ms with abs(int32) coefficients, 0.163 / 0.171
-        // with 256-bit scalars; 16 384 pairs: 0.284 against 0.262) and leave a quarter of the chip to whatever short kernels run
-        // beside this one
-        const unsigned one_blocks = n <= 4096 ? 192u : (unsigned)SMALL_BLOCKS;
-        hipLaunchKernelGGL((k_small_msm<C>), dim3(one_blocks), dim3(SMALL_THREADS), 0, stream, d_scalars, d_points_be, (uint32_t)n,
-                           g_small_c | (g_use_glv == 0 ? 0x100 : 0), (XYZZ<M>*)ws->small_part.p, counters, (uint32_t*)h_dev,
-                           (XYZZ<M>*)((uint8_t*)h_dev + SMALL_HDR_WORDS * 4), ws->small_seq, (const uint8_t*)nullptr, 0u);
-    }
-    PORLA_HIP(hipGetLastError());
-    if (!ws->done) PORLA_HIP(hipEventCreateWithFlags(&ws->done, hipEventDisableTiming));
-    PORLA_HIP(hipEventRecord(ws->done, stream));
-    ws->pend_W = -1;            // shape known to the device only: read from the pinned header by msm_finish
-    ws->pend_c = 0;
-    return PORLA_OK;
-}
-
-// The audit's pair of MSMs -- ONE scalar array over TWO point arrays (bn254_multi_exp(combined_MAC, ptc, sc, n) and
-// bn254_multi_exp(combined_align, pta, sc, n), porla/Server/Server.hpp:900-901; the IPA twins :842-848) -- as one launch of the
-// single-launch kernel: half of the chip's blocks per point set.  Both are chains of ~15 dependent additions, so side by side
-// they take little longer than one alone.  Results: two regions of the slot's pinned area, PAIR_STRIDE bytes apart.
-constexpr uint32_t SMALL_PAIR_STRIDE = 64 * 1024;
-template <class C>
-static int msm_small_pair_launch(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_points_a, const uint8_t* d_points_b, size_t n,
-                                 hipStream_t stream, int bits_hint = 0) {
-    using M = typename C::Fp;
-    int rc;
-    if (ws->h_windows_cap < 2 * SMALL_PAIR_STRIDE) {
-        if (ws->h_windows) PORLA_HIP(hipHostFree(ws->h_windows));
-        ws->h_windows_cap = 2 * SMALL_PAIR_STRIDE;
-        PORLA_HIP(hipHostMalloc(&ws->h_windows, ws->h_windows_cap, hipHostMallocMapped | hipHostMallocCoherent));
-    }
-    const size_t part_bytes = (size_t)SMALL_BLOCKS * SMALL_MAX_C * sizeof(XYZZ<M>);
-    if (ws->small_part.cap < part_bytes + 2048) {
-        if ((rc = ws->small_part.ensure(part_bytes + 2048))) return rc;
-        PORLA_HIP(hipMemsetAsync(ws->small_part.p, 0, part_bytes + 2048, stream));    // arrival counters of both sets start at zero
-    }
-    void* h_dev = nullptr;
-    PORLA_HIP(hipHostGetDevicePointer(&h_dev, ws->h_windows, 0));
-    uint32_t* counters = (uint32_t*)((uint8_t*)ws->small_part.p + part_bytes);
-    ws->small_seq++;
-    if (ws->small_seq == 0) ws->small_seq = 1;
-    ((volatile uint32_t*)ws->h_windows)[0] = 0;
-    ((volatile uint32_t*)((uint8_t*)ws->h_windows + SMALL_PAIR_STRIDE))[0] = 0;
-    {
-        ProfScope ps("small_msm", stream, true);
-        // blocks per point set: at the audit's sizes 96 (192 of the chip's 256 compute units) -- the sets are as fast as with 128 each
-        // (0.120 against 0.124 ms at 3 200 pairs) and the audit's other chain, which runs beside this kernel (row combine, the
+        // blocks per point set of a pair: at the audit's sizes 96 (192 of the chip's 256 compute units) -- the sets are as fast as with
+        // 128 each (0.120 against 0.124 ms at 3 200 pairs) and the audit's other chain, which runs beside this kernel (row combine, the
         // three commitments: short launches that need a compute unit NOW), no longer queues behind 256 long-lived blocks:
         // 0.183 -> 0.151 ms per audit
-        const unsigned pair_blocks = n <= 8192 ? 96u : (unsigned)SMALL_BLOCKS / 2;
-        hipLaunchKernelGGL((k_small_msm<C>), dim3(pair_blocks, 2), dim3(SMALL_THREADS), 0, stream, d_scalars, d_points_a, (uint32_t)n,
+        const unsigned blocks = d_points_b ? (n <= 8192 ? 96u : (unsigned)SMALL_BLOCKS / 2) : small_lone_blocks(n);
+        hipLaunchKernelGGL((k_small_msm<C>), dim3(blocks, sets), dim3(SMALL_THREADS), 0, stream, d_scalars, d_points_a, (uint32_t)n,
                            g_small_c | (g_use_glv == 0 ? 0x100 : 0) | (bits_hint << 16), (XYZZ<M>*)ws->small_part.p, counters,
                            (uint32_t*)h_dev, (XYZZ<M>*)((uint8_t*)h_dev + SMALL_HDR_WORDS * 4), ws->small_seq, d_points_b, SMALL_PAIR_STRIDE);
     }
     PORLA_HIP(hipGetLastError());
     if (!ws->done) PORLA_HIP(hipEventCreateWithFlags(&ws->done, hipEventDisableTiming));
     PORLA_HIP(hipEventRecord(ws->done, stream));
+    return PORLA_OK;
+}
+// one MSM: the one-set case of the pair launch
+template <class C>
+static int msm_small_launch(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_points_be, size_t n, hipStream_t stream) {
+    const int rc = msm_small_pair_launch<C>(ws, d_scalars, d_points_be, nullptr, n, stream);
+    if (rc) return rc;
+    ws->pend_W = -1;            // shape known to the device only: read from the pinned header by msm_finish
+    ws->pend_c = 0;
     return PORLA_OK;
 }
 // waits for set `which` (0, 1) of a pair launch and folds its window sums on the host

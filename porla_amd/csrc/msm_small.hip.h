@@ -42,6 +42,12 @@ constexpr int SMALL_MAX_S = 32;                      // slices per window: S * c
 constexpr int SMALL_DONE_SLOT = 255;                 // counters[0 .. W): arrivals per window; [255]: finished windows
 constexpr uint32_t SMALL_HDR_WORDS = 32;             // pinned header in front of fin: [0] = sequence, [1] = W, [2] = c, [3] = glv
 
+// blocks of a lone single-launch MSM of n pairs (msm_impl.hip.h) -- and of a batch entry when the batch leaves the chip idle
+// (msm_batch_impl.hip.h): up to 4 096 pairs 192 blocks are as fast as 256 (3 200 pairs: 0.1045 / 0.1046 ms with abs(int32)
+// coefficients, 0.163 / 0.171 with 256-bit scalars; 16 384 pairs: 0.284 against 0.262) and leave a quarter of the chip to whatever
+// short kernels run beside this one
+inline uint32_t small_lone_blocks(uint64_t n) { return n <= 4096 ? 192u : (uint32_t)SMALL_BLOCKS; }
+
 // the single-launch commitment of fixed_base.hip.h (k_fb_commit_small): rows per launch, slices per row
 constexpr int FB_SMALL_MAX_ROWS = 64;            // 64 rows x 8 slices = 512 blocks, two per compute unit (96 rows: 0.19 ms, the batch kernels 0.22)
 constexpr int FB_SMALL_MAX_SLICES = 8;
@@ -121,30 +127,34 @@ __device__ __forceinline__ void small_quad_adds(uint32_t tasks, F get) {
 
 // phase stamps of one block for tools/small_stamps.hip (never compiled into the library)
 #ifdef PORLA_SMALL_STAMPS
-#define SMALL_STAMP(k) do { if (threadIdx.x == 0) stamps[(size_t)blockIdx.x * 16 + (k)] = wall_clock64(); } while (0)
+#define SMALL_STAMP(k) do { if (threadIdx.x == 0 && stamps) stamps[(size_t)blockIdx.x * 16 + (k)] = wall_clock64(); } while (0)
 #define SMALL_STAMP_ARG , unsigned long long* __restrict__ stamps
+#define SMALL_STAMP_PASS(p) , (p)
 #else
 #define SMALL_STAMP(k) do { } while (0)
 #define SMALL_STAMP_ARG
+#define SMALL_STAMP_PASS(p)
 #endif
 
-template <class C>
-__global__ void __launch_bounds__(SMALL_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_small_msm(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ points, uint32_t n, int c_override,
-            XYZZ<typename C::Fp>* __restrict__ part, uint32_t* __restrict__ counters, uint32_t* __restrict__ hdr,
-            XYZZ<typename C::Fp>* __restrict__ fin, uint32_t seq, const uint8_t* __restrict__ points_b,
-            uint32_t pair_stride_bytes SMALL_STAMP_ARG) {
+// what the block body hands its kernel's epilogue: the shape, the block's window and -- for the LAST block of that window to
+// arrive, null for every other -- the window's c folded sums (S, M_0 .. M_(c-2), memory form) in LDS
+template <class M>
+struct SmallWindow {
+    SmallCfg g;
+    uint32_t w;
+    const XYZZ<M>* sums;
+};
+
+// Steps 0 - 4 of a block of k_small_msm and of k_batch_bucket (msm_batch.hip.h): block bx of the `blocks` that ONE MSM of n pairs
+// has been given.  c_flags: as small_cfg takes them; bits_hint: a bound on the scalars' bit length the caller knows (0: scan them).
+// part: the MSM's partial sums, SMALL_MAX_C per block; counters: its arrival counter per window, zero on entry and zero again once
+// the window's last block has arrived.  admit(g) runs on every lane as soon as the shape is known: false sends the block away.
+template <class C, class Admit>
+__device__ __forceinline__ SmallWindow<typename C::Fp> small_block(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ points,
+                                                                   uint32_t n, uint32_t bx, int blocks, int c_flags, int bits_hint,
+                                                                   XYZZ<typename C::Fp>* __restrict__ part, uint32_t* __restrict__ counters,
+                                                                   Admit admit SMALL_STAMP_ARG) {
     using M = typename C::Fp;
-    // gridDim.y == 2: the audit's PAIR of MSMs -- the same scalars over two point sets (combined_MAC and combined_align,
-    // porla/Server/Server.hpp:842-848 / :900-901) -- in one launch: set blockIdx.y takes its own points, partial sums, arrival
-    // counters and pinned result region (header + window sums at pair_stride_bytes); each set shapes itself for gridDim.x blocks
-    if (blockIdx.y) {
-        points = points_b;
-        part += (size_t)gridDim.x * SMALL_MAX_C;
-        counters += 256;
-        hdr = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(hdr) + pair_stride_bytes);
-        fin = reinterpret_cast<XYZZ<M>*>(reinterpret_cast<uint8_t*>(fin) + pair_stride_bytes);
-    }
     __shared__ uint32_t ent[SMALL_MAX_SUB];                    // sorted entries: sub-scalar index | sign << 31
     __shared__ XYZZ<M> pts[SMALL_THREADS];                     // first the unsorted digits (uint32 view), then the lane sums
     __shared__ XYZZ<M> bk[SMALL_MAX_B];                        // bucket sums
@@ -157,9 +167,7 @@ k_small_msm(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ poi
     uint32_t* raw = reinterpret_cast<uint32_t*>(pts);          // SMALL_THREADS * 32 words >= SMALL_MAX_SUB
 
     SMALL_STAMP(0);
-    // ---- 0. bit length of the scalars (every block for itself) -- unless the caller knows a bound: bits 16..24 of c_override (the
-    // audit's coefficients are abs(int32), expanded to 32-byte scalars by k_audit_gather: 32 bits, no scan -- ~10 us of a ~100 us kernel)
-    const int bits_hint = (c_override >> 16) & 0x1ff;
+    // ---- 0. bit length of the scalars (every block for itself) -- unless the caller knows a bound
     if (tid < 8) orw[tid] = 0;
     if (tid < SMALL_MAX_B) hist[tid] = 0;
     __syncthreads();
@@ -194,9 +202,9 @@ k_small_msm(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ poi
         for (int k = 7; k >= 0; k--)
             if (used == 0 && orw[k]) used = 32 * k + (32 - __clz(orw[k]));
     }
-    const SmallCfg g = small_cfg<C>(n, used, c_override, (int)gridDim.x);
-    if (blockIdx.x >= (uint32_t)(g.W * g.S)) return;
-    const uint32_t w = blockIdx.x / g.S, s = blockIdx.x % g.S;
+    const SmallCfg g = small_cfg<C>(n, used, c_flags, blocks);
+    if (!admit(g) || bx >= (uint32_t)(g.W * g.S)) return {g, 0, nullptr};
+    const uint32_t w = bx / g.S, s = bx % g.S;
     const int c = g.c;
     const uint32_t mask = (1u << c) - 1;
     const uint32_t Bfull = 1u << (c - 1);
@@ -385,7 +393,7 @@ k_small_msm(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ poi
     SMALL_STAMP(6);
     // the block's c sums: S, M_0 .. M_(c-2)  (the last one the tree produces is the alias S^(nlev-2)[1] -- or bucket 1 when there
     // is one level; the top window's sums beyond its own width are infinity = zero words)
-    XYZZ<M>* mine = part + (size_t)blockIdx.x * SMALL_MAX_C;
+    XYZZ<M>* mine = part + (size_t)bx * SMALL_MAX_C;
     if (tid < (uint32_t)c * 8) {
         const uint32_t kk = tid >> 3, q = tid & 7;             // 8 lanes copy the 128 bytes of sum kk
         const XYZZ<M>* src = nullptr;
@@ -405,7 +413,7 @@ k_small_msm(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ poi
         if (last_flag) counters[w] = 0;                        // ready for the next launch on this workspace
     }
     __syncthreads();
-    if (!last_flag) return;
+    if (!last_flag) return {g, w, nullptr};
     __threadfence();
     SMALL_STAMP(8);
     // the S * c sums of the window come into LDS in one pass (slice sl, sum k at pts[sl * c + k]; S <= SMALL_MAX_S)
@@ -429,16 +437,43 @@ k_small_msm(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ poi
         __syncthreads();
         cnt = half;
     }
-    if (tid < (uint32_t)c) Node<C>::store_final(fin + (size_t)w * c + tid, Node<C>::load(&pts[tid]));
+    return {g, w, pts};
+}
+
+template <class C>
+__global__ void __launch_bounds__(SMALL_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
+k_small_msm(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ points, uint32_t n, int c_override,
+            XYZZ<typename C::Fp>* __restrict__ part, uint32_t* __restrict__ counters, uint32_t* __restrict__ hdr,
+            XYZZ<typename C::Fp>* __restrict__ fin, uint32_t seq, const uint8_t* __restrict__ points_b,
+            uint32_t pair_stride_bytes SMALL_STAMP_ARG) {
+    using M = typename C::Fp;
+    // gridDim.y == 2: the audit's PAIR of MSMs -- the same scalars over two point sets (combined_MAC and combined_align,
+    // porla/Server/Server.hpp:842-848 / :900-901) -- in one launch: set blockIdx.y takes its own points, partial sums, arrival
+    // counters and pinned result region (header + window sums at pair_stride_bytes); each set shapes itself for gridDim.x blocks
+    if (blockIdx.y) {
+        points = points_b;
+        part += (size_t)gridDim.x * SMALL_MAX_C;
+        counters += 256;
+        hdr = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(hdr) + pair_stride_bytes);
+        fin = reinterpret_cast<XYZZ<M>*>(reinterpret_cast<uint8_t*>(fin) + pair_stride_bytes);
+    }
+    // bits 16..24 of c_override: the scalars' bit length when the caller knows it (the audit's coefficients are abs(int32), expanded
+    // to 32-byte scalars by k_audit_gather: 32 bits, no scan -- ~10 us of a ~100 us kernel)
+    const SmallWindow<M> win = small_block<C>(scalars, points, n, blockIdx.x, (int)gridDim.x, c_override, (c_override >> 16) & 0x1ff, part,
+                                              counters, [](const SmallCfg&) { return true; } SMALL_STAMP_PASS(stamps));
+    if (!win.sums) return;
+    const uint32_t tid = threadIdx.x;
+    const int c = win.g.c;
+    if (tid < (uint32_t)c) Node<C>::store_final(fin + (size_t)win.w * c + tid, Node<C>::load(&win.sums[tid]));
     SMALL_STAMP(9);
     // the last window to finish publishes the shape and the sequence number the host polls for
     __threadfence_system();
     __syncthreads();
     if (tid == 0) {
         const uint32_t old = atomicAdd(&counters[SMALL_DONE_SLOT], 1u);
-        if (old == (uint32_t)g.W - 1) {
+        if (old == (uint32_t)win.g.W - 1) {
             counters[SMALL_DONE_SLOT] = 0;
-            hdr[1] = (uint32_t)g.W; hdr[2] = (uint32_t)c; hdr[3] = (uint32_t)g.glv;
+            hdr[1] = (uint32_t)win.g.W; hdr[2] = (uint32_t)c; hdr[3] = (uint32_t)win.g.glv;
             __threadfence_system();
             __atomic_store_n(&hdr[0], seq, __ATOMIC_RELEASE);
         }

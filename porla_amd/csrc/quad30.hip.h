@@ -1,9 +1,10 @@
 // Quad-lane helpers shared by the kernels whose group operations run on the four lanes of a quad with the accumulator in registers
 // (ec30.hip.h: xyzz30_dbl_quadreg / xyzz30_add_quadreg): the MAC-side encode's ladders (mac_fft.hip.h) and the batched MSM's tiny
 // entries and window fold (msm_batch.hip.h).  The signed 4-bit recoding of a 128-bit half-scalar, the quad-private LDS ordering, the
-// memory form of one residue, and the general addition with its rare equal-x fallback.
+// memory form of one residue, the general addition with its rare equal-x fallback, and the windowed ladder built on them.
 #pragma once
 #include "ec30.hip.h"
+#include "glv.hip.h"
 
 namespace porla {
 
@@ -75,6 +76,65 @@ __device__ __forceinline__ void macq_add(F30<M>& c, bool& inf, const XYZZ<M>* e,
     macq_sync();
     c = macq_load_residue<M>(reinterpret_cast<const uint32_t*>(slot_a) + 8 * r, &z);
     inf = macq_quad_any(z && r == 2u, lane);
+}
+
+// (c, inf) = sc * P on the four lanes of a quad: the endomorphism split, 33 signed 4-bit windows over the table of the multiples
+// 1 .. 8 of P.  Q: the quad's LDS record -- tbl[8] (memory form; P = tbl[0], written by this quad's lanes, macq_sync or a block
+// barrier passed) and bx[8][8] (the table's X coordinates times beta: the endomorphism's half reads its X there, so phi(d P) costs
+// no product per addition); slot_a / slot_b: the quad's two slots for the rare general addition.  Lane r ends with coordinate r
+// of the product; `inf` is the same on the four lanes.
+template <class C, class Q>
+__device__ __forceinline__ void macq_ladder(Q& Qd, XYZZ<typename C::Fp>* slot_a, XYZZ<typename C::Fp>* slot_b, uint32_t r, uint32_t lane,
+                                            const uint32_t sc[8], F30<typename C::Fp>& c, bool& inf) {
+    using M = typename C::Fp;
+    using G = typename C::Glv;
+    inf = true;
+    bool z;
+    c = macq_load_residue<M>(reinterpret_cast<const uint32_t*>(&Qd.tbl[0]) + 8 * r, &z);
+    if (macq_quad_any(z && r == 2u, lane)) return;                         // P is infinity: so is every multiple
+    uint32_t m0[4], m1[4];
+    bool ng0, ng1;
+    glv_split<G>(sc, m0, ng0, m1, ng1);
+    // tbl[i] = (i + 1) P: one doubling, six additions of P
+    bool tinf = false;
+    xyzz30_dbl_quadreg<M>(c, r);
+    macq_store_residue<M>(reinterpret_cast<uint32_t*>(&Qd.tbl[1]) + 8 * r, c);
+#pragma unroll 1
+    for (int i = 2; i < 8; i++) {
+        macq_add<M>(c, tinf, &Qd.tbl[0], reinterpret_cast<const uint32_t*>(&Qd.tbl[0]), false, slot_a, slot_b, r, lane);
+        macq_store_residue<M>(reinterpret_cast<uint32_t*>(&Qd.tbl[i]) + 8 * r, c);
+    }
+    macq_sync();
+    // beta * X of the eight entries: two per lane
+    {
+        const F30<M> beta30 = f30_const<M>(G::BETA_30);
+#pragma unroll 1
+        for (int t = 0; t < 2; t++) {
+            const uint32_t e = r + 4u * (uint32_t)t;
+            const F30<M> x = macq_load_residue<M>(reinterpret_cast<const uint32_t*>(&Qd.tbl[e]), &z);
+            macq_store_residue<M>(&Qd.bx[e][0], f30_mul<M>(x, beta30));
+        }
+    }
+    macq_sync();
+#pragma unroll 1
+    for (int i = 32; i >= 0; i--) {
+        if (!inf) {
+#pragma unroll 1
+            for (int d = 0; d < 4; d++) xyzz30_dbl_quadreg<M>(c, r);
+        }
+#pragma unroll 1
+        for (int h = 0; h < 2; h++) {
+            uint32_t mh[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) mh[j] = h ? m1[j] : m0[j];
+            const int dg = mac_signed_digit(mh, i);
+            if (dg == 0) continue;
+            const uint32_t mag = (uint32_t)(dg < 0 ? -dg : dg) - 1u;
+            const XYZZ<M>* e = &Qd.tbl[mag];
+            macq_add<M>(c, inf, e, h ? &Qd.bx[mag][0] : reinterpret_cast<const uint32_t*>(e), (dg < 0) != (h ? ng1 : ng0), slot_a, slot_b,
+                        r, lane);
+        }
+    }
 }
 
 }  // namespace porla
