@@ -28,6 +28,9 @@
  *   porla_audit_combine_device, porla_*_msm_pair_*, porla_*_audit_msm_pair_*, porla_kzg_audit_device, porla_ipa_audit_device
  *                            Server::audit after the challenge, Server.hpp:790-907: the row combine (:790-828), the two MSMs over
  *                            one scalar array (:842-848 / :900-901), and -- the last two -- the whole audit in one call
+ *   porla_kzg_audit_batch_device
+ *                            Server::audit (KZG) of many files or clients at once: K complete audits in one asynchronous
+ *                            call, each record the reply Server.hpp:897-915 sends
  *   porla_kzg_{digest,complement,mac}_batch_{device,host}
  *                            compute_digest / compute_digest_complement hoisted over the blocks of Client::initialize,
  *                            Client.hpp:408-455; the last: both and the add_point that joins them (Client.hpp:229-236, 468-478)
@@ -270,6 +273,35 @@ int  porla_kzg_audit_device(const void *d_rows64, const uint64_t *d_idx64, const
                             uint8_t combined_mac[64], uint8_t combined_align[64], uint8_t align_value[64],
                             uint8_t commitment[64], uint8_t proof_h[64], uint8_t proof_point[32], uint8_t proof_claim[32],
                             uint8_t *b_out, void *hip_stream);
+/* Server::audit (KZG build) for K independent audits in ONE call (one per file or client, Server.hpp:564-931 each): everything on
+ * the device and on hip_stream.  reqs is a HOST array of K audits; each field means what the same argument of
+ * porla_kzg_audit_device means, and every audit has its own stores (different files' levels may live in different allocations).
+ * d_out receives K records of PORLA_KZG_AUDIT_RECORD_BYTES, the reply of Server::audit (Server.hpp:897-915):
+ *   commitment(64) | proof_h(64) | point(32) | claim(32) | combined_mac(64) | combined_align(64)
+ * where combined_align is the value AFTER align_MAC (Server.hpp:903, :531-561): MSM(align store) + Commit(c).  Points 64-byte
+ * big-endian affine, infinity = 64 zero bytes.  Record k is byte-identical to porla_kzg_audit_device's outputs for audit k, with
+ * bn254_add(combined_align, align_value) as its last field.  d_b_out (may be NULL): K x n x 32 bytes, B mod p_icc big-endian per
+ * audit, the single call's b_out (n = the SRS size).
+ * Asynchronous: enqueued on hip_stream, returns without waiting on the host; the work waits for whatever the caller had enqueued on
+ * hip_stream before the call; d_out is complete when hip_stream is.  No internal side stream.
+ * PORLA_ERR_ARG (message in porla_gpu_last_error), checked before the device is touched: reqs or d_out NULL while k > 0; a NULL
+ * array whose count is > 0; n_macs > 32 768 (the batched MSM's entry limit: larger audits keep using porla_kzg_audit_device);
+ * n64 + n32 >= 2^32; a byte size that overflows.  k = 0 returns 0 and writes nothing.  No SRS loaded: PORLA_ERR_STATE.  Valid
+ * arguments without a device: PORLA_ERR_NO_DEVICE.
+ * One fixed sequence of launches per call: the row combine of all K audits (two launches), the KZG opening (a wave per audit), the
+ * MSM gather, the batched MSM over the 2K entries, ONE commitment pass over the 3K rows [c_k, B_k, h_k], and the join that adds
+ * align_value, normalises each audit's four points with one inversion and writes the records.  Calls from several threads on
+ * several streams, and beside porla_kzg_audit_device, are safe. */
+#define PORLA_KZG_AUDIT_RECORD_BYTES 320
+#define PORLA_KZG_AUDIT_REQ_BYTES    112   /* sizeof(porla_kzg_audit_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    const void *d_rows64; const uint64_t *d_idx64; const uint32_t *d_coef64; size_t n64;   /* offsets 0, 8, 16, 24 */
+    const void *d_rows32; const uint64_t *d_idx32; const uint32_t *d_coef32; size_t n32;   /* 32, 40, 48, 56 */
+    const void *d_mac_store; const void *d_align_store;                                     /* 64, 72 */
+    const uint64_t *d_mac_idx; const uint32_t *d_mac_coef; size_t n_macs;                   /* 80, 88, 96 */
+    unsigned long long random_point;                                                        /* 104 */
+} porla_kzg_audit_req;
+int  porla_kzg_audit_batch_device(const porla_kzg_audit_req *reqs, size_t k, void *d_out, void *d_b_out, void *hip_stream);
 /* The last encode stage of a large CRebuild (KZG build) in ONE call, everything resident in HBM (porla/Server/Server.hpp:1487-1833,
  * :2059-2065): rows_in = n_rows x n_samples raw 32-byte chunks; outputs per part (X, Y): the rows mod p_icc (aligned_x / aligned_y:
  * n_rows * n_samples * 32 bytes each, may be NULL), the alignment scalars of BOTH parts back to back (scalars_xy: 2 * n_rows *

@@ -82,20 +82,23 @@ __device__ __forceinline__ void audit_span(uint32_t (&acc)[ACC_LIMBS], const uin
     }
 }
 
+// block (bx, by) of a combine: rows [bx * SLICES * per_slice, ...) of the challenge, columns [by * AUD_COLS, ...); partial = the
+// combine's own partials (block bx at partial + bx * ACC_LIMBS * n_cols).  Shared by k_audit_accumulate and the batched audit's
+// k_audit_accumulate_batch.
 template <int SLICES>
-static __global__ void __launch_bounds__(SLICES * AUD_COLS) __attribute__((amdgpu_waves_per_eu(4, 4)))
-k_audit_accumulate(const uint8_t* __restrict__ rows64, const uint64_t* __restrict__ idx64, const uint32_t* __restrict__ coef64,
-                   uint32_t n64, const uint8_t* __restrict__ rows32, const uint64_t* __restrict__ idx32,
-                   const uint32_t* __restrict__ coef32, uint32_t n32, uint32_t n_cols, uint32_t per_slice,
-                   unsigned long long* __restrict__ partial) {
+__device__ __forceinline__ void audit_accumulate_block(const uint8_t* __restrict__ rows64, const uint64_t* __restrict__ idx64,
+                                                       const uint32_t* __restrict__ coef64, uint32_t n64, const uint8_t* __restrict__ rows32,
+                                                       const uint64_t* __restrict__ idx32, const uint32_t* __restrict__ coef32, uint32_t n32,
+                                                       uint32_t n_cols, uint32_t per_slice, unsigned long long* __restrict__ partial,
+                                                       uint32_t bx, uint32_t by) {
     __shared__ uint32_t sums[SLICES][ACC_LIMBS][AUD_COLS];
     const uint32_t lane_col = threadIdx.x % AUD_COLS;
     const uint32_t slice = __builtin_amdgcn_readfirstlane(threadIdx.x / AUD_COLS);
-    const uint32_t col0 = blockIdx.y * AUD_COLS;
+    const uint32_t col0 = by * AUD_COLS;
     const bool live = col0 + lane_col < n_cols;
     const uint32_t col = live ? col0 + lane_col : n_cols - 1;       // idle lanes re-read the last column and drop the result
     const uint32_t total = n64 + n32;
-    const uint64_t first = ((uint64_t)blockIdx.x * SLICES + slice) * per_slice;
+    const uint64_t first = ((uint64_t)bx * SLICES + slice) * per_slice;
     const uint32_t lo = first < total ? (uint32_t)first : total;
     const uint32_t hi = first + per_slice < total ? (uint32_t)(first + per_slice) : total;
     uint32_t acc[ACC_LIMBS];
@@ -112,8 +115,18 @@ k_audit_accumulate(const uint8_t* __restrict__ rows64, const uint64_t* __restric
         unsigned long long t = 0;
 #pragma unroll
         for (int sl = 0; sl < SLICES; sl++) t += sums[sl][k][c];
-        if (col0 + c < n_cols) partial[((size_t)blockIdx.x * ACC_LIMBS + k) * n_cols + col0 + c] = t;
+        if (col0 + c < n_cols) partial[((size_t)bx * ACC_LIMBS + k) * n_cols + col0 + c] = t;
     }
+}
+
+template <int SLICES>
+static __global__ void __launch_bounds__(SLICES * AUD_COLS) __attribute__((amdgpu_waves_per_eu(4, 4)))
+k_audit_accumulate(const uint8_t* __restrict__ rows64, const uint64_t* __restrict__ idx64, const uint32_t* __restrict__ coef64,
+                   uint32_t n64, const uint8_t* __restrict__ rows32, const uint64_t* __restrict__ idx32,
+                   const uint32_t* __restrict__ coef32, uint32_t n32, uint32_t n_cols, uint32_t per_slice,
+                   unsigned long long* __restrict__ partial) {
+    audit_accumulate_block<SLICES>(rows64, idx64, coef64, n64, rows32, idx32, coef32, n32, n_cols, per_slice, partial, blockIdx.x,
+                                   blockIdx.y);
 }
 
 // One block per AUD_FIN_COLS columns, a lane per (quarter of the partials, limb, column): the blocks' carry-save limb sums are added
@@ -121,15 +134,16 @@ k_audit_accumulate(const uint8_t* __restrict__ rows64, const uint64_t* __restric
 // runs the carry chain and reduces the exact integer once mod p_icc and once mod q.
 constexpr int AUD_FIN_COLS = 8;
 constexpr int AUD_FIN_SPLIT = 4;
+// block bx of a finish over the n_blocks partials at `partial`; shared by k_audit_finish and k_audit_finish_batch
 template <class Q>
-static __global__ void __launch_bounds__(AUD_FIN_SPLIT * ACC_LIMBS * AUD_FIN_COLS)
-k_audit_finish(const unsigned long long* __restrict__ partial, uint32_t n_blocks, uint32_t n_cols, uint8_t* __restrict__ exact_out,
-               uint8_t* __restrict__ al_out, uint8_t* __restrict__ al_be_out, uint8_t* __restrict__ sc_out) {
+__device__ __forceinline__ void audit_finish_block(const unsigned long long* __restrict__ partial, uint32_t n_blocks, uint32_t n_cols,
+                                                   uint8_t* __restrict__ exact_out, uint8_t* __restrict__ al_out,
+                                                   uint8_t* __restrict__ al_be_out, uint8_t* __restrict__ sc_out, uint32_t bx) {
     __shared__ unsigned long long limb_sum[AUD_FIN_SPLIT][ACC_LIMBS][AUD_FIN_COLS];
     {
         const uint32_t c = threadIdx.x % AUD_FIN_COLS, k = (threadIdx.x / AUD_FIN_COLS) % ACC_LIMBS;
         const uint32_t part = threadIdx.x / (AUD_FIN_COLS * ACC_LIMBS);
-        const uint32_t gc = blockIdx.x * AUD_FIN_COLS + c;
+        const uint32_t gc = bx * AUD_FIN_COLS + c;
         unsigned long long t[8];
 #pragma unroll
         for (int u = 0; u < 8; u++) t[u] = 0;
@@ -147,7 +161,7 @@ k_audit_finish(const unsigned long long* __restrict__ partial, uint32_t n_blocks
         limb_sum[part][k][c] = ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
     }
     __syncthreads();
-    const uint32_t col = blockIdx.x * AUD_FIN_COLS + threadIdx.x;
+    const uint32_t col = bx * AUD_FIN_COLS + threadIdx.x;
     if (threadIdx.x >= AUD_FIN_COLS || col >= n_cols) return;
     uint32_t acc[ACC_LIMBS];
     {
@@ -185,6 +199,53 @@ k_audit_finish(const unsigned long long* __restrict__ partial, uint32_t n_blocks
         q4[0] = make_uint4(__builtin_bswap32(c.v[7]), __builtin_bswap32(c.v[6]), __builtin_bswap32(c.v[5]), __builtin_bswap32(c.v[4]));
         q4[1] = make_uint4(__builtin_bswap32(c.v[3]), __builtin_bswap32(c.v[2]), __builtin_bswap32(c.v[1]), __builtin_bswap32(c.v[0]));
     }
+}
+
+template <class Q>
+static __global__ void __launch_bounds__(AUD_FIN_SPLIT * ACC_LIMBS * AUD_FIN_COLS)
+k_audit_finish(const unsigned long long* __restrict__ partial, uint32_t n_blocks, uint32_t n_cols, uint8_t* __restrict__ exact_out,
+               uint8_t* __restrict__ al_out, uint8_t* __restrict__ al_be_out, uint8_t* __restrict__ sc_out) {
+    audit_finish_block<Q>(partial, n_blocks, n_cols, exact_out, al_out, al_be_out, sc_out, blockIdx.x);
+}
+
+// The row combine of porla_kzg_audit_batch_device: block b of the work list runs block b - blk0 of its audit's combine (partials of
+// the audit from blk0 on); the finish runs per audit (blockIdx.y) and writes the alignment scalars and B big-endian into the
+// audit's first two commit rows (a flat grid: fin_blocks blocks per audit).
+static_assert(AUDIT_BATCH_SLICES == AUD_SLICES, "the batched combine runs the large-challenge block");
+static __global__ void __launch_bounds__(AUD_SLICES * AUD_COLS) __attribute__((amdgpu_waves_per_eu(4, 4)))
+k_audit_accumulate_batch(const KzgAuditDesc* __restrict__ desc, const uint32_t* __restrict__ blk_audit, uint32_t n_cols,
+                         uint32_t per_slice, unsigned long long* __restrict__ partial) {
+    const KzgAuditDesc& D = desc[blk_audit[blockIdx.x]];
+    audit_accumulate_block<AUD_SLICES>(D.rows64, D.idx64, D.coef64, D.n64, D.rows32, D.idx32, D.coef32, D.n32, n_cols, per_slice,
+                                       partial + (size_t)D.blk0 * ACC_LIMBS * n_cols, blockIdx.x - D.blk0, blockIdx.y);
+}
+static __global__ void __launch_bounds__(AUD_FIN_SPLIT * ACC_LIMBS * AUD_FIN_COLS)
+k_audit_finish_batch(const KzgAuditDesc* __restrict__ desc, const unsigned long long* __restrict__ partial, uint32_t n_cols,
+                     uint32_t fin_blocks, uint8_t* __restrict__ rows3) {
+    const uint32_t a = blockIdx.x / fin_blocks;
+    const KzgAuditDesc& D = desc[a];
+    uint8_t* sc = rows3 + (size_t)a * 3 * 32 * n_cols;
+    audit_finish_block<IccBn254Fr>(partial + (size_t)D.blk0 * ACC_LIMBS * n_cols, D.nblk, n_cols, nullptr, nullptr, sc + 32 * (size_t)n_cols,
+                                   sc, blockIdx.x - a * fin_blocks);
+}
+
+size_t audit_combine_partial_bytes(uint32_t n_blocks, uint32_t n_cols) { return (size_t)n_blocks * ACC_LIMBS * n_cols * 8; }
+
+int audit_combine_batch_launch(const KzgAuditDesc* d_desc, const uint32_t* d_blk_audit, uint32_t n_blocks, uint32_t k, uint32_t n_cols,
+                               uint32_t per_slice, void* d_partial, uint8_t* d_rows3, hipStream_t stream) {
+    {
+        ProfScope ps("audit_batch_accumulate", stream);
+        hipLaunchKernelGGL(k_audit_accumulate_batch, dim3(n_blocks, (n_cols + AUD_COLS - 1) / AUD_COLS), dim3(AUD_SLICES * AUD_COLS), 0, stream,
+                           d_desc, d_blk_audit, n_cols, per_slice, (unsigned long long*)d_partial);
+    }
+    {
+        ProfScope ps("audit_batch_finish", stream);
+        const uint32_t fin_blocks = (n_cols + AUD_FIN_COLS - 1) / AUD_FIN_COLS;
+        hipLaunchKernelGGL(k_audit_finish_batch, dim3(fin_blocks * k), dim3(AUD_FIN_SPLIT * ACC_LIMBS * AUD_FIN_COLS), 0, stream, d_desc,
+                           (const unsigned long long*)d_partial, n_cols, fin_blocks, d_rows3);
+    }
+    PORLA_HIP(hipGetLastError());
+    return PORLA_OK;
 }
 
 struct AuditWs { int device = -1; Buf partial; UseFence fence; };

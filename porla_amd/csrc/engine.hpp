@@ -63,6 +63,11 @@ template <class C>
 int msm_batch_device(const uint8_t* d_scalars, const uint8_t* d_points, const uint64_t* offsets, size_t k, uint8_t* d_out, hipStream_t stream);
 template <class C>
 int msm_batch_host(const uint8_t* scalars, const uint8_t* points, const uint64_t* offsets, size_t k, uint8_t* out);
+// the same, but the entries' projective sums are left in d_sums (XYZZ, k of them) instead of being normalised: a caller that joins
+// them with other points normalises all of them at once (kzg_audit_batch.hip)
+template <class C>
+int msm_batch_sums_device(const uint8_t* d_scalars, const uint8_t* d_points, const uint64_t* offsets, size_t k, XYZZ<typename C::Fp>* d_sums,
+                          hipStream_t stream);
 template <class C>
 int msm_device_begin(int slot, const uint8_t* d_scalars, const uint8_t* d_points, size_t n, hipStream_t stream);
 template <class C>
@@ -243,5 +248,29 @@ int icc_wt_scalar_be(size_t n_total, unsigned long long write_step, uint8_t out[
 // icc.hip: the ICC butterfly network as an n x n matrix of 32-byte big-endian coefficients mod the group order
 int icc_network_matrix_device(int curve, size_t n, unsigned long long write_step, int part, uint8_t* d_rows_out,
                               hipStream_t stream);
+
+// One audit of porla_kzg_audit_batch_device as the device kernels see it (kzg_audit_batch.hip builds them, audit.hip and
+// kzg_audit_batch.hip read them): the caller's arrays, the audit's share of the row combine (blocks [blk0, blk0 + nblk) of the
+// partials) and of the batched MSM (its MAC entry at pairs [pair0, pair0 + n_macs), its alignment entry right behind).
+struct KzgAuditDesc {
+    const uint8_t* rows64; const uint64_t* idx64; const uint32_t* coef64;
+    const uint8_t* rows32; const uint64_t* idx32; const uint32_t* coef32;
+    const uint8_t* mac_store; const uint8_t* align_store; const uint64_t* mac_idx; const uint32_t* mac_coef;
+    uint32_t n64, n32, n_macs, blk0, nblk, gat0;   // gat0: the audit's first block of the MSM gather
+    unsigned long long z;
+    unsigned long long pair0;
+};
+static_assert(sizeof(KzgAuditDesc) == 120, "KzgAuditDesc: 80 bytes of pointers, 24 of counts, z, pair0");
+// audit.hip: the row combine of k audits (one launch each for the accumulation and the finish).  blk_audit[b] = the audit of combine
+// block b; per_slice rows per slice everywhere; partial holds n_blocks * ACC_LIMBS * n_cols 64-bit sums.  Audit a's alignment
+// scalars go to rows3 + 3 a n_cols 32 and B (big-endian, mod p_icc) to the row after it.
+int audit_combine_batch_launch(const KzgAuditDesc* d_desc, const uint32_t* d_blk_audit, uint32_t n_blocks, uint32_t k, uint32_t n_cols,
+                               uint32_t per_slice, void* d_partial, uint8_t* d_rows3, hipStream_t stream);
+size_t audit_combine_partial_bytes(uint32_t n_blocks, uint32_t n_cols);
+constexpr uint32_t AUDIT_BATCH_SLICES = 8;   // row slices per block of the batched combine (audit.hip: AUD_SLICES)
+// kzg_abi.hip: commit n_rows contiguous rows of n_samples coefficients against the resident SRS table, leave the row sums in the
+// table's partials, and run `then(sums, S)` (row r at sums[r * S]) under the table's lock before its fence is recorded again
+int kzg_commit_rows_raw(const uint8_t* d_rows, size_t n_rows, hipStream_t stream,
+                        int (*then)(const XYZZ<Bn254Fp>* sums, uint32_t S, void* ctx), void* ctx);
 
 }  // namespace porla

@@ -313,6 +313,29 @@ int commit_rows(const uint8_t* rows, bool device_ptrs, size_t n_rows, size_t len
     return kd->fb.commit_host(rows, n_rows, len, len * 32, out, engine_stream());
 }
 
+}  // namespace
+
+int porla::kzg_commit_rows_raw(const uint8_t* d_rows, size_t n_rows, hipStream_t stream,
+                               int (*then)(const XYZZ<Bn254Fp>* sums, uint32_t S, void* ctx), void* ctx) {
+    std::unique_lock<std::mutex> lk(g.mu);
+    KzgState::Dev* kd = nullptr;
+    int rc = refresh_srs_locked(&kd);
+    if (rc) {
+        if (rc == PORLA_ERR_STATE) set_last_error("porla: SRS not initialised (call init_SRS / init_SRS_from_data first)");
+        return rc;
+    }
+    const size_t len = (size_t)g.n_samples;
+    if (len == 0 || len > g.srs.size()) { set_last_error("porla: more coefficients than SRS points"); return PORLA_ERR_STATE; }
+    std::unique_lock<std::mutex> lkfb(kd->fb.mu);
+    lk.unlock();
+    if ((rc = kd->fb.commit_device(d_rows, n_rows, len, len * 32, nullptr, stream))) return rc;
+    // the table's fence was recorded behind the commit; `then` reads the partials after it, so the fence moves behind `then`
+    if ((rc = then(kd->fb.partial, kd->fb.last_S, ctx))) return rc;
+    return kd->fb.fence.leave(stream);
+}
+
+namespace {
+
 // compute_digest_from_srs arrives ONE row per call from up to 8 pool threads at once (Server.hpp:550-560, 1054-1078, 1530-1535):
 // calls that meet here are coalesced -- whoever finds no batch in progress becomes the leader, takes every row queued so far
 // (its own included), commits them in ONE launch (FixedBase::commit_small) and hands the results back; rows that arrive while a

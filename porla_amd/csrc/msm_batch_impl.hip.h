@@ -27,9 +27,10 @@ static inline uint32_t batch_blocks(uint64_t n, bool lone, uint32_t bmin) {
 
 // K independent MSMs (arguments checked by the C ABI: offsets non-decreasing from 0, entries <= SMALL_MAX_N, non-null pointers);
 // enqueued on `stream`, results written to d_out, no host wait for this call's work.  ws->mu held.
+// raw_sums != nullptr: the entries' projective sums go there instead (entry e at raw_sums[e]) and d_out is not used.
 template <class C>
 static int msm_batch_locked(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_points, const uint64_t* offsets, size_t k, uint8_t* d_out,
-                            hipStream_t stream) {
+                            hipStream_t stream, XYZZ<typename C::Fp>* raw_sums = nullptr) {
     using M = typename C::Fp;
     int rc;
     const uint32_t bmin = g_use_glv == 0 ? 34u : 18u;        // windows: <= 33 over unsplit 256-bit scalars, <= 17 otherwise (c = 8)
@@ -167,7 +168,7 @@ static int msm_batch_locked(Workspace* ws, const uint8_t* d_scalars, const uint8
     const uint32_t* d_list = (const uint32_t*)ws->batch_list.p;
     XYZZ<M>* part = (XYZZ<M>*)ws->batch_part.p;
     XYZZ<M>* fin = (XYZZ<M>*)((uint8_t*)ws->batch_part.p + part_bytes);
-    XYZZ<M>* sums = (XYZZ<M>*)ws->batch_sums.p;
+    XYZZ<M>* const round_sums = (XYZZ<M>*)ws->batch_sums.p;
     uint32_t* counters = (uint32_t*)ws->batch_ctrl.p;
     uint32_t* shape = counters + max_nb;
     for (const BatchRound& R : rounds) {
@@ -178,6 +179,7 @@ static int msm_batch_locked(Workspace* ws, const uint8_t* d_scalars, const uint8
         const uint32_t* tq = fold + R.nf;
         const uint8_t* sc = d_scalars + 32 * R.pair0;
         const uint8_t* pt = d_points + 64 * R.pair0;
+        XYZZ<M>* sums = raw_sums ? raw_sums + R.e0 : round_sums;
         if (R.nq) {
             ProfScope ps("batch_tiny", stream);
             hipLaunchKernelGGL((k_batch_tiny<C>), dim3((R.nq + BATCH_QUADS - 1) / BATCH_QUADS), dim3(4 * BATCH_QUADS), 0, stream, sc, pt, ents, tq,
@@ -198,7 +200,7 @@ static int msm_batch_locked(Workspace* ws, const uint8_t* d_scalars, const uint8
                                (const XYZZ<M>*)fin, (const uint32_t*)shape, sums);
             PORLA_HIP(hipGetLastError());
         }
-        {
+        if (!raw_sums) {
             ProfScope ps("batch_finish", stream);
             uint8_t* out = d_out + 64 * R.e0;
             if (R.k <= 4096) hipLaunchKernelGGL((k_fb_finish<C, 1>), dim3((unsigned)((R.k + 63) / 64)), dim3(64), 0, stream, sums, (uint32_t)R.k, 1u, out);
@@ -219,6 +221,18 @@ int msm_batch_device(const uint8_t* d_scalars, const uint8_t* d_points, const ui
     if ((rc = lease_blocking_slot(&ws))) return rc;
     std::lock_guard<std::mutex> lk(ws->mu, std::adopt_lock);
     return msm_batch_locked<C>(ws, d_scalars, d_points, offsets, k, d_out, stream);
+}
+
+template <class C>
+int msm_batch_sums_device(const uint8_t* d_scalars, const uint8_t* d_points, const uint64_t* offsets, size_t k, XYZZ<typename C::Fp>* d_sums,
+                          hipStream_t stream) {
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (k == 0) return PORLA_OK;
+    Workspace* ws;
+    if ((rc = lease_blocking_slot(&ws))) return rc;
+    std::lock_guard<std::mutex> lk(ws->mu, std::adopt_lock);
+    return msm_batch_locked<C>(ws, d_scalars, d_points, offsets, k, nullptr, stream, d_sums);
 }
 
 // host buffers: upload to the slot's staging buffers, the batch on the slot's own stream, results back, wait

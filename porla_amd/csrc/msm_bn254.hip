@@ -15,6 +15,7 @@ template int msm_pair_host<Bn254G1>(const uint8_t*, const uint8_t*, const uint8_
 template int msm_device_begin<Bn254G1>(int, const uint8_t*, const uint8_t*, size_t, hipStream_t);
 template int msm_device_end<Bn254G1>(int, XYZZ<Bn254Fp>*);
 template int msm_batch_device<Bn254G1>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint8_t*, hipStream_t);
+template int msm_batch_sums_device<Bn254G1>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, XYZZ<Bn254Fp>*, hipStream_t);
 template int msm_batch_host<Bn254G1>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint8_t*);
 template struct FixedBase<Bn254G1>;
 }  // namespace porla

@@ -13,6 +13,14 @@ class GoSlice(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("len", ctypes.c_longlong), ("cap", ctypes.c_longlong)]
 
 
+class KzgAuditReq(ctypes.Structure):
+    """porla_kzg_audit_req, include/porla_gpu.h: one audit of porla_kzg_audit_batch_device (PORLA_KZG_AUDIT_REQ_BYTES = 112)."""
+    _fields_ = [("d_rows64", ctypes.c_void_p), ("d_idx64", ctypes.c_void_p), ("d_coef64", ctypes.c_void_p), ("n64", ctypes.c_size_t),
+                ("d_rows32", ctypes.c_void_p), ("d_idx32", ctypes.c_void_p), ("d_coef32", ctypes.c_void_p), ("n32", ctypes.c_size_t),
+                ("d_mac_store", ctypes.c_void_p), ("d_align_store", ctypes.c_void_p), ("d_mac_idx", ctypes.c_void_p),
+                ("d_mac_coef", ctypes.c_void_p), ("n_macs", ctypes.c_size_t), ("random_point", ctypes.c_ulonglong)]
+
+
 def load():
     """Load the engine.  When torch is importable it is imported FIRST so that the HIP runtime the process
     ends up with is the one torch ships (both have soname libamdhip64.so.7; two runtimes in one process
@@ -115,6 +123,8 @@ def _declare(L):
     L.porla_ipa_audit_device.restype = ctypes.c_int
     L.porla_kzg_audit_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, ctypes.c_ulonglong] + [u8p] * 8 + [vp]
     L.porla_kzg_audit_device.restype = ctypes.c_int
+    L.porla_kzg_audit_batch_device.argtypes = [ctypes.POINTER(KzgAuditReq), sz, vp, vp, vp]
+    L.porla_kzg_audit_batch_device.restype = ctypes.c_int
     L.porla_kzg_digest_batch_device.argtypes = [vp, sz, vp, vp]; L.porla_kzg_digest_batch_device.restype = ctypes.c_int
     L.porla_kzg_complement_batch_device.argtypes = [vp, sz, vp, vp]; L.porla_kzg_complement_batch_device.restype = ctypes.c_int
     L.porla_kzg_mac_batch_device.argtypes = [vp, vp, sz, vp, vp]; L.porla_kzg_mac_batch_device.restype = ctypes.c_int

@@ -10,7 +10,7 @@ Server.hpp:183-188,365-397,550-558).  Buffers are Python bytes/bytearray; result
 """
 import ctypes
 
-from .loader import GoSlice, lib
+from .loader import GoSlice, KzgAuditReq, lib
 
 MAC_SIZE = 64       # COMMITMENT_MAC_SIZE with ENABLE_KZG, config.hpp:26
 SCALAR_SIZE = 32    # bn254_scalar = uint32_t[8], utils.h:64
@@ -399,6 +399,40 @@ def kzg_audit_device(d_rows64, d_idx64, d_coef64, n64, d_rows32, d_idx32, d_coef
                                       vp(d_idx32 or None), vp(d_coef32 or None), n32, vp(d_mac_store), vp(d_align_store), vp(d_mac_idx),
                                       vp(d_mac_coef), n_macs, z, *o, vp(stream)))
     return dict(zip(("combined_mac", "combined_align", "align_value", "commitment", "proof_h", "point", "claim", "b"), (x.raw for x in o)))
+
+
+_REQ_POINTERS = (0, 1, 2, 4, 5, 6, 8, 9, 10, 11)   # fields of porla_kzg_audit_req that are device pointers (0 -> NULL)
+KZG_AUDIT_RECORD_BYTES = 320   # commitment | proof_h | point | claim | combined_mac | combined_align (include/porla_gpu.h)
+
+
+def kzg_audit_requests(audits):
+    """a ctypes array of porla_kzg_audit_req from per-audit tuples in kzg_audit_device's argument order (without n_cols and stream):
+    (d_rows64, d_idx64, d_coef64, n64, d_rows32, d_idx32, d_coef32, n32, d_mac_store, d_align_store, d_mac_idx, d_mac_coef, n_macs, z)"""
+    arr = (KzgAuditReq * max(len(audits), 1))()
+    for i, a in enumerate(audits):
+        if len(a) != 14:
+            raise ValueError("kzg_audit_batch_device: audit %d has %d fields, want 14" % (i, len(a)))
+        arr[i] = KzgAuditReq(*[(x or None) if j in _REQ_POINTERS else x for j, x in enumerate(a)])
+    return arr
+
+
+def kzg_audit_batch_device(audits, d_out, d_b=None, stream=0):
+    """Server::audit (KZG) of len(audits) independent audits in ONE asynchronous call on `stream` (porla_kzg_audit_batch_device):
+    record k (320 bytes at d_out + 320 k) = commitment | proof_h | point | claim | combined_mac | combined_align, the reply of
+    Server::audit; d_b (optional): B mod p_icc of every audit, n x 32 bytes each.  `audits`: tuples as kzg_audit_requests takes."""
+    arr = kzg_audit_requests(audits)
+    _check(lib.porla_kzg_audit_batch_device(arr, len(audits), ctypes.c_void_p(d_out), ctypes.c_void_p(d_b or None),
+                                            ctypes.c_void_p(stream)))
+
+
+def split_audit_records(raw, k):
+    """k records -> list of dicts with the fields of kzg_audit_device's reply (combined_align after align_MAC)"""
+    out = []
+    for i in range(k):
+        r = raw[KZG_AUDIT_RECORD_BYTES * i:KZG_AUDIT_RECORD_BYTES * (i + 1)]
+        out.append(dict(commitment=r[0:64], proof_h=r[64:128], point=r[128:160], claim=r[160:192], combined_mac=r[192:256],
+                        combined_align=r[256:320]))
+    return out
 
 
 def kzg_digest_batch_device(d_rows, n_rows, d_out, stream=0):
