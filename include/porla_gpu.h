@@ -31,6 +31,9 @@
  *   porla_kzg_audit_batch_device
  *                            Server::audit (KZG) of many files or clients at once: K complete audits in one asynchronous
  *                            call, each record the reply Server.hpp:897-915 sends
+ *   porla_kzg_verify_batch_device
+ *                            Client::audit's check (KZG) of many replies at once, Client.hpp:685-778 and :849-869: K MAC
+ *                            checks and ONE folded pairing check per call, a verdict per reply
  *   porla_kzg_{digest,complement,mac}_batch_{device,host}
  *                            compute_digest / compute_digest_complement hoisted over the blocks of Client::initialize,
  *                            Client.hpp:408-455; the last: both and the add_point that joins them (Client.hpp:229-236, 468-478)
@@ -302,6 +305,54 @@ typedef struct {
     unsigned long long random_point;                                                        /* 104 */
 } porla_kzg_audit_req;
 int  porla_kzg_audit_batch_device(const porla_kzg_audit_req *reqs, size_t k, void *d_out, void *d_b_out, void *hip_stream);
+/* Client::audit's check (KZG build, Client.hpp:633-880) of K replies in ONE call: reply k is the 320-byte record k of d_records
+ * (the layout porla_kzg_audit_batch_device writes: commitment C | proof_h H | point z | claim y | combined_mac M | combined_align A),
+ * reqs[k] the client's side of that audit: the level's MAC complements d_comp_store (64-byte big-endian affine points, as
+ * compute_digest_complement / porla_kzg_complement_batch_device give them, indexed like the server's MAC store), the challenge
+ * (d_idx, d_coef, n: the arrays the server's MAC MSM used) and the client's alpha (32 bytes big-endian, taken mod r as mult_point
+ * takes its scalar; the reference's is SECRET_KEY in bytes 16..31).  status[k] receives
+ *   PORLA_KZG_VERIFY_FULL       alpha C + sum_j coef_j comp[idx_j] == M + alpha A      (the MAC check, Client.hpp:849-869)
+ *   PORLA_KZG_VERIFY_PROOF      the opening verifies: verify_proof(C, H, z, y)           (Client.hpp:868, main.go:177-193)
+ *   PORLA_KZG_VERIFY_MALFORMED  a point of the record has a coordinate >= p or is off y^2 = x^3 + 3 (64 zero bytes = infinity is
+ *                               well-formed); the other two bits are then clear
+ * and the audit passes iff status == FULL | PROOF.  For a well-formed record both bits are exactly the reference's verdicts
+ * (compute_multi_exp, mult_point, add_point and compare_commitment for FULL; verify_proof for PROOF).
+ * How: each MAC check is one MSM entry that sums to infinity iff it holds (the complements, then (alpha, C), (r - alpha, A),
+ * (r - 1, M)); the K openings are weighted with secret random 128-bit scalars w_k and folded into ONE two-pairing check
+ *   e(P, G2) * e(-Q, tau G2) == 1,   P = sum w_k (C_k - y_k G + z_k H_k),   Q = sum w_k H_k   (G = G1[0] of the SRS)
+ * -- verify_proof's form summed over k.  The MSMs run on the device (the batched MSM: K complement entries, K 3-pair entries, P
+ * with 3K pairs and Q), the pairing on the host.  When the folded check holds, every well-formed reply gets PROOF; when it fails,
+ * verify_proof's predicate runs for every well-formed reply on up to 16 host threads (about 0.9 ms of CPU per reply), so a batch
+ * with a bad opening costs K single checks on top of the batch, and its verdicts stay exact.
+ * Soundness: with weights uniformly random, nonzero, 128-bit and unknown to the prover, a batch that contains an invalid opening
+ * passes the folded check with probability <= 2^-128.  weights = NULL (the normal use): drawn per call from the operating system's
+ * random source (getrandom).  Caller-supplied weights (k x 16 bytes big-endian, nonzero) must be just as secret and random;
+ * equal weights, for instance, let two openings whose claims are off by +d and -d cancel.
+ * Blocking: the call returns when status is written (the pairing runs on the host).  Its device work runs on hip_stream and waits
+ * for whatever the caller had enqueued there before the call, so d_records can come straight from porla_kzg_audit_batch_device on
+ * the same stream with no host wait in between.  d_comp_store, d_idx, d_coef and d_records are device pointers; reqs, weights and
+ * status are host memory.
+ * PORLA_ERR_ARG (message in porla_gpu_last_error), checked before the device is touched: reqs, d_records or status NULL while
+ * k > 0; a NULL array whose count n is > 0; n > 32 768 (the batched MSM's entry limit, as for the server batch); an all-zero
+ * weight; k > PORLA_KZG_VERIFY_MAX_K (the folded entry P holds 3 pairs per reply, at most 32 768: larger batches go in several
+ * calls); a byte size that overflows.  k = 0 returns 0 and writes nothing.  No SRS or no G2 points loaded: PORLA_ERR_STATE.  Valid
+ * arguments without a device: PORLA_ERR_NO_DEVICE.
+ * One fixed sequence of launches per call: the work-list upload, k_kzg_verify_prep (a lane per reply: validation, the 3-pair and
+ * folded entries), k_kzg_verify_gather (the complement entries), the batched MSM over the 2K + 2 entries with projective sums,
+ * k_kzg_verify_join (the MAC verdicts, P and Q to affine with one inversion), one copy back of 128 + K bytes.  Calls from several
+ * threads on several streams, and beside verify_proof and porla_kzg_audit_batch_device, are safe. */
+#define PORLA_KZG_VERIFY_REQ_BYTES 64      /* sizeof(porla_kzg_verify_req) on LP64; the library static_asserts it and each offset */
+#define PORLA_KZG_VERIFY_MAX_K     10922   /* floor(32768 / 3) replies per call */
+#define PORLA_KZG_VERIFY_FULL      1
+#define PORLA_KZG_VERIFY_PROOF     2
+#define PORLA_KZG_VERIFY_MALFORMED 4
+typedef struct {
+    const void *d_comp_store;                                  /* 0 */
+    const uint64_t *d_idx; const uint32_t *d_coef; size_t n;   /* 8, 16, 24 */
+    uint8_t alpha[32];                                         /* 32 */
+} porla_kzg_verify_req;
+int  porla_kzg_verify_batch_device(const porla_kzg_verify_req *reqs, size_t k, const void *d_records, const uint8_t *weights,
+                                   uint8_t *status, void *hip_stream);
 /* The last encode stage of a large CRebuild (KZG build) in ONE call, everything resident in HBM (porla/Server/Server.hpp:1487-1833,
  * :2059-2065): rows_in = n_rows x n_samples raw 32-byte chunks; outputs per part (X, Y): the rows mod p_icc (aligned_x / aligned_y:
  * n_rows * n_samples * 32 bytes each, may be NULL), the alignment scalars of BOTH parts back to back (scalars_xy: 2 * n_rows *

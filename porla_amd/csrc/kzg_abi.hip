@@ -616,16 +616,8 @@ void create_proof(GoUint64 random_point, GoSlice* data_in, GoSlice* commitment_o
     copy_out(proof_claim, yt, 32);
 }
 
-// main.go:177-193: kzg.Verify -- e(C - y*G1, G2) == e(H, tau*G2 - z*G2), as one product of two pairings (rearranged, below)
-GoUint8 verify_proof(GoSlice* commitment_in, GoSlice* proof_H, GoSlice* proof_point, GoSlice* proof_claim) {
-    Affine<Fp> C = unmarshal64((const uint8_t*)commitment_in->data);
-    Affine<Fp> H = unmarshal64((const uint8_t*)proof_H->data);
-    Fe<Fr> z = h_fe_from_be_var<Fr>((const uint8_t*)proof_point->data, (size_t)proof_point->len);
-    Fe<Fr> y = h_fe_from_be_var<Fr>((const uint8_t*)proof_claim->data, (size_t)proof_claim->len);
-    if (!g.have_g2) {
-        printf("Verifying is wrong\n");
-        return 0;
-    }
+// main.go:177-193: kzg.Verify -- e(C - y*G1, G2) == e(H, tau*G2 - z*G2), as one product of two pairings (rearranged, below); needs g.have_g2
+static bool opening_holds(const Affine<Fp>& C, const Affine<Fp>& H, const Fe<Fr>& z, const Fe<Fr>& y) {
     uint32_t yk[8], zk[8];
     h_fe_to_plain<Fr>(yk, y);
     h_fe_to_plain<Fr>(zk, z);
@@ -640,8 +632,15 @@ GoUint8 verify_proof(GoSlice* commitment_in, GoSlice* proof_H, GoSlice* proof_po
     Affine<Fp> Aaff = h_xyzz_to_affine64<Fp>(A);
     Affine<Fp> negH = aff_neg_if<Fp>(H, true);
     if (aff_is_inf<Fp>(H)) negH = H;
-    bool ok = pairing_product_is_one(Aaff, g.g2[0], negH, g.g2[1]);
-    if (!ok) {
+    return pairing_product_is_one(Aaff, g.g2[0], negH, g.g2[1]);
+}
+
+GoUint8 verify_proof(GoSlice* commitment_in, GoSlice* proof_H, GoSlice* proof_point, GoSlice* proof_claim) {
+    Affine<Fp> C = unmarshal64((const uint8_t*)commitment_in->data);
+    Affine<Fp> H = unmarshal64((const uint8_t*)proof_H->data);
+    Fe<Fr> z = h_fe_from_be_var<Fr>((const uint8_t*)proof_point->data, (size_t)proof_point->len);
+    Fe<Fr> y = h_fe_from_be_var<Fr>((const uint8_t*)proof_claim->data, (size_t)proof_claim->len);
+    if (!g.have_g2 || !opening_holds(C, H, z, y)) {
         printf("Verifying is wrong\n");
         return 0;
     }
@@ -1302,3 +1301,23 @@ int porla_kzg_commit_shape(int* window_bits, int* windows) {
 }
 
 }  // extern "C"
+
+// ---- the batched verifier's share of the KZG state (kzg_verify_batch.hip)
+int porla::kzg_verify_base(uint8_t g_be[64]) {
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (g.srs.empty() || !g.have_g2) {
+        set_last_error("porla: SRS and its G2 points not initialised (call init_SRS / init_SRS_from_data first)");
+        return PORLA_ERR_STATE;
+    }
+    h_affine_to_bytes<Fp>(g_be, g.srs[0]);
+    return PORLA_OK;
+}
+
+bool porla::kzg_opening_holds(const uint8_t rec[192]) {
+    return opening_holds(unmarshal64(rec), unmarshal64(rec + 64), h_fe_from_be_var<Fr>(rec + 128, 32), h_fe_from_be_var<Fr>(rec + 160, 32));
+}
+
+bool porla::kzg_folded_opening_holds(const uint8_t p_be[64], const uint8_t q_be[64]) {
+    const Affine<Fp> P = h_affine_from_bytes<Fp>(p_be), Q = h_affine_from_bytes<Fp>(q_be);
+    return pairing_product_is_one(P, g.g2[0], aff_neg_if<Fp>(Q, true), g.g2[1]);   // -infinity = infinity (fe_neg_if of 0)
+}

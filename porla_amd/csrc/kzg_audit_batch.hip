@@ -14,8 +14,8 @@
 //   k_kzg_audit_join      per audit: align_value + MSM(align) (align_MAC, Server.hpp:903), the four points of the record to affine
 //                         with one inversion, the 320-byte record
 #include "engine.hpp"
-#include "fixed_base.hip.h"
 #include "icc.hip.h"
+#include "kzg_batch.hip.h"
 #include "../../include/porla_gpu.h"
 
 #include <cstddef>
@@ -27,7 +27,6 @@ namespace porla {
 constexpr size_t KZG_AUDIT_RECORD = PORLA_KZG_AUDIT_RECORD_BYTES;
 constexpr uint32_t KZG_AUDIT_MAX_MACS = 32768;     // the batched MSM's entry limit (SMALL_MAX_N)
 constexpr uint32_t KZG_OPEN_WAVES = 4;             // audits per block of k_kzg_open
-constexpr uint32_t KZG_GATHER_PAIRS = 64;          // pairs per block of k_kzg_audit_gather (four lanes per pair)
 
 // ---- the KZG opening, a wave per audit.  f = B_k reduced mod r (fr.SetBytes), n >= 1 coefficients.  C_j = sum_{i >= j} f_i z^(i-j)
 // (C_n = 0) gives every output: h[j - 1] = C_j for 1 <= j < n, h[n - 1] = 0, y = C_0.  Lane l owns the run [s, e) of m = ceil(n / 64)
@@ -101,29 +100,17 @@ k_kzg_open(const KzgAuditDesc* __restrict__ desc, uint32_t k, uint32_t n, uint8_
 }
 
 // ---- the MSM entries of every audit: entry 2a = (coef_i, mac_store[idx_i]), entry 2a + 1 = (coef_i, align_store[idx_i]), i < n_macs,
-// at pairs [pair0, pair0 + n) and [pair0 + n, pair0 + 2n); four lanes per pair as k_audit_gather (msm_impl.hip.h), the scalar a 32-byte
-// big-endian integer (bn254_scalar_set_int).  Block b covers pairs [64 (b - gat0), ...) of audit gat_audit[b].
+// at pairs [pair0, pair0 + n) and [pair0 + n, pair0 + 2n).  Block b covers pairs [64 (b - gat0), ...) of audit gat_audit[b].
 __global__ void __launch_bounds__(4 * KZG_GATHER_PAIRS)
 k_kzg_audit_gather(const KzgAuditDesc* __restrict__ desc, const uint32_t* __restrict__ gat_audit, uint8_t* __restrict__ scalars,
                    uint8_t* __restrict__ points) {
     const KzgAuditDesc& D = desc[gat_audit[blockIdx.x]];
-    const uint32_t i = (blockIdx.x - D.gat0) * KZG_GATHER_PAIRS + (threadIdx.x >> 2), q = threadIdx.x & 3u;
-    if (i >= D.n_macs) return;
-    const uint64_t src = D.mac_idx[i];
-    const size_t pa = D.pair0 + i, pb = D.pair0 + D.n_macs + i;
-    reinterpret_cast<uint4*>(points + 64 * pa)[q] = reinterpret_cast<const uint4*>(D.mac_store + 64 * src)[q];
-    reinterpret_cast<uint4*>(points + 64 * pb)[q] = reinterpret_cast<const uint4*>(D.align_store + 64 * src)[q];
-    if (q < 2) {
-        uint4 z = make_uint4(0, 0, 0, 0);
-        if (q == 1) z.w = __builtin_bswap32(D.mac_coef[i]);   // bytes 28..31 of the big-endian scalar
-        reinterpret_cast<uint4*>(scalars + 32 * pa)[q] = z;
-        reinterpret_cast<uint4*>(scalars + 32 * pb)[q] = z;
-    }
+    kzg_gather_pairs<true>(D.mac_store, D.align_store, D.mac_idx, D.mac_coef, D.n_macs, D.pair0, blockIdx.x - D.gat0, scalars, points);
 }
 
 // ---- the records: a lane per audit.  Its commit rows' sums (c_k, B_k, h_k at commit[(3a + j) S]) and MSM sums (msm[2a], msm[2a + 1]);
 // combined_align = MSM(align) + Commit(c) (align_MAC); then commitment, proof_h, combined_mac and combined_align to affine with ONE
-// inversion (Montgomery's trick over their ZZZ, as k_fb_finish does for a lane's rows), big-endian, 64 zero bytes = infinity.
+// inversion, big-endian, 64 zero bytes = infinity.
 __global__ void __launch_bounds__(64)
 k_kzg_audit_join(const XYZZ<Bn254Fp>* __restrict__ commit, uint32_t S, const XYZZ<Bn254Fp>* __restrict__ msm, uint32_t k,
                  uint8_t* __restrict__ out) {
@@ -140,39 +127,8 @@ k_kzg_audit_join(const XYZZ<Bn254Fp>* __restrict__ commit, uint32_t S, const XYZ
         const XYZZ<M> av = load_xyzz<M>(commit + (size_t)3 * a * S);
         xyzz_add_cold<M>(&p[3], &av);
     }
-    Fe<M> zzz[4], pre[4];
-    bool live[4];
-    Fe<M> acc = fe_one<M>();
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        live[j] = !fe_is_zero<M>(p[j].zzz);
-        zzz[j] = live[j] ? p[j].zzz : fe_one<M>();
-        pre[j] = acc;
-        acc = fe_mul_call<M>(acc, zzz[j]);
-    }
-    Fe<M> inv;
-    if constexpr (C::F30_BUCKETS) inv = fe_inv_safegcd<M>(acc);
-    else inv = fe_inv_dev<M>(acc);
-    Fe<M> one = fe_zero<M>();
-    one.v[0] = 1;
-    uint8_t* rec = out + (size_t)a * KZG_AUDIT_RECORD;
     constexpr uint32_t at[4] = {0, 64, 192, 256};
-#pragma unroll
-    for (int j = 3; j >= 0; j--) {
-        const Fe<M> inv_j = fe_mul_call<M>(inv, pre[j]);
-        inv = fe_mul_call<M>(inv, zzz[j]);
-        uint8_t* dst = rec + at[j];
-        if (!live[j]) {
-            const uint4 z = make_uint4(0, 0, 0, 0);
-            uint4* q = reinterpret_cast<uint4*>(dst);
-            q[0] = z; q[1] = z; q[2] = z; q[3] = z;
-            continue;
-        }
-        const Affine<M> af = xyzz_to_affine_with_inv<M>(p[j], inv_j);
-        const Fe<M> x = fe_mul_call<M>(af.x, one), y = fe_mul_call<M>(af.y, one);   // out of Montgomery form
-        store_be256(dst, x.v);
-        store_be256(dst + 32, y.v);
-    }
+    xyzz_to_be_one_inv<C, 4>(p, out + (size_t)a * KZG_AUDIT_RECORD, at);
 }
 
 // ---- per-device workspace: the work list (pinned staging + device copy), the combine's partials, the commit rows, the MSM entries and

@@ -21,6 +21,12 @@ class KzgAuditReq(ctypes.Structure):
                 ("d_mac_coef", ctypes.c_void_p), ("n_macs", ctypes.c_size_t), ("random_point", ctypes.c_ulonglong)]
 
 
+class KzgVerifyReq(ctypes.Structure):
+    """porla_kzg_verify_req, include/porla_gpu.h: one reply of porla_kzg_verify_batch_device (PORLA_KZG_VERIFY_REQ_BYTES = 64)."""
+    _fields_ = [("d_comp_store", ctypes.c_void_p), ("d_idx", ctypes.c_void_p), ("d_coef", ctypes.c_void_p), ("n", ctypes.c_size_t),
+                ("alpha", ctypes.c_uint8 * 32)]
+
+
 def load():
     """Load the engine.  When torch is importable it is imported FIRST so that the HIP runtime the process
     ends up with is the one torch ships (both have soname libamdhip64.so.7; two runtimes in one process
@@ -125,6 +131,8 @@ def _declare(L):
     L.porla_kzg_audit_device.restype = ctypes.c_int
     L.porla_kzg_audit_batch_device.argtypes = [ctypes.POINTER(KzgAuditReq), sz, vp, vp, vp]
     L.porla_kzg_audit_batch_device.restype = ctypes.c_int
+    L.porla_kzg_verify_batch_device.argtypes = [ctypes.POINTER(KzgVerifyReq), sz, vp, u8p, u8p, vp]
+    L.porla_kzg_verify_batch_device.restype = ctypes.c_int
     L.porla_kzg_digest_batch_device.argtypes = [vp, sz, vp, vp]; L.porla_kzg_digest_batch_device.restype = ctypes.c_int
     L.porla_kzg_complement_batch_device.argtypes = [vp, sz, vp, vp]; L.porla_kzg_complement_batch_device.restype = ctypes.c_int
     L.porla_kzg_mac_batch_device.argtypes = [vp, vp, sz, vp, vp]; L.porla_kzg_mac_batch_device.restype = ctypes.c_int

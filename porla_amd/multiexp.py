@@ -10,7 +10,7 @@ Server.hpp:183-188,365-397,550-558).  Buffers are Python bytes/bytearray; result
 """
 import ctypes
 
-from .loader import GoSlice, KzgAuditReq, lib
+from .loader import GoSlice, KzgAuditReq, KzgVerifyReq, lib
 
 MAC_SIZE = 64       # COMMITMENT_MAC_SIZE with ENABLE_KZG, config.hpp:26
 SCALAR_SIZE = 32    # bn254_scalar = uint32_t[8], utils.h:64
@@ -433,6 +433,48 @@ def split_audit_records(raw, k):
         out.append(dict(commitment=r[0:64], proof_h=r[64:128], point=r[128:160], claim=r[160:192], combined_mac=r[192:256],
                         combined_align=r[256:320]))
     return out
+
+
+KZG_VERIFY_FULL = 1        # alpha C + sum coef comp == M + alpha A (Client.hpp:849-869)
+KZG_VERIFY_PROOF = 2       # the opening verifies (verify_proof)
+KZG_VERIFY_MALFORMED = 4   # a point of the record has a coordinate >= p or is off the curve
+KZG_VERIFY_PASS = KZG_VERIFY_FULL | KZG_VERIFY_PROOF
+KZG_VERIFY_MAX_K = 10922   # replies per call (include/porla_gpu.h)
+
+
+def kzg_verify_requests(verifs):
+    """a ctypes array of porla_kzg_verify_req from per-reply tuples (d_comp_store, d_idx, d_coef, n, alpha): device pointers (0 ->
+    NULL), the challenge length and the client's alpha as big-endian bytes of at most 32 (left-padded: a 16-byte SECRET_KEY lands in
+    bytes 16..31, as Client::audit places it)"""
+    arr = (KzgVerifyReq * max(len(verifs), 1))()
+    for i, v in enumerate(verifs):
+        if len(v) != 5:
+            raise ValueError("kzg_verify_batch_device: reply %d has %d fields, want 5" % (i, len(v)))
+        comp, idx, coef, n, alpha = v
+        alpha = bytes(alpha)
+        if len(alpha) > 32:
+            raise ValueError("kzg_verify_batch_device: alpha of reply %d is longer than 32 bytes" % i)
+        arr[i] = KzgVerifyReq(comp or None, idx or None, coef or None, n, (ctypes.c_uint8 * 32)(*alpha.rjust(32, b"\0")))
+    return arr
+
+
+def kzg_verify_batch_device(verifs, d_records, weights=None, stream=0):
+    """Client::audit's check of len(verifs) replies in ONE blocking call (porla_kzg_verify_batch_device): reply k is the 320-byte record
+    at d_records + 320 k (as kzg_audit_batch_device writes it), verifs[k] the client's side as kzg_verify_requests takes it.  Returns
+    the status bytes; reply k passes iff status[k] == KZG_VERIFY_PASS.  weights: None (drawn per call, the normal use) or k secret
+    random nonzero weights, as 16-byte big-endian bytes or ints < 2^128."""
+    k = len(verifs)
+    arr = kzg_verify_requests(verifs)
+    w = None
+    if weights is not None:
+        if len(weights) != k:
+            raise ValueError("kzg_verify_batch_device: %d weights for %d replies" % (len(weights), k))
+        w = b"".join(x.to_bytes(16, "big") if isinstance(x, int) else bytes(x) for x in weights)
+        if len(w) != 16 * k:
+            raise ValueError("kzg_verify_batch_device: every weight is 16 bytes")
+    status = ctypes.create_string_buffer(max(k, 1))
+    _check(lib.porla_kzg_verify_batch_device(arr, k, ctypes.c_void_p(d_records or None), w, status, ctypes.c_void_p(stream)))
+    return list(status.raw[:k])
 
 
 def kzg_digest_batch_device(d_rows, n_rows, d_out, stream=0):
