@@ -14,6 +14,8 @@
 //   D  = Q - X3 + 6p                               <= 7
 //   Y3 = R D - Y1 PPP                              <= 1 as one two-product reduction (-Y3 = Rn D + Y1 PPP), <= 3 as T1 - T2 + 2p in the full addition
 // Everything is below 8p < 2^257, so limb 8 stays below 2^18 as the products require.
+// The layer is checked per operation by tools/ec30_check.hip / tests/test_ec30_gpu.py: every function below, both curves, operands up
+// to these bounds (the bounds themselves are restated in tests/ec_vectors.py:BOUNDS and asserted on every result).
 #pragma once
 #include "ec.hip.h"
 #include "fe30.hip.h"

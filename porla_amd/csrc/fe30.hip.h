@@ -349,7 +349,8 @@ __device__ __forceinline__ void f30_ripple(F30<M>& a) {
 }
 
 // K * p written with limbs large enough for a borrow-free limb-wise "+ K p - b" of a NORMAL b whose value is at most
-// (K - 1) p + 2^240: limb 0 gets + 2^30, limbs 1..7 get + 2^30 - 1, limb 8 gets - 1 (the sum is still K p).
+// (K - 1) p + 2^247 (tools/check_fe30_bounds.py:check_sub_tables; fed at exactly that value by tests/test_ec30_gpu.py): limb 0 gets
+// + 2^30, limbs 1..7 get + 2^30 - 1, limb 8 gets - 1 (the sum is still K p).
 template <class M, int K>
 struct KP30 {
     struct Tab { uint32_t v[9]; };
@@ -372,7 +373,7 @@ struct KP30 {
 template <class M, int K>
 constexpr typename KP30<M, K>::Tab KP30<M, K>::T;
 
-// a - b + K p, normal result.  a normal (or any limbs < 2^30 + 2^29), b normal with value <= (K-1) p + 2^240.
+// a - b + K p, normal result.  a normal (or any limbs < 2^30 + 2^29), b normal with value <= (K-1) p + 2^247.
 template <class M, int K>
 __device__ __forceinline__ F30<M> f30_sub(const F30<M>& a, const F30<M>& b) {
     F30<M> r;
@@ -381,7 +382,7 @@ __device__ __forceinline__ F30<M> f30_sub(const F30<M>& a, const F30<M>& b) {
     f30_ripple<M>(r);
     return r;
 }
-// a - 2 b + K p in one pass, normal result.  a, b normal, 2 b <= (K-1) p + 2^240.  The table of K p is the one of f30_sub with
+// a - 2 b + K p in one pass, normal result.  a, b normal, 2 b <= (K-1) p + 2^247.  The table of K p is the one of f30_sub with
 // the borrow allowance doubled (limb 0 + 2^31, limbs 1..7 + 2^31 - 2, limb 8 - 2): every limb-wise sum stays below 2^32
 // (2^30 + 2^30 + 2^31 - 2) and non-negative.
 template <class M, int K>
