@@ -31,6 +31,9 @@
  *   porla_kzg_audit_batch_device
  *                            Server::audit (KZG) of many files or clients at once: K complete audits in one asynchronous
  *                            call, each record the reply Server.hpp:897-915 sends
+ *   porla_ipa_audit_batch_device, porla_ipa_prove_batch_device
+ *                            Server::audit (IPA) of many files or clients at once, the inner-product proof included
+ *                            (Server.hpp:790-892, :2279-2452): K complete replies in one asynchronous call; the prover alone
  *   porla_kzg_verify_batch_device
  *                            Client::audit's check (KZG) of many replies at once, Client.hpp:685-778 and :849-869: K MAC
  *                            checks and ONE folded pairing check per call, a verdict per reply
@@ -305,6 +308,59 @@ typedef struct {
     unsigned long long random_point;                                                        /* 104 */
 } porla_kzg_audit_req;
 int  porla_kzg_audit_batch_device(const porla_kzg_audit_req *reqs, size_t k, void *d_out, void *d_b_out, void *hip_stream);
+/* Server::audit (IPA build) for K independent audits in ONE call, inner-product proofs included (Server.hpp:790-892 and
+ * Server::inner_product_prove, :2279-2452, each): everything on the device and on hip_stream.  porla_ipa_audit_device stops before
+ * the proof; this call goes through it.  gens_u_fb: a secp256k1 fixed base over the 129 points generators[0..127] || u
+ * (porla_fixed_base_create(1, ...)): the audit's two Pedersen commitments use its first 128 points, the prover's rows all 129.  Fewer
+ * than 129 points, or a BN254 base: PORLA_ERR_ARG.  n_cols is fixed at 128: the prover's index pattern is written for NUM_CHUNKS = 128.
+ * reqs is a HOST array of K audits; the first 13 fields are porla_kzg_audit_req's, with secp256k1 stores; a_value is
+ * audit_values[n_points] (Server.hpp:861) as 32 bytes big-endian, taken mod the group order n.
+ * d_out receives K records of PORLA_IPA_AUDIT_RECORD_BYTES, packed back to back, the reply of Server::audit (Server.hpp:880-892):
+ *   commitment(33) | combined_MAC(33) | combined_align(33) | proof(556)
+ * commitment = Commit(B) over the 128 generators; combined_align is the value AFTER align_MAC (Server.hpp:850, :495-529): MSM(align
+ * store) + Commit(c).  Points in libsecp256k1's compressed form: 0x02 | (y & 1), then X big-endian.  The reference cannot serialise
+ * infinity (secp256k1_eckey_pubkey_serialize returns 0 and writes nothing); this library writes 33 ZERO bytes there, in the record
+ * and in the proof, and hashes those 33 bytes into the transcript.
+ *   proof = c(32) | 6 x (L(33) | R(33)) | a0(32) b0(32) a1(32) b1(32)
+ * scalars as eight little-endian 32-bit words from the low word up (convert_ZZ_to_arr, utils.h:353-364), i.e. 32 bytes little-endian;
+ * the proof of a = B, b = (v, v^2, v^4, ..., v^(2^127)), v = a_value -- repeated squaring, Server.hpp:863-867.  The transcript is the
+ * reference's: one SHA-256 object that keeps being written to after each finalize, which zeroes its state while its byte counter runs
+ * on (secp256k1_lib/hash_impl.h:151-165).
+ * d_b_out (may be NULL): K x 128 x 32 bytes, B mod p_icc big-endian per audit, as porla_ipa_audit_device's b_out.
+ * commitment, combined_MAC and B equal porla_ipa_audit_device's outputs for the same audit, and combined_align equals the secp256k1
+ * sum of its combined_align and align_value.
+ * Asynchronous: enqueued on hip_stream, returns without waiting on the host; the work waits for whatever the caller had enqueued on
+ * hip_stream before the call; d_out is complete when hip_stream is.  No internal side stream.
+ * PORLA_ERR_ARG (message in porla_gpu_last_error), checked before the device is touched: reqs, d_out or gens_u_fb NULL while k > 0; a
+ * NULL array whose count is > 0; n_macs > 32 768 (the batched MSM's entry limit: larger audits keep using porla_ipa_audit_device);
+ * n64 + n32 >= 2^32; a byte size that overflows.  k = 0 returns 0 and writes nothing.  Valid arguments without a device:
+ * PORLA_ERR_NO_DEVICE (a fixed base exists only where a device does, so its curve and point count are read after that check).
+ * One fixed sequence of launches per call, whatever K: the row combine of all K audits (two launches), the MSM gather, the batched MSM
+ * over the 2K entries, ONE commitment pass over the 2K rows [c_k, B_k] and the join that writes the three points; then the prover:
+ * its opening (c, the first hash), and six times the round's rows [L_k, R_k] (129 coefficients), ONE commitment pass over these 2K
+ * rows, and the round's close (L, R into the proof, the next challenge, the fold of a and b).  The host round trips of the
+ * single-call path are what the batch saves: measured on an MI355X it draws level with K single-call audits at K = 8 and is 6x
+ * their rate at K = 64 (profiles/r09_a_ipa_audit_batch.jsonl); below 8 audits the fixed sequence (about 4.3 ms, mostly the six
+ * rounds' inversion chains) is not amortised and porla_ipa_audit_device with the rounds on the host is the faster path.
+ * Calls from several threads on several streams, and beside porla_ipa_audit_device and the fixed base's other users, are safe. */
+#define PORLA_IPA_AUDIT_RECORD_BYTES 655   /* 33 * 3 + PORLA_IPA_PROOF_BYTES */
+#define PORLA_IPA_PROOF_BYTES        556   /* 32 + 6 * 66 + 128 */
+#define PORLA_IPA_AUDIT_REQ_BYTES    136   /* sizeof(porla_ipa_audit_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    const void *d_rows64; const uint64_t *d_idx64; const uint32_t *d_coef64; size_t n64;   /* offsets 0, 8, 16, 24 */
+    const void *d_rows32; const uint64_t *d_idx32; const uint32_t *d_coef32; size_t n32;   /* 32, 40, 48, 56 */
+    const void *d_mac_store; const void *d_align_store;                                     /* 64, 72 */
+    const uint64_t *d_mac_idx; const uint32_t *d_mac_coef; size_t n_macs;                   /* 80, 88, 96 */
+    uint8_t a_value[32];                                                                    /* 104 */
+} porla_ipa_audit_req;
+int  porla_ipa_audit_batch_device(porla_fixed_base *gens_u_fb, const porla_ipa_audit_req *reqs, size_t k, void *d_out,
+                                  void *d_b_out, void *hip_stream);
+/* The prover alone: K proofs of Server::inner_product_prove(a, b, proof).  d_a, d_b: K x 128 x 32 bytes big-endian on the device
+ * (16-byte aligned), taken mod n; d_proofs: K x PORLA_IPA_PROOF_BYTES, packed.  gens_u_fb, the proof's bytes and the contract
+ * (asynchronous on hip_stream, argument checks, k = 0, no device) as porla_ipa_audit_batch_device, which runs the same code on
+ * (B_k, powers of a_value). */
+int  porla_ipa_prove_batch_device(porla_fixed_base *gens_u_fb, const void *d_a, const void *d_b, size_t k, void *d_proofs,
+                                  void *hip_stream);
 /* Client::audit's check (KZG build, Client.hpp:633-880) of K replies in ONE call: reply k is the 320-byte record k of d_records
  * (the layout porla_kzg_audit_batch_device writes: commitment C | proof_h H | point z | claim y | combined_mac M | combined_align A),
  * reqs[k] the client's side of that audit: the level's MAC complements d_comp_store (64-byte big-endian affine points, as

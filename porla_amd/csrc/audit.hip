@@ -209,8 +209,8 @@ k_audit_finish(const unsigned long long* __restrict__ partial, uint32_t n_blocks
 }
 
 // The row combine of porla_kzg_audit_batch_device: block b of the work list runs block b - blk0 of its audit's combine (partials of
-// the audit from blk0 on); the finish runs per audit (blockIdx.y) and writes the alignment scalars and B big-endian into the
-// audit's first two commit rows (a flat grid: fin_blocks blocks per audit).
+// the audit from blk0 on); the finish runs per audit and writes the alignment scalars (mod Q) and B big-endian to the
+// caller's two destinations, audit_stride bytes apart per audit (a flat grid: fin_blocks blocks per audit).
 static_assert(AUDIT_BATCH_SLICES == AUD_SLICES, "the batched combine runs the large-challenge block");
 static __global__ void __launch_bounds__(AUD_SLICES * AUD_COLS) __attribute__((amdgpu_waves_per_eu(4, 4)))
 k_audit_accumulate_batch(const KzgAuditDesc* __restrict__ desc, const uint32_t* __restrict__ blk_audit, uint32_t n_cols,
@@ -219,20 +219,21 @@ k_audit_accumulate_batch(const KzgAuditDesc* __restrict__ desc, const uint32_t* 
     audit_accumulate_block<AUD_SLICES>(D.rows64, D.idx64, D.coef64, D.n64, D.rows32, D.idx32, D.coef32, D.n32, n_cols, per_slice,
                                        partial + (size_t)D.blk0 * ACC_LIMBS * n_cols, blockIdx.x - D.blk0, blockIdx.y);
 }
+template <class Q>
 static __global__ void __launch_bounds__(AUD_FIN_SPLIT * ACC_LIMBS * AUD_FIN_COLS)
 k_audit_finish_batch(const KzgAuditDesc* __restrict__ desc, const unsigned long long* __restrict__ partial, uint32_t n_cols,
-                     uint32_t fin_blocks, uint8_t* __restrict__ rows3) {
+                     uint32_t fin_blocks, uint8_t* __restrict__ sc_out, uint8_t* __restrict__ be_out, size_t audit_stride) {
     const uint32_t a = blockIdx.x / fin_blocks;
     const KzgAuditDesc& D = desc[a];
-    uint8_t* sc = rows3 + (size_t)a * 3 * 32 * n_cols;
-    audit_finish_block<IccBn254Fr>(partial + (size_t)D.blk0 * ACC_LIMBS * n_cols, D.nblk, n_cols, nullptr, nullptr, sc + 32 * (size_t)n_cols,
-                                   sc, blockIdx.x - a * fin_blocks);
+    audit_finish_block<Q>(partial + (size_t)D.blk0 * ACC_LIMBS * n_cols, D.nblk, n_cols, nullptr, nullptr, be_out + a * audit_stride,
+                          sc_out + a * audit_stride, blockIdx.x - a * fin_blocks);
 }
 
 size_t audit_combine_partial_bytes(uint32_t n_blocks, uint32_t n_cols) { return (size_t)n_blocks * ACC_LIMBS * n_cols * 8; }
 
 int audit_combine_batch_launch(const KzgAuditDesc* d_desc, const uint32_t* d_blk_audit, uint32_t n_blocks, uint32_t k, uint32_t n_cols,
-                               uint32_t per_slice, void* d_partial, uint8_t* d_rows3, hipStream_t stream) {
+                               uint32_t per_slice, void* d_partial, int curve, uint8_t* d_sc, uint8_t* d_be, size_t audit_stride,
+                               hipStream_t stream) {
     {
         ProfScope ps("audit_batch_accumulate", stream);
         hipLaunchKernelGGL(k_audit_accumulate_batch, dim3(n_blocks, (n_cols + AUD_COLS - 1) / AUD_COLS), dim3(AUD_SLICES * AUD_COLS), 0, stream,
@@ -241,8 +242,13 @@ int audit_combine_batch_launch(const KzgAuditDesc* d_desc, const uint32_t* d_blk
     {
         ProfScope ps("audit_batch_finish", stream);
         const uint32_t fin_blocks = (n_cols + AUD_FIN_COLS - 1) / AUD_FIN_COLS;
-        hipLaunchKernelGGL(k_audit_finish_batch, dim3(fin_blocks * k), dim3(AUD_FIN_SPLIT * ACC_LIMBS * AUD_FIN_COLS), 0, stream, d_desc,
-                           (const unsigned long long*)d_partial, n_cols, fin_blocks, d_rows3);
+        const dim3 grid(fin_blocks * k), block(AUD_FIN_SPLIT * ACC_LIMBS * AUD_FIN_COLS);
+        if (curve == 0)
+            hipLaunchKernelGGL((k_audit_finish_batch<IccBn254Fr>), grid, block, 0, stream, d_desc, (const unsigned long long*)d_partial, n_cols,
+                               fin_blocks, d_sc, d_be, audit_stride);
+        else
+            hipLaunchKernelGGL((k_audit_finish_batch<IccSecp256k1Fn>), grid, block, 0, stream, d_desc, (const unsigned long long*)d_partial,
+                               n_cols, fin_blocks, d_sc, d_be, audit_stride);
     }
     PORLA_HIP(hipGetLastError());
     return PORLA_OK;

@@ -277,12 +277,6 @@ struct IccSecp256k1FnHost {  // secp256k1 group order, only P is needed (fe_redu
 };
 }  // namespace
 
-struct porla_fixed_base {
-    int curve;
-    FixedBase<Bn254G1> bn;
-    FixedBase<Secp256k1G> secp;
-};
-
 extern "C" {
 
 int porla_gpu_device_count(void) {

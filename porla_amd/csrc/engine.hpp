@@ -127,6 +127,53 @@ struct UseFence {
     void reset() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; used = false; last = nullptr; }
 };
 
+// A host-built work list on its way to the device (the batched audits): a pinned staging buffer, the event of its last upload, and
+// the buffers whose upload was still queued when a later call came (freed once that copy is done, so that no call waits on the
+// host for earlier work).  Used under the mutex that serialises the owner's enqueue.
+struct PinnedList {
+    void* h = nullptr;
+    size_t cap = 0;
+    hipEvent_t upload = nullptr;                                  // recorded after the last upload from h
+    std::vector<std::pair<void*, hipEvent_t>> retired;
+    // a pinned buffer of at least `bytes` whose previous upload is done
+    int stage(size_t bytes) {
+        for (size_t i = 0; i < retired.size();) {
+            const hipError_t q = hipEventQuery(retired[i].second);
+            if (q == hipErrorNotReady) { i++; continue; }
+            PORLA_HIP(q);
+            PORLA_HIP(hipHostFree(retired[i].first));
+            PORLA_HIP(hipEventDestroy(retired[i].second));
+            retired.erase(retired.begin() + (long)i);
+        }
+        if (upload) {
+            const hipError_t q = hipEventQuery(upload);
+            if (q == hipErrorNotReady) {
+                retired.emplace_back(h, upload);
+                h = nullptr;
+                cap = 0;
+                upload = nullptr;
+            } else {
+                PORLA_HIP(q);
+            }
+        }
+        if (cap < bytes) {
+            if (h) PORLA_HIP(hipHostFree(h));
+            h = nullptr;
+            cap = 0;
+            PORLA_HIP(hipHostMalloc(&h, bytes + bytes / 4 + 4096, hipHostMallocDefault));
+            cap = bytes + bytes / 4 + 4096;
+        }
+        return PORLA_OK;
+    }
+    // the copy of the first `bytes` of h to `dst` on `stream`, and its event
+    int send(void* dst, size_t bytes, hipStream_t stream) {
+        PORLA_HIP(hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, stream));
+        if (!upload) PORLA_HIP(hipEventCreateWithFlags(&upload, hipEventDisableTiming));
+        PORLA_HIP(hipEventRecord(upload, stream));
+        return PORLA_OK;
+    }
+};
+
 struct Workspace {
     std::mutex mu;   // held while kernels are enqueued on / results folded from this slot (the registry has its own lock)
     int device = -1;
@@ -230,6 +277,15 @@ struct FixedBase {
     static bool small_ok(size_t n_rows, size_t n_coeffs);
 };
 
+}  // namespace porla
+// the C ABI's fixed-base handle (include/porla_gpu.h): one table, on the curve it was created for
+struct porla_fixed_base {
+    int curve;
+    porla::FixedBase<porla::Bn254G1> bn;
+    porla::FixedBase<porla::Secp256k1G> secp;
+};
+namespace porla {
+
 extern std::mutex g_ws_mu;   // the workspace registry (lookup / creation / release); a slot's use is under Workspace::mu
 extern int g_window_override;
 extern int g_small_mode;      // single-launch path for n <= SMALL_MAX_N (32 768): 1 on (default), 0 off
@@ -249,8 +305,8 @@ int icc_wt_scalar_be(size_t n_total, unsigned long long write_step, uint8_t out[
 int icc_network_matrix_device(int curve, size_t n, unsigned long long write_step, int part, uint8_t* d_rows_out,
                               hipStream_t stream);
 
-// One audit of porla_kzg_audit_batch_device as the device kernels see it (kzg_audit_batch.hip builds them, audit.hip and
-// kzg_audit_batch.hip read them): the caller's arrays, the audit's share of the row combine (blocks [blk0, blk0 + nblk) of the
+// One audit of porla_kzg_audit_batch_device (and of porla_ipa_audit_batch_device: z unused) as the device kernels see it
+// (kzg_audit_batch.hip and ipa_audit_batch.hip build them; they and audit.hip read them): the caller's arrays, the audit's share of the row combine (blocks [blk0, blk0 + nblk) of the
 // partials) and of the batched MSM (its MAC entry at pairs [pair0, pair0 + n_macs), its alignment entry right behind).
 struct KzgAuditDesc {
     const uint8_t* rows64; const uint64_t* idx64; const uint32_t* coef64;
@@ -263,9 +319,11 @@ struct KzgAuditDesc {
 static_assert(sizeof(KzgAuditDesc) == 120, "KzgAuditDesc: 80 bytes of pointers, 24 of counts, z, pair0");
 // audit.hip: the row combine of k audits (one launch each for the accumulation and the finish).  blk_audit[b] = the audit of combine
 // block b; per_slice rows per slice everywhere; partial holds n_blocks * ACC_LIMBS * n_cols 64-bit sums.  Audit a's alignment
-// scalars go to rows3 + 3 a n_cols 32 and B (big-endian, mod p_icc) to the row after it.
+// scalars (mod the group order of `curve`: 0 = BN254, 1 = secp256k1) go to d_sc + a * audit_stride and B (big-endian, mod p_icc) to
+// d_be + a * audit_stride, n_cols 32-byte values each (the batched KZG audit: rows 0 and 1 of the audit's three commit rows).
 int audit_combine_batch_launch(const KzgAuditDesc* d_desc, const uint32_t* d_blk_audit, uint32_t n_blocks, uint32_t k, uint32_t n_cols,
-                               uint32_t per_slice, void* d_partial, uint8_t* d_rows3, hipStream_t stream);
+                               uint32_t per_slice, void* d_partial, int curve, uint8_t* d_sc, uint8_t* d_be, size_t audit_stride,
+                               hipStream_t stream);
 size_t audit_combine_partial_bytes(uint32_t n_blocks, uint32_t n_cols);
 constexpr uint32_t AUDIT_BATCH_SLICES = 8;   // row slices per block of the batched combine (audit.hip: AUD_SLICES)
 // kzg_abi.hip: commit n_rows contiguous rows of n_samples coefficients against the resident SRS table, leave the row sums in the

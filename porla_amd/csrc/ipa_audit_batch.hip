@@ -1,0 +1,559 @@
+// Server::audit (IPA build) for K independent audits in ONE asynchronous call, inner-product proofs included
+// (include/porla_gpu.h: porla_ipa_audit_batch_device, porla_ipa_prove_batch_device).  porla_ipa_audit_device stops before the proof and
+// leaves Server::inner_product_prove (porla/Server/Server.hpp:2279-2452) to the caller: six blocking two-row commitments per audit with
+// the folding and the transcript hash on the host between them.  For K audits the rounds stay sequential, but each round is ONE
+// fixed-base pass over 2K rows, and everything between the passes runs on the device, on the caller's stream:
+//
+//   upload                one copy of the host-built work list (a_values, audit descriptors, combine blocks, gather blocks)
+//   audit_batch_*         the row combine of all K audits (audit.hip): alignment scalars c_k (mod n) and B_k into the rows [c_k, B_k]
+//   k_ipa_audit_gather    the 2K MSM entries (coef_i, MAC[idx_i]) and (coef_i, align[idx_i]); batch_*: the batched MSM over them
+//   fb_commit / fb_fold   ONE pass over the 2K rows [c_k, B_k] (128 coefficients), then
+//   k_ipa_audit_join      per audit: Commit(B), MSM(MAC), MSM(align) + Commit(c) (align_MAC) to affine with one inversion, compressed
+//   k_ipa_open            a block per audit: a = B_k, b = (v, v^2, v^4, ...) by repeated squaring (Server.hpp:863-867), x_values = 1,
+//                         c = <a, b> mod n into the proof, the first transcript hash
+//   six times:
+//   k_ipa_round_rows      a block per audit: x, 1/x from the hash, cL, cR, the L row and the R row (129 coefficients: the
+//                         generators' and u's), the x_values updates
+//   fb_commit / fb_fold   ONE pass over the 2K rows [L_k, R_k]
+//   k_ipa_round_close     a block per audit: L, R to affine with one inversion, compressed into the proof; the next hash; the fold of
+//                         a and b; after the last round a0 b0 a1 b1
+//
+// The transcript (Server.hpp:2306-2310, :2381-2382, :2431-2432) is ONE secp256k1_sha256 object that is written to again after
+// every finalize.  finalize (secp256k1_lib/hash_impl.h:151-165) pads, emits the state and sets the eight state words to ZERO while the
+// byte counter keeps counting, padding included.  So h0 = SHA-256(tag | c), and every later hash is one compression from the all-zero
+// state over a 33-byte point padded with the cumulative length: 128 + 64 (i - 1) + 33 bytes for the i-th of them.  The hash over L
+// is overwritten before anything reads it and leaves no trace in the state, so only R's is computed: the challenge of round r + 1.
+#include "engine.hpp"
+#include "icc.hip.h"
+#include "kzg_batch.hip.h"
+#include "../../include/porla_gpu.h"
+
+#include <cstddef>
+#include <mutex>
+#include <vector>
+
+namespace porla {
+
+constexpr size_t IPA_RECORD = PORLA_IPA_AUDIT_RECORD_BYTES;
+constexpr size_t IPA_PROOF = PORLA_IPA_PROOF_BYTES;
+constexpr uint32_t IPA_N = 128;                    // NUM_CHUNKS: the prover's index pattern is written for it
+constexpr uint32_t IPA_ROUNDS = 6;                 // half_width = 64 .. 2
+constexpr uint32_t IPA_ROW_COEFFS = IPA_N + 1;     // the generators' coefficients, then u's
+constexpr uint32_t IPA_AUDIT_MAX_MACS = 32768;     // the batched MSM's entry limit (SMALL_MAX_N)
+static_assert(IPA_PROOF == 32 + IPA_ROUNDS * 66 + 128 && IPA_RECORD == 99 + IPA_PROOF, "the reply of Server.hpp:856, :880-892");
+
+// the prover's state of one audit between kernels, 32-bit words: a, b, x_values (Montgomery residues mod n), then the transcript's last
+// hash (the eight state words), x and 1 / x of the current round (Montgomery)
+constexpr uint32_t ST_A = 0, ST_B = 8 * IPA_N, ST_XV = 16 * IPA_N, ST_H = 24 * IPA_N, ST_X = ST_H + 8, ST_XI = ST_X + 8;
+constexpr uint32_t ST_WORDS = ST_XI + 8;
+
+using Fn = IccSecp256k1Fn;
+
+struct Sha256K {
+    static constexpr uint32_t K[64] = {
+        0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u, 0xd807aa98u, 0x12835b01u,
+        0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu,
+        0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau, 0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u,
+        0x06ca6351u, 0x14292967u, 0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
+        0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u, 0x19a4c116u, 0x1e376c08u,
+        0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u,
+        0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
+    // the transcript's tag, "hash of P, c, etc. all that jazz" (Server.hpp:2284), as big-endian words
+    static constexpr uint32_t TAG[8] = {0x68617368u, 0x206f6620u, 0x502c2063u, 0x2c206574u, 0x632e2061u, 0x6c6c2074u, 0x68617420u, 0x6a617a7au};
+    static constexpr uint32_t IV[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+};
+
+__device__ __forceinline__ uint32_t rotr32(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+// one SHA-256 compression of the 16 big-endian words w (destroyed) into the state s; fully unrolled, so that the message schedule
+// stays in registers
+__device__ __forceinline__ void sha256_compress(uint32_t (&s)[8], uint32_t (&w)[16]) {
+    uint32_t v[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) v[i] = s[i];
+#pragma unroll
+    for (int t = 0; t < 64; t++) {
+        if (t >= 16) {
+            const uint32_t w15 = w[(t + 1) & 15], w2 = w[(t + 14) & 15];
+            w[t & 15] += (rotr32(w15, 7) ^ rotr32(w15, 18) ^ (w15 >> 3)) + w[(t + 9) & 15] + (rotr32(w2, 17) ^ rotr32(w2, 19) ^ (w2 >> 10));
+        }
+        const uint32_t e = v[4], a = v[0];
+        const uint32_t t1 = v[7] + (rotr32(e, 6) ^ rotr32(e, 11) ^ rotr32(e, 25)) + ((e & v[5]) ^ (~e & v[6])) + Sha256K::K[t] + w[t & 15];
+        const uint32_t t2 = (rotr32(a, 2) ^ rotr32(a, 13) ^ rotr32(a, 22)) + ((a & v[1]) ^ (a & v[2]) ^ (v[1] & v[2]));
+        v[7] = v[6]; v[6] = v[5]; v[5] = v[4]; v[4] = v[3] + t1; v[3] = v[2]; v[2] = v[1]; v[1] = v[0]; v[0] = t1 + t2;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) s[i] += v[i];
+}
+
+// 32 bytes little-endian (convert_ZZ_to_arr, utils.h:353-364) of a plain residue at any address
+__device__ __forceinline__ void store_le256_bytes(uint8_t* dst, const uint32_t v[8]) {
+#pragma unroll
+    for (int i = 0; i < 32; i++) dst[i] = (uint8_t)(v[i >> 2] >> (8 * (i & 3)));
+}
+// a point in libsecp256k1's compressed form at any address: 0x02 | (y & 1), X big-endian; infinity (which the reference cannot
+// serialise) as 33 zero bytes
+__device__ __forceinline__ void store_compressed(uint8_t* dst, bool live, const uint32_t x[8], const uint32_t y[8]) {
+    dst[0] = live ? (uint8_t)(2u | (y[0] & 1u)) : (uint8_t)0;
+#pragma unroll
+    for (int i = 0; i < 32; i++) dst[1 + i] = live ? (uint8_t)(x[7 - (i >> 2)] >> (24 - 8 * (i & 3))) : (uint8_t)0;
+}
+
+__device__ __forceinline__ Fe<Fn> st_load(const uint32_t* st, uint32_t at) { return ld_fe<Fn>(st + at); }
+__device__ __forceinline__ void st_store(uint32_t* st, uint32_t at, const Fe<Fn>& f) { st_fe<Fn>(st + at, f); }
+
+// the sum of the 128 lanes' values mod n, to every lane (red: 128 x 8 words of LDS, free again on return)
+__device__ __forceinline__ Fe<Fn> block_sum(Fe<Fn> v, uint32_t (*red)[8]) {
+    const uint32_t t = threadIdx.x;
+#pragma unroll
+    for (int w = 0; w < 8; w++) red[t][w] = v.v[w];
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t s = IPA_N / 2; s >= 1; s >>= 1) {
+        if (t < s) {
+            Fe<Fn> o;
+#pragma unroll
+            for (int w = 0; w < 8; w++) o.v[w] = red[t + s][w];
+            v = fe_add<Fn>(v, o);
+#pragma unroll
+            for (int w = 0; w < 8; w++) red[t][w] = v.v[w];
+        }
+        __syncthreads();
+    }
+    Fe<Fn> r;
+#pragma unroll
+    for (int w = 0; w < 8; w++) r.v[w] = red[0][w];
+    __syncthreads();
+    return r;
+}
+
+// 32 big-endian bytes taken mod n, in the Montgomery form
+__device__ __forceinline__ Fe<Fn> load_scalar_mont(const uint8_t* src) {
+    Fe<Fn> f;
+    load_be256(f.v, src);
+    fe_reduce_plain<Fn>(f.v, Fn::MAX_Q_IN);
+    return fe_to_mont<Fn>(f);
+}
+
+// ---- the opening of the proof, a block of 128 lanes per audit, lane j = element j.  a from a_src (128 x 32 bytes big-endian per audit);
+// b from b_src likewise, or, with a_values, b_j = v^(2^j): A[i] = A_value, A_value = A_value^2 (Server.hpp:863-867).  c = <a, b> mod n
+// (Server.hpp:2286) goes to the proof's first 32 bytes, h0 = SHA-256(tag | c) to the state.  b_out: the audit's copy of B.
+__global__ void __launch_bounds__(IPA_N)
+k_ipa_open(const uint8_t* __restrict__ a_src, size_t a_stride, const uint8_t* __restrict__ b_src, const uint8_t* __restrict__ a_values,
+           uint32_t* __restrict__ state, uint8_t* __restrict__ proofs, size_t proof_stride, uint8_t* __restrict__ b_out) {
+    __shared__ uint32_t red[IPA_N][8];
+    const uint32_t k = blockIdx.x, j = threadIdx.x;
+    uint32_t* st = state + (size_t)k * ST_WORDS;
+    const uint8_t* ap = a_src + k * a_stride + 32 * (size_t)j;
+    const Fe<Fn> a = load_scalar_mont(ap);
+    if (b_out) {
+        const uint4* s4 = reinterpret_cast<const uint4*>(ap);
+        uint4* d4 = reinterpret_cast<uint4*>(b_out + ((size_t)k * IPA_N + j) * 32);
+        d4[0] = s4[0]; d4[1] = s4[1];
+    }
+    Fe<Fn> b;
+    if (a_values) {
+        b = load_scalar_mont(a_values + 32 * (size_t)k);
+#pragma unroll 1
+        for (uint32_t i = 0; i + 1 < IPA_N; i++) {
+            const Fe<Fn> sq = fe_mul<Fn>(b, b);
+            if (i < j) b = sq;
+        }
+    } else {
+        b = load_scalar_mont(b_src + ((size_t)k * IPA_N + j) * 32);
+    }
+    st_store(st, ST_A + 8 * j, a);
+    st_store(st, ST_B + 8 * j, b);
+    st_store(st, ST_XV + 8 * j, fe_one<Fn>());
+    const Fe<Fn> c = fe_from_mont<Fn>(block_sum(fe_mul<Fn>(a, b), red));
+    if (j != 0) return;
+    store_le256_bytes(proofs + k * proof_stride, c.v);
+    uint32_t s[8], w[16];
+#pragma unroll
+    for (int i = 0; i < 8; i++) { s[i] = Sha256K::IV[i]; w[i] = Sha256K::TAG[i]; w[8 + i] = __builtin_bswap32(c.v[i]); }
+    sha256_compress(s, w);
+#pragma unroll
+    for (int i = 0; i < 16; i++) w[i] = 0;
+    w[0] = 0x80000000u;
+    w[15] = 512;
+    sha256_compress(s, w);
+    uint4* h4 = reinterpret_cast<uint4*>(st + ST_H);
+    h4[0] = make_uint4(s[0], s[1], s[2], s[3]);
+    h4[1] = make_uint4(s[4], s[5], s[6], s[7]);
+}
+
+// ---- the rows of one round (Server.hpp:2320-2349, :2388-2399), a block per audit, lane j = generator j.  x = the last hash read as a
+// little-endian integer mod n (convert_arr_to_ZZ_p, utils.h:384-393), 1 / x by Fermat: every lane runs the same chain, which costs
+// the block no more time than one lane running it and saves the broadcast.  A hash that is 0 mod n has no inverse (NTL raises an error
+// there; probability 2^-256): the chain then gives 0 and the kernel goes on.  cL = <a_lo, b_hi>, cR = <a_hi, b_lo> as block sums.
+// With blk = j / half, q = j % half: the L row takes a[q] x_values[j] on odd blk (then x_values[j] *= x), the R row a[half + q]
+// x_values[j] on even blk (then x_values[j] *= 1 / x), 0 elsewhere; coefficient 128 (u's) is cL and cR.  The R row does not depend on
+// L's hash, so both rows go into one commitment pass: rows 2k and 2k + 1 of `rows`, 129 x 32 bytes big-endian each.
+__global__ void __launch_bounds__(IPA_N)
+k_ipa_round_rows(uint32_t* __restrict__ state, uint8_t* __restrict__ rows, uint32_t half) {
+    __shared__ uint32_t red[IPA_N][8];
+    const uint32_t k = blockIdx.x, j = threadIdx.x;
+    uint32_t* st = state + (size_t)k * ST_WORDS;
+    Fe<Fn> x;
+    {
+        const Fe<Fn> h = st_load(st, ST_H);
+#pragma unroll
+        for (int i = 0; i < 8; i++) x.v[i] = __builtin_bswap32(h.v[i]);
+        fe_reduce_plain<Fn>(x.v, Fn::MAX_Q_IN);
+        x = fe_to_mont<Fn>(x);
+    }
+    const Fe<Fn> xi = fe_inv_dev<Fn>(x);
+    Fe<Fn> tl = fe_zero<Fn>(), tr = fe_zero<Fn>();
+    if (j < half) {
+        tl = fe_mul<Fn>(st_load(st, ST_A + 8 * j), st_load(st, ST_B + 8 * (half + j)));
+        tr = fe_mul<Fn>(st_load(st, ST_A + 8 * (half + j)), st_load(st, ST_B + 8 * j));
+    }
+    const Fe<Fn> cl = block_sum(tl, red), cr = block_sum(tr, red);
+    const uint32_t q = j & (half - 1);
+    const bool odd = (j / half) & 1u;
+    Fe<Fn> xv = st_load(st, ST_XV + 8 * j);
+    const Fe<Fn> coef = fe_from_mont<Fn>(fe_mul<Fn>(st_load(st, ST_A + 8 * (odd ? q : half + q)), xv));
+    st_store(st, ST_XV + 8 * j, fe_mul<Fn>(xv, odd ? x : xi));
+    uint8_t* lrow = rows + (size_t)2 * k * IPA_ROW_COEFFS * 32;
+    uint8_t* rrow = lrow + IPA_ROW_COEFFS * 32;
+    const Fe<Fn> zero = fe_zero<Fn>();
+    store_be256(lrow + 32 * j, odd ? coef.v : zero.v);
+    store_be256(rrow + 32 * j, odd ? zero.v : coef.v);
+    if (j == 0) {
+        const Fe<Fn> pl = fe_from_mont<Fn>(cl), pr = fe_from_mont<Fn>(cr);
+        store_be256(lrow + 32 * IPA_N, pl.v);
+        store_be256(rrow + 32 * IPA_N, pr.v);
+        st_store(st, ST_X, x);
+        st_store(st, ST_XI, xi);
+    }
+}
+
+// ---- the end of round r, a block per audit.  Wave 1's first lane: L and R (the pass's sums, row i at sums[i S]) to affine with ONE
+// inversion, compressed into the proof, and the hash over R: the next round's challenge.  Lanes j < half: the fold
+// a'[j] = a[j] x + a[j + half] / x, b'[j] = b[j] / x + b[j + half] x (Server.hpp:2436-2442): a lane writes element j < half only and
+// reads, of the elements below half, only its own.  After the last round lanes 0 and 1 write a0 b0 a1 b1 (Server.hpp:2445-2451).
+__global__ void __launch_bounds__(IPA_N)
+k_ipa_round_close(uint32_t* __restrict__ state, const XYZZ<Secp256k1Fp>* __restrict__ sums, uint32_t S, uint8_t* __restrict__ proofs,
+                  size_t proof_stride, uint32_t round, uint32_t half) {
+    using M = Secp256k1Fp;
+    const uint32_t k = blockIdx.x, j = threadIdx.x;
+    uint32_t* st = state + (size_t)k * ST_WORDS;
+    uint8_t* proof = proofs + k * proof_stride;
+    if (j == 64) {
+        XYZZ<M> p[2];
+        p[0] = load_xyzz<M>(sums + (size_t)2 * k * S);
+        p[1] = load_xyzz<M>(sums + ((size_t)2 * k + 1) * S);
+        uint8_t* dst = proof + 32 + 66 * round;
+        uint32_t w[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) w[i] = 0;
+        xyzz_each_affine_one_inv<Secp256k1G, 2>(p, [&](int i, bool live, const Fe<M>& x, const Fe<M>& y) {
+            store_compressed(dst + 33 * i, live, x.v, y.v);
+            if (i == 1 && live) {          // the 33 bytes of R as big-endian words
+                w[0] = ((2u | (y.v[0] & 1u)) << 24) | (x.v[7] >> 8);
+#pragma unroll
+                for (int t = 1; t < 8; t++) w[t] = (x.v[8 - t] << 24) | (x.v[7 - t] >> 8);
+                w[8] = x.v[0] << 24;
+            }
+        });
+        w[8] |= 0x00800000u;
+        w[15] = 8u * (225u + 128u * round);        // the object's byte count so far: 128 + 64 (2 round + 1) + 33
+        uint32_t s[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) s[i] = 0;
+        sha256_compress(s, w);
+        uint4* h4 = reinterpret_cast<uint4*>(st + ST_H);
+        h4[0] = make_uint4(s[0], s[1], s[2], s[3]);
+        h4[1] = make_uint4(s[4], s[5], s[6], s[7]);
+    }
+    if (j >= half) return;
+    const Fe<Fn> x = st_load(st, ST_X), xi = st_load(st, ST_XI);
+    const Fe<Fn> a = fe_add<Fn>(fe_mul<Fn>(st_load(st, ST_A + 8 * j), x), fe_mul<Fn>(st_load(st, ST_A + 8 * (j + half)), xi));
+    const Fe<Fn> b = fe_add<Fn>(fe_mul<Fn>(st_load(st, ST_B + 8 * j), xi), fe_mul<Fn>(st_load(st, ST_B + 8 * (j + half)), x));
+    st_store(st, ST_A + 8 * j, a);
+    st_store(st, ST_B + 8 * j, b);
+    if (half == 2) {
+        const Fe<Fn> pa = fe_from_mont<Fn>(a), pb = fe_from_mont<Fn>(b);
+        uint8_t* tail = proof + 32 + 66 * IPA_ROUNDS + 64 * j;
+        store_le256_bytes(tail, pa.v);
+        store_le256_bytes(tail + 32, pb.v);
+    }
+}
+
+// ---- the MSM entries of every audit, as the batched KZG audit's: entry 2a = (coef_i, mac_store[idx_i]), entry 2a + 1 = (coef_i,
+// align_store[idx_i]); the stores are 64-byte big-endian affine points on both curves
+__global__ void __launch_bounds__(4 * KZG_GATHER_PAIRS)
+k_ipa_audit_gather(const KzgAuditDesc* __restrict__ desc, const uint32_t* __restrict__ gat_audit, uint8_t* __restrict__ scalars,
+                   uint8_t* __restrict__ points) {
+    const KzgAuditDesc& D = desc[gat_audit[blockIdx.x]];
+    kzg_gather_pairs<true>(D.mac_store, D.align_store, D.mac_idx, D.mac_coef, D.n_macs, D.pair0, blockIdx.x - D.gat0, scalars, points);
+}
+
+// ---- the three points of the record, a lane per audit: commitment = Commit(B) (row 2a + 1 of the pass), combined_MAC = msm[2a],
+// combined_align = msm[2a + 1] + Commit(c) (align_MAC, Server.hpp:495-529; row 2a), to affine with ONE inversion, compressed
+__global__ void __launch_bounds__(64)
+k_ipa_audit_join(const XYZZ<Secp256k1Fp>* __restrict__ commit, uint32_t S, const XYZZ<Secp256k1Fp>* __restrict__ msm, uint32_t k,
+                 uint8_t* __restrict__ out) {
+    using M = Secp256k1Fp;
+    const uint32_t a = blockIdx.x * 64 + threadIdx.x;
+    if (a >= k) return;
+    XYZZ<M> p[3];
+    p[0] = load_xyzz<M>(commit + ((size_t)2 * a + 1) * S);
+    p[1] = load_xyzz<M>(msm + 2 * (size_t)a);
+    p[2] = load_xyzz<M>(msm + 2 * (size_t)a + 1);
+    {
+        const XYZZ<M> av = load_xyzz<M>(commit + (size_t)2 * a * S);
+        xyzz_add_cold<M>(&p[2], &av);
+    }
+    uint8_t* rec = out + (size_t)a * IPA_RECORD;
+    xyzz_each_affine_one_inv<Secp256k1G, 3>(p, [&](int i, bool live, const Fe<M>& x, const Fe<M>& y) {
+        store_compressed(rec + 33 * i, live, x.v, y.v);
+    });
+}
+
+// ---- per-device workspace: the work list (pinned staging + device copy), the combine's partials, the rows [c_k, B_k], the MSM
+// entries and sums, the prover's state and round rows.  One call at a time enqueues (mu); `fence` orders the buffers between calls on
+// different streams.
+struct IpaBatchWs {
+    std::mutex mu;
+    int device = -1;
+    Buf list, partial, rows2, msm_sc, msm_pt, msm_sums, state, rows;
+    PinnedList h_list;
+    UseFence fence;
+};
+static std::mutex g_ipa_mu;
+static std::vector<IpaBatchWs*> g_ipa_ws;
+
+static int ipa_workspace(IpaBatchWs** out) {
+    int dev = 0;
+    PORLA_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_ipa_mu);
+    for (auto* w : g_ipa_ws) if (w->device == dev) { *out = w; return PORLA_OK; }
+    IpaBatchWs* w = new IpaBatchWs();
+    w->device = dev;
+    g_ipa_ws.push_back(w);
+    *out = w;
+    return PORLA_OK;
+}
+
+// one commitment pass over n_rows contiguous rows of n_coeffs coefficients, sums left projective in the table's partials, and
+// `then(sums, S)` (row r at sums[r S]) enqueued under the table's lock before its fence is recorded again: the partials hold only the
+// LAST pass's sums, and another caller's pass may follow as soon as the lock is let go
+template <class Then>
+static int commit_then(FixedBase<Secp256k1G>& fb, const uint8_t* d_rows, size_t n_rows, size_t n_coeffs, hipStream_t stream, Then then) {
+    std::lock_guard<std::mutex> lk(fb.mu);
+    int rc;
+    if ((rc = fb.commit_device(d_rows, n_rows, n_coeffs, 32 * n_coeffs, nullptr, stream))) return rc;
+    if ((rc = then((const XYZZ<Secp256k1Fp>*)fb.partial, fb.last_S))) return rc;
+    return fb.fence.leave(stream);
+}
+
+static bool mul_ok(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
+
+// ws->mu held, ws->fence entered.  The k proofs of (a, b): a_src as k_ipa_open takes it, b from b_src or from a_values.
+static int prove_enqueue(IpaBatchWs* ws, FixedBase<Secp256k1G>& fb, size_t k, const uint8_t* a_src, size_t a_stride, const uint8_t* b_src,
+                         const uint8_t* a_values, uint8_t* proofs, size_t proof_stride, uint8_t* b_out, hipStream_t stream) {
+    int rc;
+    if ((rc = ws->state.ensure(k * ST_WORDS * 4))) return rc;
+    if ((rc = ws->rows.ensure(2 * k * IPA_ROW_COEFFS * 32))) return rc;
+    uint32_t* state = (uint32_t*)ws->state.p;
+    uint8_t* rows = (uint8_t*)ws->rows.p;
+    {
+        ProfScope ps("ipa_open", stream);
+        hipLaunchKernelGGL(k_ipa_open, dim3((unsigned)k), dim3(IPA_N), 0, stream, a_src, a_stride, b_src, a_values, state, proofs, proof_stride,
+                           b_out);
+        PORLA_HIP(hipGetLastError());
+    }
+    for (uint32_t r = 0, half = IPA_N / 2; r < IPA_ROUNDS; r++, half >>= 1) {
+        {
+            ProfScope ps("ipa_round_rows", stream);
+            hipLaunchKernelGGL(k_ipa_round_rows, dim3((unsigned)k), dim3(IPA_N), 0, stream, state, rows, half);
+            PORLA_HIP(hipGetLastError());
+        }
+        rc = commit_then(fb, rows, 2 * k, IPA_ROW_COEFFS, stream, [&](const XYZZ<Secp256k1Fp>* sums, uint32_t S) {
+            ProfScope ps("ipa_round_close", stream);
+            hipLaunchKernelGGL(k_ipa_round_close, dim3((unsigned)k), dim3(IPA_N), 0, stream, state, sums, S, proofs, proof_stride, r, half);
+            PORLA_HIP(hipGetLastError());
+            return (int)PORLA_OK;
+        });
+        if (rc) return rc;
+    }
+    return PORLA_OK;
+}
+
+static int audit_enqueue(IpaBatchWs* ws, FixedBase<Secp256k1G>& fb, const porla_ipa_audit_req* reqs, size_t k, uint8_t* d_out,
+                         uint8_t* d_b_out, hipStream_t stream) {
+    int rc;
+    const size_t n = IPA_N;
+    // ---- the plan, as the batched KZG audit's: combine blocks (the single call's rule over the batch's total rows), gather blocks,
+    // MSM offsets
+    uint64_t rows_total = 0;
+    for (size_t a = 0; a < k; a++) rows_total += reqs[a].n64 + reqs[a].n32;
+    const uint64_t spb = (uint64_t)AUDIT_BATCH_SLICES * 512;
+    uint64_t per_slice64 = (rows_total + spb - 1) / spb;
+    if (per_slice64 < 4) per_slice64 = 4;
+    if (per_slice64 > 0xffffffffull / AUDIT_BATCH_SLICES) per_slice64 = 0xffffffffull / AUDIT_BATCH_SLICES;
+    const uint32_t per_slice = (uint32_t)per_slice64, per_block = per_slice * AUDIT_BATCH_SLICES;
+    std::vector<KzgAuditDesc> desc(k);
+    std::vector<uint64_t> offsets(2 * k + 1);
+    uint64_t blocks = 0, gblocks = 0, pairs = 0;
+    for (size_t a = 0; a < k; a++) {
+        const porla_ipa_audit_req& R = reqs[a];
+        KzgAuditDesc& D = desc[a];
+        D.rows64 = (const uint8_t*)R.d_rows64; D.idx64 = R.d_idx64; D.coef64 = R.d_coef64;
+        D.rows32 = (const uint8_t*)R.d_rows32; D.idx32 = R.d_idx32; D.coef32 = R.d_coef32;
+        D.mac_store = (const uint8_t*)R.d_mac_store; D.align_store = (const uint8_t*)R.d_align_store;
+        D.mac_idx = R.d_mac_idx; D.mac_coef = R.d_mac_coef;
+        D.n64 = (uint32_t)R.n64; D.n32 = (uint32_t)R.n32; D.n_macs = (uint32_t)R.n_macs;
+        const uint64_t total = R.n64 + R.n32;
+        const uint64_t nb = total ? (total + per_block - 1) / per_block : 1;   // an empty challenge still writes B = 0
+        D.blk0 = (uint32_t)blocks; D.nblk = (uint32_t)nb;
+        D.gat0 = (uint32_t)gblocks;
+        D.z = 0;
+        D.pair0 = pairs;
+        blocks += nb;
+        gblocks += (R.n_macs + KZG_GATHER_PAIRS - 1) / KZG_GATHER_PAIRS;
+        offsets[2 * a] = pairs;
+        offsets[2 * a + 1] = pairs + R.n_macs;
+        pairs += 2 * (uint64_t)R.n_macs;
+    }
+    offsets[2 * k] = pairs;
+    if (blocks > 0xffffffffull || gblocks > 0xffffffffull) { set_last_error("porla: audit batch too large for one call"); return PORLA_ERR_ARG; }
+    size_t pt_b;
+    if (!mul_ok((size_t)pairs, 64, &pt_b)) { set_last_error("porla: audit batch byte size overflows"); return PORLA_ERR_ARG; }
+    const size_t sc_b = (size_t)pairs * 32, rows2_b = 2 * k * 32 * n;
+    const size_t part_b = audit_combine_partial_bytes((uint32_t)blocks, (uint32_t)n);
+    // ---- the work list: a_values | descriptors | combine block -> audit | gather block -> audit, one pinned buffer, one copy
+    const size_t av_b = 32 * k, desc_b = k * sizeof(KzgAuditDesc);
+    const size_t list_b = av_b + desc_b + 4 * (size_t)(blocks + gblocks);
+    if ((rc = ws->h_list.stage(list_b))) return rc;
+    {
+        uint8_t* h = (uint8_t*)ws->h_list.h;
+        for (size_t a = 0; a < k; a++) memcpy(h + 32 * a, reqs[a].a_value, 32);
+        memcpy(h + av_b, desc.data(), desc_b);
+        uint32_t* bl = (uint32_t*)(h + av_b + desc_b);
+        uint32_t* gl = bl + blocks;
+        for (size_t a = 0; a < k; a++) {
+            for (uint32_t b = 0; b < desc[a].nblk; b++) *bl++ = (uint32_t)a;
+            for (uint32_t b = 0; b < (desc[a].n_macs + KZG_GATHER_PAIRS - 1) / KZG_GATHER_PAIRS; b++) *gl++ = (uint32_t)a;
+        }
+    }
+    if ((rc = ws->list.ensure(list_b))) return rc;
+    if ((rc = ws->partial.ensure(part_b))) return rc;
+    if ((rc = ws->rows2.ensure(rows2_b))) return rc;
+    if ((rc = ws->msm_sc.ensure(sc_b + 64))) return rc;
+    if ((rc = ws->msm_pt.ensure(pt_b + 64))) return rc;
+    if ((rc = ws->msm_sums.ensure(2 * k * sizeof(XYZZ<Secp256k1Fp>)))) return rc;
+    if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
+    const uint8_t* d_av = (const uint8_t*)ws->list.p;
+    const KzgAuditDesc* d_desc = (const KzgAuditDesc*)(d_av + av_b);
+    const uint32_t* d_blk = (const uint32_t*)(d_av + av_b + desc_b);
+    const uint32_t* d_gat = d_blk + blocks;
+    uint8_t* rows2 = (uint8_t*)ws->rows2.p;
+    // ---- 1. the row combine: c_k (mod n) and B_k into the rows [c_k, B_k]
+    if ((rc = audit_combine_batch_launch(d_desc, d_blk, (uint32_t)blocks, (uint32_t)k, (uint32_t)n, per_slice, ws->partial.p, 1, rows2,
+                                         rows2 + 32 * n, 2 * 32 * n, stream)))
+        return rc;
+    // ---- 2. the MSM pairs: gather, then the batched MSM over the 2K entries, sums left projective
+    if (gblocks) {
+        ProfScope ps("ipa_audit_gather", stream);
+        hipLaunchKernelGGL(k_ipa_audit_gather, dim3((unsigned)gblocks), dim3(4 * KZG_GATHER_PAIRS), 0, stream, d_desc, d_gat,
+                           (uint8_t*)ws->msm_sc.p, (uint8_t*)ws->msm_pt.p);
+        PORLA_HIP(hipGetLastError());
+    }
+    XYZZ<Secp256k1Fp>* msm_sums = (XYZZ<Secp256k1Fp>*)ws->msm_sums.p;
+    if ((rc = msm_batch_sums_device<Secp256k1G>((const uint8_t*)ws->msm_sc.p, (const uint8_t*)ws->msm_pt.p, offsets.data(), 2 * k, msm_sums,
+                                                stream)))
+        return rc;
+    // ---- 3. the 2K Pedersen commitments and the record's points: the prover's first pass overwrites these sums
+    rc = commit_then(fb, rows2, 2 * k, n, stream, [&](const XYZZ<Secp256k1Fp>* sums, uint32_t S) {
+        ProfScope ps("ipa_audit_join", stream);
+        hipLaunchKernelGGL(k_ipa_audit_join, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, stream, sums, S, msm_sums, (uint32_t)k, d_out);
+        PORLA_HIP(hipGetLastError());
+        return (int)PORLA_OK;
+    });
+    if (rc) return rc;
+    // ---- 4. the proofs of (B_k, powers of a_value): B < p_icc < n, so the reduction mod n leaves it as it is
+    return prove_enqueue(ws, fb, k, rows2 + 32 * n, 2 * 32 * n, nullptr, d_av, d_out + 99, IPA_RECORD, d_b_out, stream);
+}
+
+}  // namespace porla
+
+using namespace porla;
+
+static_assert(sizeof(porla_ipa_audit_req) == PORLA_IPA_AUDIT_REQ_BYTES, "porla_ipa_audit_req size");
+static_assert(offsetof(porla_ipa_audit_req, d_rows64) == 0 && offsetof(porla_ipa_audit_req, d_idx64) == 8 &&
+              offsetof(porla_ipa_audit_req, d_coef64) == 16 && offsetof(porla_ipa_audit_req, n64) == 24 &&
+              offsetof(porla_ipa_audit_req, d_rows32) == 32 && offsetof(porla_ipa_audit_req, d_idx32) == 40 &&
+              offsetof(porla_ipa_audit_req, d_coef32) == 48 && offsetof(porla_ipa_audit_req, n32) == 56 &&
+              offsetof(porla_ipa_audit_req, d_mac_store) == 64 && offsetof(porla_ipa_audit_req, d_align_store) == 72 &&
+              offsetof(porla_ipa_audit_req, d_mac_idx) == 80 && offsetof(porla_ipa_audit_req, d_mac_coef) == 88 &&
+              offsetof(porla_ipa_audit_req, n_macs) == 96 && offsetof(porla_ipa_audit_req, a_value) == 104,
+              "porla_ipa_audit_req offsets (include/porla_gpu.h)");
+
+// the fixed base of an IPA batch call: secp256k1, the 128 generators and u.  (A handle exists only where a device does, so this comes
+// after ensure_device: without a device every non-NULL handle is refused as PORLA_ERR_NO_DEVICE before it is read.)
+static int ipa_check_base(const porla_fixed_base* fb, const char* who) {
+    if (fb->curve != 1 || fb->secp.n_points < IPA_ROW_COEFFS) {
+        set_last_error(std::string(who) + ": gens_u_fb must be a secp256k1 fixed base over generators[0..127] || u (129 points)");
+        return PORLA_ERR_ARG;
+    }
+    return PORLA_OK;
+}
+
+extern "C" int porla_ipa_audit_batch_device(porla_fixed_base* gens_u_fb, const porla_ipa_audit_req* reqs, size_t k, void* d_out,
+                                            void* d_b_out, void* hip_stream) {
+    static const char* who = "porla_ipa_audit_batch_device";
+    auto bad = [](const char* what) { set_last_error(std::string(who) + ": " + what); return PORLA_ERR_ARG; };
+    if (k && (!reqs || !d_out || !gens_u_fb)) return bad("reqs, d_out or gens_u_fb is NULL");
+    size_t out_b;
+    if (!mul_ok(k, IPA_RECORD, &out_b)) return bad("k records overflow a byte size");
+    uint64_t pairs = 0;
+    for (size_t a = 0; a < k; a++) {
+        const porla_ipa_audit_req& R = reqs[a];
+        if (R.n64 && (!R.d_rows64 || !R.d_idx64 || !R.d_coef64)) return bad("a NULL 64-byte-row array with n64 > 0");
+        if (R.n32 && (!R.d_rows32 || !R.d_idx32 || !R.d_coef32)) return bad("a NULL 32-byte-row array with n32 > 0");
+        if (R.n_macs && (!R.d_mac_store || !R.d_align_store || !R.d_mac_idx || !R.d_mac_coef)) return bad("a NULL MAC array with n_macs > 0");
+        if (R.n_macs > IPA_AUDIT_MAX_MACS) return bad("n_macs > 32768 (the batched MSM's entry limit; use porla_ipa_audit_device)");
+        if (R.n64 >= (1ull << 32) || R.n32 >= (1ull << 32) || R.n64 + R.n32 >= (1ull << 32)) return bad("n64 + n32 >= 2^32");
+        pairs += 2 * (uint64_t)R.n_macs;
+    }
+    size_t b;
+    if (!mul_ok(k, (size_t)ST_WORDS * 4 + 2 * IPA_ROW_COEFFS * 32 + 3 * 32 * IPA_N, &b) || !mul_ok((size_t)pairs, 96, &b))
+        return bad("the batch's byte size overflows");
+    if (k == 0) return PORLA_OK;
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = ipa_check_base(gens_u_fb, who))) return rc;
+    IpaBatchWs* ws = nullptr;
+    if ((rc = ipa_workspace(&ws))) return rc;
+    std::lock_guard<std::mutex> lk(ws->mu);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if ((rc = ws->fence.enter(stream))) return rc;
+    rc = audit_enqueue(ws, gens_u_fb->secp, reqs, k, (uint8_t*)d_out, (uint8_t*)d_b_out, stream);
+    // the buffers of this call are behind the fence on every exit, a failing one included
+    const int rf = ws->fence.leave(stream);
+    return rc ? rc : rf;
+}
+
+extern "C" int porla_ipa_prove_batch_device(porla_fixed_base* gens_u_fb, const void* d_a, const void* d_b, size_t k, void* d_proofs,
+                                            void* hip_stream) {
+    static const char* who = "porla_ipa_prove_batch_device";
+    auto bad = [](const char* what) { set_last_error(std::string(who) + ": " + what); return PORLA_ERR_ARG; };
+    if (k && (!gens_u_fb || !d_a || !d_b || !d_proofs)) return bad("gens_u_fb, d_a, d_b or d_proofs is NULL");
+    size_t b;
+    if (!mul_ok(k, (size_t)ST_WORDS * 4 + 2 * IPA_ROW_COEFFS * 32, &b)) return bad("k proofs overflow a byte size");
+    if (k > 0x7fffffffu) return bad("more than 2^31 - 1 proofs in one call");
+    if (k == 0) return PORLA_OK;
+    int rc = ensure_device();
+    if (rc) return rc;
+    if ((rc = ipa_check_base(gens_u_fb, who))) return rc;
+    IpaBatchWs* ws = nullptr;
+    if ((rc = ipa_workspace(&ws))) return rc;
+    std::lock_guard<std::mutex> lk(ws->mu);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if ((rc = ws->fence.enter(stream))) return rc;
+    rc = prove_enqueue(ws, gens_u_fb->secp, k, (const uint8_t*)d_a, 32 * IPA_N, (const uint8_t*)d_b, nullptr, (uint8_t*)d_proofs, IPA_PROOF,
+                       nullptr, stream);
+    const int rf = ws->fence.leave(stream);
+    return rc ? rc : rf;
+}

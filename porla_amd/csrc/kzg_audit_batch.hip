@@ -137,10 +137,7 @@ struct KzgAuditBatchWs {
     std::mutex mu;
     int device = -1;
     Buf list, partial, rows3, msm_sc, msm_pt, msm_sums;
-    void* h_list = nullptr;
-    size_t h_list_cap = 0;
-    hipEvent_t upload = nullptr;                                  // recorded after the last upload from h_list
-    std::vector<std::pair<void*, hipEvent_t>> retired;           // staging buffers whose upload was still queued when a call came
+    PinnedList h_list;
     UseFence fence;
 };
 static std::mutex g_kab_mu;
@@ -152,38 +149,6 @@ static int launch_join(const XYZZ<Bn254Fp>* sums, uint32_t S, void* ctx) {
     ProfScope ps("kzg_audit_join", j->stream);
     hipLaunchKernelGGL(k_kzg_audit_join, dim3((j->k + 63) / 64), dim3(64), 0, j->stream, sums, S, j->msm, j->k, j->out);
     PORLA_HIP(hipGetLastError());
-    return PORLA_OK;
-}
-
-// ws->mu held; a pinned buffer of at least `bytes` whose previous upload is done (a buffer still being uploaded from is retired and
-// freed by a later call, so that no call waits for earlier work)
-static int stage_list(KzgAuditBatchWs* ws, size_t bytes) {
-    for (size_t i = 0; i < ws->retired.size();) {
-        const hipError_t q = hipEventQuery(ws->retired[i].second);
-        if (q == hipErrorNotReady) { i++; continue; }
-        PORLA_HIP(q);
-        PORLA_HIP(hipHostFree(ws->retired[i].first));
-        PORLA_HIP(hipEventDestroy(ws->retired[i].second));
-        ws->retired.erase(ws->retired.begin() + (long)i);
-    }
-    if (ws->upload) {
-        const hipError_t q = hipEventQuery(ws->upload);
-        if (q == hipErrorNotReady) {
-            ws->retired.emplace_back(ws->h_list, ws->upload);
-            ws->h_list = nullptr;
-            ws->h_list_cap = 0;
-            ws->upload = nullptr;
-        } else {
-            PORLA_HIP(q);
-        }
-    }
-    if (ws->h_list_cap < bytes) {
-        if (ws->h_list) PORLA_HIP(hipHostFree(ws->h_list));
-        ws->h_list = nullptr;
-        ws->h_list_cap = 0;
-        PORLA_HIP(hipHostMalloc(&ws->h_list, bytes + bytes / 4 + 4096, hipHostMallocDefault));
-        ws->h_list_cap = bytes + bytes / 4 + 4096;
-    }
     return PORLA_OK;
 }
 
@@ -235,9 +200,9 @@ static int audit_batch_enqueue(KzgAuditBatchWs* ws, const porla_kzg_audit_req* r
     // ---- the work list: descriptors | combine block -> audit | gather block -> audit, one pinned buffer, one copy
     const size_t desc_b = k * sizeof(KzgAuditDesc);
     const size_t list_b = desc_b + 4 * (size_t)(blocks + gblocks);
-    if ((rc = stage_list(ws, list_b))) return rc;
+    if ((rc = ws->h_list.stage(list_b))) return rc;
     {
-        uint8_t* h = (uint8_t*)ws->h_list;
+        uint8_t* h = (uint8_t*)ws->h_list.h;
         memcpy(h, desc.data(), desc_b);
         uint32_t* bl = (uint32_t*)(h + desc_b);
         uint32_t* gl = bl + blocks;
@@ -253,15 +218,14 @@ static int audit_batch_enqueue(KzgAuditBatchWs* ws, const porla_kzg_audit_req* r
     if ((rc = ws->msm_pt.ensure(pt_b + 64))) return rc;
     if ((rc = ws->msm_sums.ensure(2 * k * sizeof(XYZZ<Bn254Fp>)))) return rc;
     if ((rc = ws->fence.enter(stream))) return rc;
-    PORLA_HIP(hipMemcpyAsync(ws->list.p, ws->h_list, list_b, hipMemcpyHostToDevice, stream));
-    if (!ws->upload) PORLA_HIP(hipEventCreateWithFlags(&ws->upload, hipEventDisableTiming));
-    PORLA_HIP(hipEventRecord(ws->upload, stream));
+    if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
     const KzgAuditDesc* d_desc = (const KzgAuditDesc*)ws->list.p;
     const uint32_t* d_blk = (const uint32_t*)((const uint8_t*)ws->list.p + desc_b);
     const uint32_t* d_gat = d_blk + blocks;
     uint8_t* rows3 = (uint8_t*)ws->rows3.p;
     // ---- 1. the row combine: c_k and B_k into the commit rows
-    if ((rc = audit_combine_batch_launch(d_desc, d_blk, (uint32_t)blocks, (uint32_t)k, (uint32_t)n, per_slice, ws->partial.p, rows3, stream)))
+    if ((rc = audit_combine_batch_launch(d_desc, d_blk, (uint32_t)blocks, (uint32_t)k, (uint32_t)n, per_slice, ws->partial.p, 0, rows3,
+                                         rows3 + 32 * n, 3 * 32 * n, stream)))
         return rc;
     // ---- 2. the opening: h_k, point, claim (and B into d_b_out)
     {

@@ -1,6 +1,5 @@
-// Device pieces the batched KZG audit (kzg_audit_batch.hip) and the batched verifier (kzg_verify_batch.hip) share: the gather of
-// challenged store entries into batched-MSM pairs, and the conversion of a lane's projective points to big-endian affine with one
-// inversion.
+// Device pieces the batched audits (kzg_audit_batch.hip, ipa_audit_batch.hip) and the batched verifier (kzg_verify_batch.hip) share: the gather of
+// challenged store entries into batched-MSM pairs, and the conversion of a lane's projective points to affine with one inversion.
 #pragma once
 #include "fixed_base.hip.h"
 
@@ -28,10 +27,10 @@ __device__ __forceinline__ void kzg_gather_pairs(const uint8_t* store_a, const u
     }
 }
 
-// N projective points to 64-byte big-endian affine at base + at[j] (64 zero bytes = infinity) with ONE inversion: Montgomery's
-// trick over their ZZZ, as k_fb_finish does for a lane's rows
-template <class C, int N>
-__device__ __forceinline__ void xyzz_to_be_one_inv(const XYZZ<typename C::Fp> (&p)[N], uint8_t* base, const uint32_t (&at)[N]) {
+// N projective points to affine with ONE inversion: Montgomery's trick over their ZZZ, as k_fb_finish does for a lane's rows.
+// emit(j, live, x, y) for j = N - 1 .. 0: the plain (non-Montgomery) coordinates of point j, or live = false for infinity
+template <class C, int N, class Emit>
+__device__ __forceinline__ void xyzz_each_affine_one_inv(const XYZZ<typename C::Fp> (&p)[N], Emit emit) {
     using M = typename C::Fp;
     Fe<M> zzz[N], pre[N];
     bool live[N];
@@ -52,18 +51,31 @@ __device__ __forceinline__ void xyzz_to_be_one_inv(const XYZZ<typename C::Fp> (&
     for (int j = N - 1; j >= 0; j--) {
         const Fe<M> inv_j = fe_mul_call<M>(inv, pre[j]);
         inv = fe_mul_call<M>(inv, zzz[j]);
-        uint8_t* dst = base + at[j];
         if (!live[j]) {
-            const uint4 z = make_uint4(0, 0, 0, 0);
-            uint4* q = reinterpret_cast<uint4*>(dst);
-            q[0] = z; q[1] = z; q[2] = z; q[3] = z;
+            emit(j, false, one, one);
             continue;
         }
         const Affine<M> af = xyzz_to_affine_with_inv<M>(p[j], inv_j);
         const Fe<M> x = fe_mul_call<M>(af.x, one), y = fe_mul_call<M>(af.y, one);   // out of Montgomery form
+        emit(j, true, x, y);
+    }
+}
+
+// ... to 64-byte big-endian affine at base + at[j] (64 zero bytes = infinity)
+template <class C, int N>
+__device__ __forceinline__ void xyzz_to_be_one_inv(const XYZZ<typename C::Fp> (&p)[N], uint8_t* base, const uint32_t (&at)[N]) {
+    using M = typename C::Fp;
+    xyzz_each_affine_one_inv<C, N>(p, [&](int j, bool live, const Fe<M>& x, const Fe<M>& y) {
+        uint8_t* dst = base + at[j];
+        if (!live) {
+            const uint4 z = make_uint4(0, 0, 0, 0);
+            uint4* q = reinterpret_cast<uint4*>(dst);
+            q[0] = z; q[1] = z; q[2] = z; q[3] = z;
+            return;
+        }
         store_be256(dst, x.v);
         store_be256(dst + 32, y.v);
-    }
+    });
 }
 
 }  // namespace porla

@@ -15,6 +15,7 @@ template int msm_pair_host<Secp256k1G>(const uint8_t*, const uint8_t*, const uin
 template int msm_device_begin<Secp256k1G>(int, const uint8_t*, const uint8_t*, size_t, hipStream_t);
 template int msm_device_end<Secp256k1G>(int, XYZZ<Secp256k1Fp>*);
 template int msm_batch_device<Secp256k1G>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint8_t*, hipStream_t);
+template int msm_batch_sums_device<Secp256k1G>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, XYZZ<Secp256k1Fp>*, hipStream_t);
 template int msm_batch_host<Secp256k1G>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint8_t*);
 template struct FixedBase<Secp256k1G>;
 }  // namespace porla

@@ -21,6 +21,11 @@ class KzgAuditReq(ctypes.Structure):
                 ("d_mac_coef", ctypes.c_void_p), ("n_macs", ctypes.c_size_t), ("random_point", ctypes.c_ulonglong)]
 
 
+class IpaAuditReq(ctypes.Structure):
+    """porla_ipa_audit_req, include/porla_gpu.h: one audit of porla_ipa_audit_batch_device (PORLA_IPA_AUDIT_REQ_BYTES = 136)."""
+    _fields_ = KzgAuditReq._fields_[:13] + [("a_value", ctypes.c_uint8 * 32)]
+
+
 class KzgVerifyReq(ctypes.Structure):
     """porla_kzg_verify_req, include/porla_gpu.h: one reply of porla_kzg_verify_batch_device (PORLA_KZG_VERIFY_REQ_BYTES = 64)."""
     _fields_ = [("d_comp_store", ctypes.c_void_p), ("d_idx", ctypes.c_void_p), ("d_coef", ctypes.c_void_p), ("n", ctypes.c_size_t),
@@ -131,6 +136,9 @@ def _declare(L):
     L.porla_kzg_audit_device.restype = ctypes.c_int
     L.porla_kzg_audit_batch_device.argtypes = [ctypes.POINTER(KzgAuditReq), sz, vp, vp, vp]
     L.porla_kzg_audit_batch_device.restype = ctypes.c_int
+    L.porla_ipa_audit_batch_device.argtypes = [vp, ctypes.POINTER(IpaAuditReq), sz, vp, vp, vp]
+    L.porla_ipa_audit_batch_device.restype = ctypes.c_int
+    L.porla_ipa_prove_batch_device.argtypes = [vp, vp, vp, sz, vp, vp]; L.porla_ipa_prove_batch_device.restype = ctypes.c_int
     L.porla_kzg_verify_batch_device.argtypes = [ctypes.POINTER(KzgVerifyReq), sz, vp, u8p, u8p, vp]
     L.porla_kzg_verify_batch_device.restype = ctypes.c_int
     L.porla_kzg_digest_batch_device.argtypes = [vp, sz, vp, vp]; L.porla_kzg_digest_batch_device.restype = ctypes.c_int

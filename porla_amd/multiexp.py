@@ -10,7 +10,7 @@ Server.hpp:183-188,365-397,550-558).  Buffers are Python bytes/bytearray; result
 """
 import ctypes
 
-from .loader import GoSlice, KzgAuditReq, KzgVerifyReq, lib
+from .loader import GoSlice, IpaAuditReq, KzgAuditReq, KzgVerifyReq, lib
 
 MAC_SIZE = 64       # COMMITMENT_MAC_SIZE with ENABLE_KZG, config.hpp:26
 SCALAR_SIZE = 32    # bn254_scalar = uint32_t[8], utils.h:64
@@ -341,6 +341,21 @@ class FixedBase:
                                           vp(d_align_store), vp(d_mac_idx), vp(d_mac_coef), n_macs, *o, vp(stream)))
         return dict(zip(("combined_mac", "combined_align", "align_value", "commitment", "b"), (x.raw for x in o)))
 
+    def ipa_audit_batch_device(self, audits, d_out, d_b=None, stream=0):
+        """Server::audit (IPA) of len(audits) independent audits, proofs included, in ONE asynchronous call on `stream`
+        (porla_ipa_audit_batch_device); self = the fixed base over generators[0..127] || u.  Record k (655 bytes at d_out + 655 k) =
+        commitment(33) | combined_MAC(33) | combined_align(33) | proof(556); d_b (optional): B mod p_icc of every audit, 128 x 32 bytes
+        each.  `audits`: tuples as ipa_audit_requests takes."""
+        arr = ipa_audit_requests(audits)
+        _check(lib.porla_ipa_audit_batch_device(self.h, arr, len(audits), ctypes.c_void_p(d_out), ctypes.c_void_p(d_b or None),
+                                                ctypes.c_void_p(stream)))
+
+    def ipa_prove_batch_device(self, d_a, d_b, k, d_proofs, stream=0):
+        """k proofs of Server::inner_product_prove(a, b) in ONE asynchronous call (porla_ipa_prove_batch_device): d_a, d_b = k x 128 x
+        32 bytes big-endian, d_proofs = k x 556 bytes"""
+        _check(lib.porla_ipa_prove_batch_device(self.h, ctypes.c_void_p(d_a), ctypes.c_void_p(d_b), k, ctypes.c_void_p(d_proofs),
+                                                ctypes.c_void_p(stream)))
+
     def close(self):
         if self.h:
             lib.porla_fixed_base_destroy(self.h)
@@ -432,6 +447,39 @@ def split_audit_records(raw, k):
         r = raw[KZG_AUDIT_RECORD_BYTES * i:KZG_AUDIT_RECORD_BYTES * (i + 1)]
         out.append(dict(commitment=r[0:64], proof_h=r[64:128], point=r[128:160], claim=r[160:192], combined_mac=r[192:256],
                         combined_align=r[256:320]))
+    return out
+
+
+IPA_AUDIT_RECORD_BYTES = 655   # commitment(33) | combined_mac(33) | combined_align(33) | proof(556) (include/porla_gpu.h)
+IPA_PROOF_BYTES = 556          # c(32) | 6 x (L(33) | R(33)) | a0 b0 a1 b1 (4 x 32)
+
+
+def ipa_audit_requests(audits):
+    """a ctypes array of porla_ipa_audit_req from per-audit tuples: the first 13 fields as kzg_audit_requests takes them, then a_value
+    (audit_values[n_points]) as an integer or as big-endian bytes of at most 32 (left-padded)"""
+    arr = (IpaAuditReq * max(len(audits), 1))()
+    for i, a in enumerate(audits):
+        if len(a) != 14:
+            raise ValueError("ipa_audit_batch_device: audit %d has %d fields, want 14" % (i, len(a)))
+        v = a[13].to_bytes(32, "big") if isinstance(a[13], int) else bytes(a[13]).rjust(32, b"\0")
+        if len(v) != 32:
+            raise ValueError("ipa_audit_batch_device: audit %d: a_value longer than 32 bytes" % i)
+        arr[i] = IpaAuditReq(*[(x or None) if j in _REQ_POINTERS else x for j, x in enumerate(a[:13])], (ctypes.c_uint8 * 32)(*v))
+    return arr
+
+
+def split_ipa_records(raw, k):
+    """k records of porla_ipa_audit_batch_device -> list of dicts: the three compressed points and the proof, and the proof's parts
+    (c, a0, b0, a1, b1 as integers; rounds: six (L, R) pairs of 33 bytes)"""
+    out = []
+    le = lambda b: int.from_bytes(b, "little")
+    for i in range(k):
+        r = raw[IPA_AUDIT_RECORD_BYTES * i:IPA_AUDIT_RECORD_BYTES * (i + 1)]
+        p = r[99:]
+        tail = p[32 + 6 * 66:]
+        out.append(dict(commitment=r[0:33], combined_mac=r[33:66], combined_align=r[66:99], proof=p, c=le(p[:32]),
+                        rounds=[(p[32 + 66 * j:65 + 66 * j], p[65 + 66 * j:98 + 66 * j]) for j in range(6)],
+                        a0=le(tail[0:32]), b0=le(tail[32:64]), a1=le(tail[64:96]), b1=le(tail[96:128])))
     return out
 
 
