@@ -19,7 +19,7 @@
 //                       field form of fe30.hip.h / ec30.hip.h (k_bucket_sum: the same on 8 x 32-bit limbs, kept for curves
 //                       without that form)
 //   k_bucket_combine    wave per multi-item bucket: folds that bucket's item sums (no-op for uniform scalars)
-//   k_tree_level(_quad), k_tree_tail   per window sum_b (b+1)*B_b as a bit-sliced tree: S (plain sum) and M_k (sum of the
+//   k_tree_front2, k_tree_level(_quad), k_tree_tail   per window sum_b (b+1)*B_b as a bit-sliced tree: S (plain sum) and M_k (sum of the
 //                       buckets with index bit k set) per node, log2(B) levels of independent additions; small levels run
 //                       each addition on the four lanes of a quad, the last levels in one block per window
 //   host                one Horner pass over the W*c single-bit terms (host_fold64.hpp), affine normalisation, marshal
@@ -857,6 +857,35 @@ k_tree_level_quad(TreeLevelArgs<typename C::Fp> a) {
     if (!live) t = total - 1;                         // padding quads compute a valid task and store nothing
     const uint32_t i = t % a.n;
     tree_task_quad<C>(a, t / a.n, i, i, i, live, threadIdx.x & 63u);
+}
+
+// Levels 0 and 1 in one launch: lane i takes the four buckets B[4i .. 4i+3] and forms
+//   S^0[2i] = B[4i] + B[4i+1],  M_0^1[i] = B[4i+1] + B[4i+3],  S^0[2i+1] = B[4i+2] + B[4i+3],  S^1[i] = S^0[2i] + S^0[2i+1]
+// -- the four additions k_tree_level makes for them at l = 0 and l = 1 -- and stores what later levels read, where they read it:
+// S^0[2i+1] (level 2 takes the odd S^0 entries through s_prev2), M_0^1[i] and S^1[i].  S^0[2i] has no reader but level 1 (tree_op:
+// s_prev is read at level l + 1 only, s_prev2 at odd entries only) and stays in registers.  Four node loads and three stores per
+// group instead of eight and four, one launch and one dependent pass less.  The additions run in this order so that at most
+// three nodes are live (keep, x, y); ONE inlined addition in a loop the compiler must not unroll (an addition is ~2 900
+// instructions).  a.s_prev = the buckets, a.s_out = S^0, a.n = groups; s1_out = S^1, a.m_out = slot 0 of M^1.
+template <class C>
+__global__ void __launch_bounds__(256)
+k_tree_front2(TreeLevelArgs<typename C::Fp> a, XYZZ<typename C::Fp>* __restrict__ s1_out) {
+    using M = typename C::Fp;
+    using N = Node<C>;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const XYZZ<M>* bk = a.s_prev + 4 * (size_t)i;
+    typename N::T x = N::inf(), y = N::inf(), keep = N::inf();
+#pragma unroll 1
+    for (uint32_t s = 0; s < 4; s++) {
+        if (s == 0) { x = N::load(bk); y = N::load(bk + 1); }
+        else if (s == 1) { x = y; y = N::load(bk + 3); }
+        else if (s == 2) { x = N::load(bk + 2); }
+        else { y = x; x = keep; }
+        N::add(x, y);
+        if (s == 0) keep = x;
+        else N::store(s == 1 ? a.m_out + i : (s == 2 ? a.s_out + 2 * (size_t)i + 1 : s1_out + i), x);
+    }
 }
 
 // the last levels l0 .. nlev-1 of ONE window per block (few nodes are left: launch gaps would dominate).  The levels

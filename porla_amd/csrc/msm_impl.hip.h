@@ -435,7 +435,22 @@ static int msm_tree_launch(Workspace* ws, const XYZZ<typename C::Fp>* buckets, i
         const uint32_t l0 = tree_tail_start(B, nlev, quad);
         {
             ProfScope ps("tree_levels", st);
-            for (uint32_t l = 0; l < l0; l++) {
+            uint32_t l_first = 0;
+            // levels 0 and 1 as one launch (k_tree_front2) where both are full-width levels and another MSM is in flight: the chip
+            // time the tree takes from that MSM's accumulation is what counts there, not the tree's depth
+            if (!ws->lone && l0 >= 2 && (nbp & 3) == 0 && nbp / 2 > (size_t)TREE_QUAD_MAX_TASKS) {
+                TreeLevelArgs<M> a;
+                a.s_prev = bk; a.s_prev2 = bk; a.m_prev = m_half[0];
+                a.s_out = s_level(0);
+                a.m_out = m_half[1];                          // M^1, slot 0
+                a.fin = nullptr;
+                a.n = (uint32_t)(nbp >> 2);
+                a.m_prev_stride = 0; a.m_out_stride = a.n;
+                a.l = 1; a.nlev = nlev; a.last = 0;
+                hipLaunchKernelGGL((k_tree_front2<C>), dim3((a.n + 255) / 256), dim3(256), 0, st, a, s_level(1));
+                l_first = 2;
+            }
+            for (uint32_t l = l_first; l < l0; l++) {
                 TreeLevelArgs<M> a;
                 a.s_prev = l ? s_level(l - 1) : bk;
                 a.s_prev2 = l >= 2 ? s_level(l - 2) : bk;
