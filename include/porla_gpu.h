@@ -361,6 +361,54 @@ int  porla_ipa_audit_batch_device(porla_fixed_base *gens_u_fb, const porla_ipa_a
  * (B_k, powers of a_value). */
 int  porla_ipa_prove_batch_device(porla_fixed_base *gens_u_fb, const void *d_a, const void *d_b, size_t k, void *d_proofs,
                                   void *hip_stream);
+/* Client::audit's check (IPA build, Client.hpp:633-880) of K replies in ONE asynchronous call: reply k is record k of d_records
+ * (PORLA_IPA_AUDIT_RECORD_BYTES each, the layout porla_ipa_audit_batch_device writes: commitment C (33) | combined_MAC M (33) |
+ * combined_align A (33) | proof (556)), reqs[k] the client's side of that audit: the level's MAC complements d_comp_store (64-byte
+ * big-endian affine secp256k1 points, zeros = infinity, indexed like the server's MAC store), the challenge (d_idx, d_coef, n: the
+ * arrays the server's MAC MSM used), the client's alpha (32 bytes big-endian, taken mod n; the reference's is 128 bits) and a_value
+ * as in porla_ipa_audit_req.  gens_u_fb: the fixed base porla_ipa_audit_batch_device takes.  d_status[k], ON THE DEVICE, receives
+ *   PORLA_IPA_VERIFY_FULL       alpha C + sum_j coef_j comp[idx_j] == M + alpha A                     (Client.hpp:801-829)
+ *   PORLA_IPA_VERIFY_PROOF      Client::inner_product_verify's final ge_equals_ge holds              (Client.hpp:1465-1628)
+ *   PORLA_IPA_VERIFY_BVEC       b_i == sum_(j = i mod 2) a_value^(2^j) x_values[j] (mod n) for i = 0, 1, x_values the verifier's own
+ *                               array after the six rounds: the proof's b0, b1 are the fold of the audit's b = (v, v^2, v^4, ...)
+ *   PORLA_IPA_VERIFY_MALFORMED  one of the record's 3 + 12 compressed points breaks secp256k1_eckey_pubkey_parse's rules (first byte
+ *                               2 or 3, X < p, X^3 + 7 a square) and is not the 33 zero bytes this library writes for infinity; the
+ *                               other bits are then clear, and nothing is computed on the record
+ * The reference's verdict is FULL | PROOF.  BVEC is an extension: inner_product_verify takes b0, b1 on trust, so a proof made for ANY
+ * vector b passes it (porla_ipa_prove_batch_device with an arbitrary d_b makes such proofs); a client that wants the proof bound to
+ * its challenge asks for FULL | PROOF | BVEC.  BVEC changes neither of the other two bits.  The proof's scalars (c, a0, b0, a1, b1)
+ * are any 32 little-endian bytes, reduced mod n.  A challenge that is 0 mod n (probability 2^-256; NTL raises an error there) has no
+ * inverse: the six inverses come from one inversion of the challenges' product, so all six are then taken as 0, and the equation
+ * decides.
+ * Exact per reply: no random folding, no fallback, no pairing.  Each MAC check is a pair of batched-MSM entries that sum to infinity
+ * iff it holds (the complements, then (alpha, C), (n - alpha, A), (n - 1, M)); each proof check is the 13-pair entry (1, C),
+ * (x_r^2, L_r), (x_r^-2, R_r) minus one row of 129 coefficients (a_(j & 1) x_values[j]; a0 b0 + a1 b1 - c for u) on gens_u_fb.
+ * Asynchronous: enqueued on hip_stream, returns without waiting on the host; the work waits for whatever the caller had enqueued on
+ * hip_stream before the call (d_records can come straight from porla_ipa_audit_batch_device on the same stream); d_status is
+ * complete when hip_stream is.  No internal side stream.
+ * PORLA_ERR_ARG (message in porla_gpu_last_error), checked before the device is touched: reqs, d_records, d_status or gens_u_fb NULL
+ * while k > 0; a NULL array whose count n is > 0; n > 32 768 (the batched MSM's entry limit); a byte size that overflows.  k = 0
+ * returns 0 and writes nothing.  There is no cap on k.  Valid arguments without a device: PORLA_ERR_NO_DEVICE; then a base with fewer
+ * than 129 points or on BN254: PORLA_ERR_ARG.
+ * One fixed sequence of launches per call, whatever K: the work-list upload, k_ipa_verify_prep (a block per reply: the transcript's
+ * six challenges, ONE inversion mod n, x_values, the row, the 3-pair and 13-pair entries, the fifteen decompressions, BVEC),
+ * k_ipa_verify_gather (the complement entries), the batched MSM over the 3K entries, ONE commitment pass over the K rows and
+ * k_ipa_verify_join (a lane per reply: both sums against infinity, the status byte).  Not yet measured on an MI355X
+ * (tools/bench_ipa_verify_batch.py; DESIGN.md section 4 has what is expected).  Calls from several threads on several
+ * streams, and beside porla_ipa_audit_batch_device and the fixed base's other users, are safe. */
+#define PORLA_IPA_VERIFY_REQ_BYTES 96      /* sizeof(porla_ipa_verify_req) on LP64; the library static_asserts it and each offset */
+#define PORLA_IPA_VERIFY_FULL      1
+#define PORLA_IPA_VERIFY_PROOF     2
+#define PORLA_IPA_VERIFY_MALFORMED 4
+#define PORLA_IPA_VERIFY_BVEC      8
+typedef struct {
+    const void *d_comp_store;                                  /* 0 */
+    const uint64_t *d_idx; const uint32_t *d_coef; size_t n;   /* 8, 16, 24 */
+    uint8_t alpha[32];                                         /* 32 */
+    uint8_t a_value[32];                                       /* 64 */
+} porla_ipa_verify_req;
+int  porla_ipa_verify_batch_device(porla_fixed_base *gens_u_fb, const porla_ipa_verify_req *reqs, size_t k, const void *d_records,
+                                   uint8_t *d_status, void *hip_stream);
 /* Client::audit's check (KZG build, Client.hpp:633-880) of K replies in ONE call: reply k is the 320-byte record k of d_records
  * (the layout porla_kzg_audit_batch_device writes: commitment C | proof_h H | point z | claim y | combined_mac M | combined_align A),
  * reqs[k] the client's side of that audit: the level's MAC complements d_comp_store (64-byte big-endian affine points, as

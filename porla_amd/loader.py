@@ -32,6 +32,11 @@ class KzgVerifyReq(ctypes.Structure):
                 ("alpha", ctypes.c_uint8 * 32)]
 
 
+class IpaVerifyReq(ctypes.Structure):
+    """porla_ipa_verify_req, include/porla_gpu.h: one reply of porla_ipa_verify_batch_device (PORLA_IPA_VERIFY_REQ_BYTES = 96)."""
+    _fields_ = KzgVerifyReq._fields_ + [("a_value", ctypes.c_uint8 * 32)]
+
+
 def load():
     """Load the engine.  When torch is importable it is imported FIRST so that the HIP runtime the process
     ends up with is the one torch ships (both have soname libamdhip64.so.7; two runtimes in one process
@@ -139,6 +144,8 @@ def _declare(L):
     L.porla_ipa_audit_batch_device.argtypes = [vp, ctypes.POINTER(IpaAuditReq), sz, vp, vp, vp]
     L.porla_ipa_audit_batch_device.restype = ctypes.c_int
     L.porla_ipa_prove_batch_device.argtypes = [vp, vp, vp, sz, vp, vp]; L.porla_ipa_prove_batch_device.restype = ctypes.c_int
+    L.porla_ipa_verify_batch_device.argtypes = [vp, ctypes.POINTER(IpaVerifyReq), sz, vp, vp, vp]
+    L.porla_ipa_verify_batch_device.restype = ctypes.c_int
     L.porla_kzg_verify_batch_device.argtypes = [ctypes.POINTER(KzgVerifyReq), sz, vp, u8p, u8p, vp]
     L.porla_kzg_verify_batch_device.restype = ctypes.c_int
     L.porla_kzg_digest_batch_device.argtypes = [vp, sz, vp, vp]; L.porla_kzg_digest_batch_device.restype = ctypes.c_int

@@ -10,7 +10,7 @@ Server.hpp:183-188,365-397,550-558).  Buffers are Python bytes/bytearray; result
 """
 import ctypes
 
-from .loader import GoSlice, IpaAuditReq, KzgAuditReq, KzgVerifyReq, lib
+from .loader import GoSlice, IpaAuditReq, IpaVerifyReq, KzgAuditReq, KzgVerifyReq, lib
 
 MAC_SIZE = 64       # COMMITMENT_MAC_SIZE with ENABLE_KZG, config.hpp:26
 SCALAR_SIZE = 32    # bn254_scalar = uint32_t[8], utils.h:64
@@ -356,6 +356,31 @@ class FixedBase:
         _check(lib.porla_ipa_prove_batch_device(self.h, ctypes.c_void_p(d_a), ctypes.c_void_p(d_b), k, ctypes.c_void_p(d_proofs),
                                                 ctypes.c_void_p(stream)))
 
+    def ipa_verify_batch_device(self, verifs, d_records, d_status=None, stream=0):
+        """Client::audit's check (IPA) of len(verifs) replies in ONE asynchronous call on `stream` (porla_ipa_verify_batch_device);
+        self = the fixed base over generators[0..127] || u.  Reply k is the 655-byte record at d_records + 655 k (as
+        ipa_audit_batch_device writes it), verifs[k] the client's side as ipa_verify_requests takes it.  The status bytes go to
+        d_status (a device address, len(verifs) bytes, complete when `stream` is).  d_status=None: a status buffer is allocated, the
+        stream synchronised and the bytes returned as a list of ints; reply k passes the reference's checks iff status[k] &
+        IPA_VERIFY_PASS == IPA_VERIFY_PASS, and is bound to its challenge as well iff status[k] == IPA_VERIFY_PASS_BOUND."""
+        k = len(verifs)
+        arr = ipa_verify_requests(verifs)
+        if d_status is not None:
+            _check(lib.porla_ipa_verify_batch_device(self.h, arr, k, ctypes.c_void_p(d_records or None), ctypes.c_void_p(d_status),
+                                                     ctypes.c_void_p(stream)))
+            return None
+        if k == 0:
+            _check(lib.porla_ipa_verify_batch_device(self.h, arr, 0, ctypes.c_void_p(d_records or None), None, ctypes.c_void_p(stream)))
+            return []
+        import torch
+        s = torch.cuda.ExternalStream(stream) if stream else torch.cuda.default_stream()
+        with torch.cuda.stream(s):
+            st = torch.zeros(k, dtype=torch.uint8, device="cuda")
+        _check(lib.porla_ipa_verify_batch_device(self.h, arr, k, ctypes.c_void_p(d_records or None), ctypes.c_void_p(st.data_ptr()),
+                                                 ctypes.c_void_p(stream)))
+        s.synchronize()
+        return list(bytes(st.cpu().numpy()))
+
     def close(self):
         if self.h:
             lib.porla_fixed_base_destroy(self.h)
@@ -481,6 +506,34 @@ def split_ipa_records(raw, k):
                         rounds=[(p[32 + 66 * j:65 + 66 * j], p[65 + 66 * j:98 + 66 * j]) for j in range(6)],
                         a0=le(tail[0:32]), b0=le(tail[32:64]), a1=le(tail[64:96]), b1=le(tail[96:128])))
     return out
+
+
+IPA_VERIFY_FULL = 1         # alpha C + sum coef comp == M + alpha A (Client.hpp:801-829)
+IPA_VERIFY_PROOF = 2        # Client::inner_product_verify's equation holds
+IPA_VERIFY_MALFORMED = 4    # a compressed point of the record does not parse
+IPA_VERIFY_BVEC = 8         # the proof's b0, b1 are the fold of b = (v, v^2, v^4, ...), v = a_value
+IPA_VERIFY_PASS = IPA_VERIFY_FULL | IPA_VERIFY_PROOF                 # the reference's verdict
+IPA_VERIFY_PASS_BOUND = IPA_VERIFY_PASS | IPA_VERIFY_BVEC            # ... with the proof bound to the challenge
+
+
+def _be32(v, what, i):
+    b = v.to_bytes(32, "big") if isinstance(v, int) else bytes(v)
+    if len(b) > 32:
+        raise ValueError("ipa_verify_batch_device: %s of reply %d is longer than 32 bytes" % (what, i))
+    return (ctypes.c_uint8 * 32)(*b.rjust(32, b"\0"))
+
+
+def ipa_verify_requests(verifs):
+    """a ctypes array of porla_ipa_verify_req from per-reply tuples (d_comp_store, d_idx, d_coef, n, alpha, a_value): device pointers
+    (0 -> NULL), the challenge length, and the client's alpha and the audit's a_value as integers or big-endian bytes of at most 32
+    (left-padded)"""
+    arr = (IpaVerifyReq * max(len(verifs), 1))()
+    for i, v in enumerate(verifs):
+        if len(v) != 6:
+            raise ValueError("ipa_verify_batch_device: reply %d has %d fields, want 6" % (i, len(v)))
+        comp, idx, coef, n, alpha, a_value = v
+        arr[i] = IpaVerifyReq(comp or None, idx or None, coef or None, n, _be32(alpha, "alpha", i), _be32(a_value, "a_value", i))
+    return arr
 
 
 KZG_VERIFY_FULL = 1        # alpha C + sum coef comp == M + alpha A (Client.hpp:849-869)
