@@ -608,6 +608,54 @@ int porla_kzg_hadd_host(const uint8_t *data_in, const uint8_t mac_in[64], size_t
 int porla_icc_hrebuild_host(uint8_t *const *levels, int level, size_t n_cols, size_t n_total, int curve);
 int porla_icc_mac_hrebuild_host(uint8_t *const *levels, int level, size_t n_total, int curve);
 
+/* ---- Server::update's H path for K independent files in ONE asynchronous call (Server.hpp:401-476: HAdd :1388-1477, HRebuildX /
+ * HRebuildY :1329-1386, mix :1209-1328, the complement adds :449-469) ----
+ * The level stores -- data rows, MAC commitments, MAC alignments, X and Y parts -- stay in HBM, where the batched audits read them;
+ * the host wrappers above carry one block through host buffers and wait.  Request a is one write to one file:
+ *   d_block        n_cols x 32 bytes little-endian raw chunks (any 256-bit values)
+ *   d_mac          the block's MAC, 64 bytes big-endian affine (zeros = infinity)
+ *   d_complements  2 * 2^level points of 64 bytes (2^level for the X part, then 2^level for Y), or NULL = none
+ *   write_step     the value HAdd sees (after the ++ of Server.hpp:431); write_step % n_total == 0 is CRebuild's step and refused
+ *   level          the level HAdd lands on (0 = level 0 was empty); pad must be 0
+ *   data_x .. align_y  HOST arrays of level + 1 DEVICE pointers: family[i] = level i's 2 * 2^i rows as porla_icc_hrebuild_host lays them
+ *                  out (the first 2^i resident, the second 2^i incoming; a data row = n_cols 64-byte little-endian symbols < LCM, a
+ *                  point row = one 64-byte affine point)
+ * n_cols = the SRS size (KZG) or 128 (IPA); n_total = num_blocks, a power of two >= 2; the curve is the entry point's.
+ * Per request, byte for byte the reference's sequence:
+ *   HAdd      wt = w^reverse_bits(write_step % n_total, height-1); data X row = the chunks, data Y row = (chunk * wt) mod p_icc (both
+ *             zero-extended to 64 bytes); MAC X = MAC, MAC Y = wt * MAC; align X = infinity, align Y = Commit(c), c = (Y - chunk * wt)
+ *             mod q, against the resident SRS (KZG) or generators_fb's first 128 points (IPA).  level == 0: row 0 of level 0, and the
+ *             request is done apart from its complements; otherwise row 1, the incoming half.
+ *   HRebuild  for i < level: the halves of family[i] mixed into the incoming half of family[i+1] (the arithmetic of
+ *             porla_icc_mix_device / porla_icc_mac_mix_pair_device, v = w^(n_total / 2^i)), all six families; then the incoming half
+ *             of family[level] copied over its resident half.
+ *   complements  mac_x[level][j] += comp[j], mac_y[level][j] += comp[2^level + j], j < 2^level: the RESIDENT half only.
+ * Rows the reference does not write stay untouched.
+ * Contract: asynchronous on hip_stream -- no host wait, no internal side stream; the work waits for whatever was enqueued on
+ * hip_stream before the call and the levels are complete when the stream is.  Two writes to the same file go in two calls on one
+ * stream, with no host synchronisation between them.  The launch sequence depends on the highest level of the call, not on k.
+ * PORLA_ERR_ARG (with a message, before the device is touched): NULL reqs with k > 0; a NULL block, MAC, family array or level
+ * pointer; n_total not a power of two or < 2; level < 0 or 2^level > n_total; write_step % n_total == 0; pad != 0; two requests of
+ * one call naming the same level-0 pointer in any family (requests must be disjoint); IPA: a NULL base, a BN254 base, a base with
+ * fewer than 128 points.  k = 0 returns 0 and does nothing; no SRS (KZG): PORLA_ERR_STATE; valid arguments without a device:
+ * PORLA_ERR_NO_DEVICE.  Thread-safe beside the audits and the mixes (the twiddle tables are used under the workspace locks and fences
+ * of porla_icc_mix_device / porla_icc_mac_mix_device).
+ * Not yet measured on an MI355X: tools/bench_update_batch.py times it against the composition of the single-step entry points. */
+#define PORLA_UPDATE_REQ_BYTES 88   /* sizeof(porla_update_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    const void *d_block;
+    const void *d_mac;
+    const void *d_complements;
+    unsigned long long write_step;
+    int level; int pad;
+    void *const *data_x, *const *data_y;
+    void *const *mac_x,  *const *mac_y;
+    void *const *align_x, *const *align_y;
+} porla_update_req;
+int porla_kzg_update_batch_device(const porla_update_req *reqs, size_t k, size_t n_total, void *hip_stream);
+int porla_ipa_update_batch_device(porla_fixed_base *generators_fb, const porla_update_req *reqs, size_t k, size_t n_total,
+                                  void *hip_stream);
+
 /* ---- audit row combine (Server::audit, Server.hpp:790-828) + the scalar part of align_MAC on the result (:531-541) ----
  * B_j = sum_i coeff_i * row_i[j] (exact integer), then aligned_j = B_j mod p_icc, c_j = (aligned_j - B_j) mod q.
  * The challenged rows are addressed inside row stores resident in HBM:

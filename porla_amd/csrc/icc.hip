@@ -63,14 +63,12 @@ static int ensure_twiddles(IccWs* ws, int curve, size_t n, hipStream_t stream) {
     return PORLA_OK;
 }
 
+// the fence entered on `stream`, the twiddle table and its reduced-radix form (80-byte slots) resident for (n_total, curve)
 template <class Q>
-static int icc_mix_core(IccWs* ws, int curve, const uint8_t* d_a0, const uint8_t* d_a1, size_t len, size_t ncols, size_t n_total,
-                        uint8_t* d_out, hipStream_t stream) {
+static int icc_mix_tables(IccWs* ws, int curve, size_t n_total, hipStream_t stream) {
     int rc;
     if ((rc = ws->fence.enter(stream))) return rc;
     if ((rc = ensure_twiddles<Q>(ws, curve, n_total, stream))) return rc;
-    const size_t total = len * ncols;
-    // the reduced-radix kernel (icc30.hip.h:k_icc_mix30) and its twiddle table
     if (ws->tw30_n != n_total || ws->tw30_curve != curve) {
         if ((rc = ws->tw30.ensure(n_total * ICC30_SLOT_WORDS * 4))) return rc;
         hipLaunchKernelGGL((k_icc_twiddles30<Q>), dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, stream,
@@ -78,6 +76,15 @@ static int icc_mix_core(IccWs* ws, int curve, const uint8_t* d_a0, const uint8_t
         ws->tw30_n = (uint32_t)n_total;
         ws->tw30_curve = curve;
     }
+    return PORLA_OK;
+}
+template <class Q>
+static int icc_mix_core(IccWs* ws, int curve, const uint8_t* d_a0, const uint8_t* d_a1, size_t len, size_t ncols, size_t n_total,
+                        uint8_t* d_out, hipStream_t stream) {
+    int rc;
+    // the reduced-radix kernel (icc30.hip.h:k_icc_mix30) and its twiddle table
+    if ((rc = icc_mix_tables<Q>(ws, curve, n_total, stream))) return rc;
+    const size_t total = len * ncols;
     {
         ProfScope ps("icc_mix", stream);
         hipLaunchKernelGGL((k_icc_mix30<Q>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, d_a0, d_a1, (uint32_t)len,
@@ -211,6 +218,38 @@ static int icc_encode_dispatch(IccWs* ws, int curve, const uint8_t* d_rows, size
                     : icc_encode_core<IccSecp256k1Fn>(ws, 1, d_rows, n, ncols, ws_step, part, d_x, d_al, d_sc, scalar_le, stream, d_qres, out_y);
     if (rc) return rc;
     return ws->fence.leave(stream);
+}
+
+// For update_batch.hip: wt of one write as the data side multiplies by it (the Montgomery residue pair) and as the MAC side does (the
+// plain integer, 32 bytes big-endian); and the reduced-radix twiddle table k_icc_mix30 reads, under the lock and the fence of
+// icc_mix_core.  acquire returns with the workspace's mutex HELD when it succeeds; release records the fence and lets go.
+int icc_wt_residues(int curve, size_t n_total, unsigned long long write_step, uint32_t wt_p[8], uint32_t wt_q[8], uint8_t plain_be[32]) {
+    if (curve == 0) {
+        const IccElem<IccBn254Fr> wt = icc_wt<IccBn254Fr>(n_total, write_step, plain_be);
+        for (int k = 0; k < 8; k++) { wt_p[k] = wt.p.v[k]; wt_q[k] = wt.q.v[k]; }
+    } else {
+        const IccElem<IccSecp256k1Fn> wt = icc_wt<IccSecp256k1Fn>(n_total, write_step, plain_be);
+        for (int k = 0; k < 8; k++) { wt_p[k] = wt.p.v[k]; wt_q[k] = wt.q.v[k]; }
+    }
+    return PORLA_OK;
+}
+int icc_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** tw30) {
+    IccWs* ws = nullptr;
+    int rc = get_icc_ws(&ws);
+    if (rc) return rc;
+    ws->mu.lock();
+    rc = curve == 0 ? icc_mix_tables<IccBn254Fr>(ws, 0, n_total, stream) : icc_mix_tables<IccSecp256k1Fn>(ws, 1, n_total, stream);
+    if (rc) { ws->mu.unlock(); return rc; }
+    *tw30 = (const uint32_t*)ws->tw30.p;
+    return PORLA_OK;
+}
+int icc_mix_tables_release(hipStream_t stream) {
+    IccWs* ws = nullptr;
+    int rc = get_icc_ws(&ws);
+    if (rc) return rc;                       // (the workspace exists: acquire made it)
+    rc = ws->fence.leave(stream);
+    ws->mu.unlock();
+    return rc;
 }
 
 int icc_wt_scalar_be(size_t n_total, unsigned long long write_step, uint8_t out[32]) {

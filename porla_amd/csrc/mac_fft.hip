@@ -142,8 +142,6 @@ static size_t maco_lds_bytes() {
     }
     return sizeof(MacOctLds<M>);
 }
-// butterflies (or mix elements) up to which a launch leaves half the chip idle at four lanes each: eight lanes per butterfly
-constexpr size_t MACO_MAX_BUTTERFLIES = 8192;      // same-box A/B against four lanes: profiles/r05_k_mac_octet_ab.txt
 
 template <class C, class Q>
 static int mac_mix_core(MacWs* ws, int curve, const uint8_t* d_a0, const uint8_t* d_a1, size_t len, size_t n_total, uint8_t* d_out,
@@ -294,6 +292,28 @@ static int mac_encode_core(MacWs* ws, int curve, const uint8_t* d_in, size_t n, 
     }
     PORLA_HIP(hipGetLastError());
     return PORLA_OK;
+}
+
+// For update_batch.hip: the scalar table the point mixes read (w^e mod p_icc, reduced mod the group order), under the lock and the
+// fence mac_mix_core's callers hold.  acquire returns with g_mac_mu HELD when it succeeds; release records the fence and lets go.
+// quad_max_log: the row count (log2) up to which mac_mix_core takes its four- and eight-lane forms (PORLA_MAC_QUAD_MAX).
+int mac_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** tws, int* quad_max_log) {
+    g_mac_mu.lock();
+    MacWs* ws = nullptr;
+    int rc = get_mac_ws(&ws);
+    if (!rc) rc = ws->fence.enter(stream);
+    if (!rc) rc = curve == 0 ? ensure_mac_twiddles<IccBn254Fr>(ws, 0, n_total, stream) : ensure_mac_twiddles<IccSecp256k1Fn>(ws, 1, n_total, stream);
+    if (rc) { g_mac_mu.unlock(); return rc; }
+    *tws = (const uint32_t*)ws->tws.p;
+    *quad_max_log = macq_max_log(14);
+    return PORLA_OK;
+}
+int mac_mix_tables_release(hipStream_t stream) {
+    MacWs* ws = nullptr;
+    int rc = get_mac_ws(&ws);
+    if (!rc) rc = ws->fence.leave(stream);
+    g_mac_mu.unlock();
+    return rc;
 }
 
 static int mac_dispatch(MacWs* ws, int curve, const uint8_t* d_in, size_t n, unsigned long long write_step, int part,

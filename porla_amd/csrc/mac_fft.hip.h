@@ -552,6 +552,8 @@ __device__ __forceinline__ void store_affine_be(uint8_t* dst, const XYZZ<M>& p);
 // (um + tm | um - tm).  ~570 product rounds in sequence instead of ~700.  The two quads of an octet sit in one wave: the LDS traffic
 // between them needs no block barrier (macq_sync).  32 octets per block: 68 KiB of LDS, two blocks per compute unit.
 constexpr int MACO_BF = 32;
+// butterflies (or mix elements) up to which a launch leaves half the chip idle at four lanes each: eight lanes per butterfly
+constexpr size_t MACO_MAX_BUTTERFLIES = 8192;      // same-box A/B against four lanes: profiles/r05_k_mac_octet_ab.txt
 // (these kernels only run where the chip is under-filled: no neighbour to leave registers to -- two waves per SIMD, 256 registers)
 #define MACO_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
 template <class M>
@@ -769,19 +771,14 @@ k_mac_stage30_oct_uniform(XYZZ<typename C::Fp>* __restrict__ work, const uint32_
 
 // Server::mix's MAC part with eight lanes per i (k_mac_mix_quad's work): lanes 0 / 4 convert the two inputs on the way in, invert for
 // the two outputs
+// butterfly i of one mix on the calling octet (all eight lanes; `valid` false: a padding octet that computes butterfly 0 and stores
+// nothing): the body of k_mac_mix_oct, shared with the work-list form of update_batch.hip.h
 template <class C>
-__global__ void __launch_bounds__(8 * MACO_BF) MACO_ATTR
-k_mac_mix_oct(const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1, uint32_t len, const uint32_t* __restrict__ tws,
-              uint32_t tw_step, uint8_t* __restrict__ out, const uint8_t* __restrict__ b0, const uint8_t* __restrict__ b1,
-              uint8_t* __restrict__ out_b) {
+__device__ __forceinline__ void maco_mix_one(MacOctLds<typename C::Fp>& L, const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1,
+                                             uint32_t i, uint32_t len, bool valid, const uint32_t* __restrict__ tws, uint32_t tw_step,
+                                             uint8_t* __restrict__ out) {
     using M = typename C::Fp;
-    MACO_LDS(L);
-    __builtin_amdgcn_s_setprio(3);                                         // (the data part of the same mix runs beside this kernel)
-    if (blockIdx.y) { a0 = b0; a1 = b1; out = out_b; }                      // the second array pair of a mix (see k_mac_mix_quad)
     const uint32_t o = threadIdx.x >> 3, half = (threadIdx.x >> 2) & 1u, r = threadIdx.x & 3u, lane = threadIdx.x & 63u;
-    uint32_t i = blockIdx.x * MACO_BF + o;
-    const bool valid = i < len;
-    if (!valid) i = 0;
     uint32_t sc[8];
     {
         const uint4* w4 = reinterpret_cast<const uint4*>(tws + (size_t)i * tw_step * 8);
@@ -795,6 +792,20 @@ k_mac_mix_oct(const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1, ui
     macq_sync();
     if (valid && r == 0u)                                                  // the two inversions side by side (lanes 0 and 4)
         store_affine_be<M>(out + ((size_t)i + (half ? len : 0)) * 64, xyzz30_to_xyzz<M>(xyzz30_load_lazy<M>(&L.qd[o].tbl[1 + half])));
+}
+template <class C>
+__global__ void __launch_bounds__(8 * MACO_BF) MACO_ATTR
+k_mac_mix_oct(const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1, uint32_t len, const uint32_t* __restrict__ tws,
+              uint32_t tw_step, uint8_t* __restrict__ out, const uint8_t* __restrict__ b0, const uint8_t* __restrict__ b1,
+              uint8_t* __restrict__ out_b) {
+    using M = typename C::Fp;
+    MACO_LDS(L);
+    __builtin_amdgcn_s_setprio(3);                                         // (the data part of the same mix runs beside this kernel)
+    if (blockIdx.y) { a0 = b0; a1 = b1; out = out_b; }                      // the second array pair of a mix (see k_mac_mix_quad)
+    uint32_t i = blockIdx.x * MACO_BF + (threadIdx.x >> 3);
+    const bool valid = i < len;
+    if (!valid) i = 0;
+    maco_mix_one<C>(L, a0, a1, i, len, valid, tws, tw_step, out);
 }
 
 // Stage 1 of the network with four lanes per butterfly: every twiddle is w^0 = 1 (tm = MAC[k+1]), so the stage is its two
@@ -844,21 +855,13 @@ k_mac_load30_quad(const uint8_t* __restrict__ in, uint32_t n, XYZZ<typename C::F
 
 // Server::mix's MAC part (k_mac_mix below) with four lanes per i: the butterfly out[i] = A0[i] + v^i A1[i], out[i + len] = A0[i] -
 // v^i A1[i] on 64-byte affine points -- lanes 0 / 1 convert the two inputs on the way in and invert for the two outputs
+// butterfly i of one mix on the calling quad (`valid` as for maco_mix_one): the body of k_mac_mix_quad, shared with update_batch.hip.h
 template <class C>
-__global__ void __launch_bounds__(4 * MACQ_BF) MACQ_GUEST_ATTR
-k_mac_mix_quad(const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1, uint32_t len, const uint32_t* __restrict__ tws,
-               uint32_t tw_step, uint8_t* __restrict__ out, const uint8_t* __restrict__ b0, const uint8_t* __restrict__ b1,
-               uint8_t* __restrict__ out_b) {
+__device__ __forceinline__ void macq_mix_one(MacQuadLds<typename C::Fp>& L, const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1,
+                                             uint32_t i, uint32_t len, bool valid, const uint32_t* __restrict__ tws, uint32_t tw_step,
+                                             uint8_t* __restrict__ out) {
     using M = typename C::Fp;
-    MACQ_LDS(L);
-    // gridDim.y == 2: Server::mix runs this butterfly on the MAC commitments AND on the MAC alignments with the same v^i
-    // (Server.hpp:1281-1318) -- the second array pair rides in the same launch (a stage this short is latency: two for the price of one)
-    __builtin_amdgcn_s_setprio(3);                                         // (the data part of the same mix runs beside this kernel)
-    if (blockIdx.y) { a0 = b0; a1 = b1; out = out_b; }
     const uint32_t q = threadIdx.x >> 2, r = threadIdx.x & 3u, lane = threadIdx.x & 63u;
-    uint32_t i = blockIdx.x * MACQ_BF + q;
-    const bool valid = i < len;
-    if (!valid) i = 0;
     uint32_t sc[8];
     {
         const uint4* w4 = reinterpret_cast<const uint4*>(tws + (size_t)i * tw_step * 8);
@@ -874,6 +877,22 @@ k_mac_mix_quad(const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1, u
     macq_sync();
     if (valid && r < 2u)                                                           // the two inversions side by side
         store_affine_be<M>(out + ((size_t)i + (r ? len : 0)) * 64, xyzz30_to_xyzz<M>(xyzz30_load_lazy<M>(&L.qd[q].tbl[1 + r])));
+}
+template <class C>
+__global__ void __launch_bounds__(4 * MACQ_BF) MACQ_GUEST_ATTR
+k_mac_mix_quad(const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1, uint32_t len, const uint32_t* __restrict__ tws,
+               uint32_t tw_step, uint8_t* __restrict__ out, const uint8_t* __restrict__ b0, const uint8_t* __restrict__ b1,
+               uint8_t* __restrict__ out_b) {
+    using M = typename C::Fp;
+    MACQ_LDS(L);
+    // gridDim.y == 2: Server::mix runs this butterfly on the MAC commitments AND on the MAC alignments with the same v^i
+    // (Server.hpp:1281-1318) -- the second array pair rides in the same launch (a stage this short is latency: two for the price of one)
+    __builtin_amdgcn_s_setprio(3);                                         // (the data part of the same mix runs beside this kernel)
+    if (blockIdx.y) { a0 = b0; a1 = b1; out = out_b; }
+    uint32_t i = blockIdx.x * MACQ_BF + (threadIdx.x >> 2);
+    const bool valid = i < len;
+    if (!valid) i = 0;
+    macq_mix_one<C>(L, a0, a1, i, len, valid, tws, tw_step, out);
 }
 
 template <class M>
@@ -895,15 +914,11 @@ __device__ __forceinline__ void store_affine_be(uint8_t* dst, const XYZZ<M>& p) 
 
 // MAC part of Server::mix (Server.hpp:1281-1318): out[i] = A0[i] + v^i * A1[i], out[i+len] = A0[i] - v^i * A1[i], v = w^(N/len);
 // 64-byte big-endian affine points in and out.  One lane per i.
+// butterfly i of one mix on ONE lane: the body of k_mac_mix, shared with update_batch.hip.h
 template <class C>
-__global__ void __launch_bounds__(64)
-k_mac_mix(const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1, uint32_t len, const uint32_t* __restrict__ tws,
-          uint32_t tw_step, uint8_t* __restrict__ out, const uint8_t* __restrict__ b0, const uint8_t* __restrict__ b1,
-          uint8_t* __restrict__ out_b) {
+__device__ __forceinline__ void mac_mix_one(const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1, uint32_t i, uint32_t len,
+                                            const uint32_t* __restrict__ tws, uint32_t tw_step, uint8_t* __restrict__ out) {
     using M = typename C::Fp;
-    if (blockIdx.y) { a0 = b0; a1 = b1; out = out_b; }          // the second array pair of a mix (see k_mac_mix_quad)
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= len) return;
     uint32_t sc[8];
     const uint4* q = reinterpret_cast<const uint4*>(tws + (size_t)i * tw_step * 8);
     uint4 a = q[0], b = q[1];
@@ -917,6 +932,16 @@ k_mac_mix(const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1, uint32
     xyzz30_add_mem<M>(&dif, &tm, 1, 0, nullptr);
     store_affine_be<M>(out + (size_t)i * 64, xyzz30_to_xyzz<M>(xyzz30_load_lazy<M>(&sum)));
     store_affine_be<M>(out + ((size_t)i + len) * 64, xyzz30_to_xyzz<M>(xyzz30_load_lazy<M>(&dif)));
+}
+template <class C>
+__global__ void __launch_bounds__(64)
+k_mac_mix(const uint8_t* __restrict__ a0, const uint8_t* __restrict__ a1, uint32_t len, const uint32_t* __restrict__ tws,
+          uint32_t tw_step, uint8_t* __restrict__ out, const uint8_t* __restrict__ b0, const uint8_t* __restrict__ b1,
+          uint8_t* __restrict__ out_b) {
+    if (blockIdx.y) { a0 = b0; a1 = b1; out = out_b; }          // the second array pair of a mix (see k_mac_mix_quad)
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    mac_mix_one<C>(a0, a1, i, len, tws, tw_step, out);
 }
 
 // XYZZ work array -> 64-byte big-endian affine MACs (infinity = 64 zero bytes, main.go:224-230)

@@ -1,0 +1,275 @@
+// Server::update's H path for K independent files in ONE asynchronous call (include/porla_gpu.h: porla_kzg_update_batch_device /
+// porla_ipa_update_batch_device): HAdd, HRebuildX / HRebuildY and the complement adds (porla/Server/Server.hpp:401-476, 1329-1477) on
+// level stores that stay in HBM.  The host wrappers (porla_icc_hadd_host, porla_icc_hrebuild_host, porla_icc_mac_hrebuild_host) carry one
+// block through host buffers and wait; here every step of every request is on the device and on the caller's stream, and the launch
+// sequence depends on Lmax = the highest level of the call, never on K:
+//
+//   upload                   one copy of the host-built work list (descriptors with wt, the level pointers) from pinned memory
+//   k_update_hadd            data X / data Y rows of level 0 in place, the K rows of alignment scalars to scratch
+//   fb_commit / fb_fold      ONE commitment pass over the K scalar rows (the resident SRS table, or the generators' fixed base)
+//   k_update_place           MAC X, MAC Y = wt * MAC, align X = infinity, align Y = Commit(c)
+//   for i < Lmax:            k_update_mix_data (both parts) and k_update_mix_points (the four point families) of the requests with level > i
+//   k_update_close           incoming half over resident half at the request's level, then the complements onto MAC X / MAC Y
+#include "engine.hpp"
+#include "update_batch.hip.h"
+#include "../../include/porla_gpu.h"
+
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+namespace porla {
+
+constexpr size_t UPD_IPA_COLS = 128;           // NUM_CHUNKS: the row width of the IPA build
+
+struct UpdateBatchWs {
+    std::mutex mu;
+    int device = -1;
+    Buf list, scalars;
+    PinnedList h_list;
+    UseFence fence;
+    bool lds_set = false;
+};
+static std::mutex g_upd_mu;
+static std::vector<UpdateBatchWs*> g_upd_ws;
+
+// dynamic LDS above 64 KiB: a kernel must be told once per device (as mac_fft.hip does for the kernels these are forms of)
+static void update_lds_attributes(UpdateBatchWs* ws) {
+    if (ws->lds_set) return;
+    auto set = [](const void* f, size_t bytes) { (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+    set(reinterpret_cast<const void*>(&k_update_place<Bn254G1>), sizeof(MacOctLds<Bn254Fp>));
+    set(reinterpret_cast<const void*>(&k_update_place<Secp256k1G>), sizeof(MacOctLds<Secp256k1Fp>));
+    set(reinterpret_cast<const void*>(&k_update_mix_points_oct<Bn254G1>), sizeof(MacOctLds<Bn254Fp>));
+    set(reinterpret_cast<const void*>(&k_update_mix_points_oct<Secp256k1G>), sizeof(MacOctLds<Secp256k1Fp>));
+    set(reinterpret_cast<const void*>(&k_update_mix_points_quad<Bn254G1>), sizeof(MacQuadLds<Bn254Fp>));
+    set(reinterpret_cast<const void*>(&k_update_mix_points_quad<Secp256k1G>), sizeof(MacQuadLds<Secp256k1Fp>));
+    ws->lds_set = true;
+}
+
+template <class C> struct UpdCurve;
+template <> struct UpdCurve<Bn254G1> { using Q = IccBn254Fr; static constexpr int id = 0; };
+template <> struct UpdCurve<Secp256k1G> { using Q = IccSecp256k1Fn; static constexpr int id = 1; };
+
+struct UpdPlan {
+    const UpdDesc* d_desc;
+    uint8_t* const* d_ptrs;
+    uint32_t l1, k, ncols;
+    hipStream_t stream;
+};
+
+template <class C>
+static int launch_place(const UpdPlan& P, const XYZZ<typename C::Fp>* sums, uint32_t S) {
+    ProfScope ps("update_place", P.stream);
+    hipLaunchKernelGGL((k_update_place<C>), dim3((P.k + MACO_BF - 1) / MACO_BF), dim3(8 * MACO_BF), sizeof(MacOctLds<typename C::Fp>), P.stream,
+                       P.d_desc, P.d_ptrs, P.l1, P.k, sums, S);
+    PORLA_HIP(hipGetLastError());
+    return PORLA_OK;
+}
+static int place_after_srs(const XYZZ<Bn254Fp>* sums, uint32_t S, void* ctx) { return launch_place<Bn254G1>(*(const UpdPlan*)ctx, sums, S); }
+
+// the mixes of steps 0 .. lmax - 1 under the table leases (the MAC side's lock first, as mac_fft.hip's matrix form takes them)
+template <class C>
+static int launch_steps(const UpdPlan& P, const std::vector<uint32_t>& active, uint32_t lmax, size_t n_total) {
+    using Q = typename UpdCurve<C>::Q;
+    using M = typename C::Fp;
+    const uint32_t* tws = nullptr;
+    const uint32_t* tw30 = nullptr;
+    int quad_log = 0, rc;
+    if ((rc = mac_mix_tables_acquire(UpdCurve<C>::id, n_total, P.stream, &tws, &quad_log))) return rc;
+    if ((rc = icc_mix_tables_acquire(UpdCurve<C>::id, n_total, P.stream, &tw30))) { (void)mac_mix_tables_release(P.stream); return rc; }
+    for (uint32_t i = 0; i < lmax && !rc; i++) {
+        const uint32_t a = active[i], tw_step = (uint32_t)(n_total >> i);
+        {
+            ProfScope ps("update_mix_data", P.stream);
+            const size_t total = ((size_t)2 * a * P.ncols) << i;
+            hipLaunchKernelGGL((k_update_mix_data<Q>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, P.stream, P.d_ptrs, P.l1, a, i, P.ncols,
+                               tw30, tw_step);
+        }
+        ProfScope ps("update_mix_points", P.stream);
+        // the form by the step's total butterfly count, with mac_mix_core's thresholds
+        const size_t bf = ((size_t)4 * a) << i, quad_max = (size_t)1 << quad_log;
+        if (quad_log > 0 && bf <= quad_max && bf <= MACO_MAX_BUTTERFLIES)
+            hipLaunchKernelGGL((k_update_mix_points_oct<C>), dim3((unsigned)((bf + MACO_BF - 1) / MACO_BF)), dim3(8 * MACO_BF), sizeof(MacOctLds<M>),
+                               P.stream, P.d_ptrs, P.l1, a, i, tws, tw_step);
+        else if (quad_log > 0 && bf <= quad_max)
+            hipLaunchKernelGGL((k_update_mix_points_quad<C>), dim3((unsigned)((bf + MACQ_BF - 1) / MACQ_BF)), dim3(4 * MACQ_BF), sizeof(MacQuadLds<M>),
+                               P.stream, P.d_ptrs, P.l1, a, i, tws, tw_step);
+        else
+            hipLaunchKernelGGL((k_update_mix_points_lane<C>), dim3((unsigned)((bf + 63) / 64)), dim3(64), 0, P.stream, P.d_ptrs, P.l1, a, i, tws,
+                               tw_step);
+        if (hipGetLastError() != hipSuccess) { set_last_error("porla: update batch: a mix launch failed"); rc = PORLA_ERR_HIP; }
+    }
+    const int r1 = icc_mix_tables_release(P.stream), r2 = mac_mix_tables_release(P.stream);
+    return rc ? rc : (r1 ? r1 : r2);
+}
+
+// ws->mu held.  fb == nullptr: the resident SRS (KZG).
+template <class C>
+static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_update_req* reqs, size_t k, size_t ncols, size_t n_total,
+                          hipStream_t stream) {
+    using Q = typename UpdCurve<C>::Q;
+    int rc;
+    // ---- the plan: requests by level, highest first (stable), so that the requests step i concerns are the first active[i]
+    std::vector<uint32_t> order(k);
+    for (size_t a = 0; a < k; a++) order[a] = (uint32_t)a;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return reqs[x].level > reqs[y].level; });
+    const uint32_t lmax = (uint32_t)reqs[order[0]].level, l1 = lmax + 1;
+    std::vector<uint32_t> active(lmax);
+    for (uint32_t i = 0; i < lmax; i++) {
+        uint32_t a = 0;
+        while (a < k && (uint32_t)reqs[order[a]].level > i) a++;
+        active[i] = a;
+    }
+    // ---- the work list: descriptors | level pointers, one pinned buffer, one copy
+    const size_t desc_b = k * sizeof(UpdDesc), ptr_b = k * UPD_FAMILIES * l1 * sizeof(void*), list_b = desc_b + ptr_b;
+    if ((rc = ws->h_list.stage(list_b))) return rc;
+    {
+        UpdDesc* hd = (UpdDesc*)ws->h_list.h;
+        void** hp = (void**)((uint8_t*)ws->h_list.h + desc_b);
+        for (size_t a = 0; a < k; a++) {
+            const porla_update_req& R = reqs[order[a]];
+            UpdDesc& D = hd[a];
+            D.block = (const uint8_t*)R.d_block; D.mac = (const uint8_t*)R.d_mac; D.comp = (const uint8_t*)R.d_complements;
+            uint8_t be[32];
+            (void)icc_wt_residues(UpdCurve<C>::id, n_total, R.write_step, D.wt_p, D.wt_q, be);
+            h_load_be(D.wt_sc, be);
+            fe_reduce_plain<Q>(D.wt_sc, 8);                    // the group sees wt mod its order (convert_ZZ_to_scalar / fr.SetBytes)
+            D.level = (uint32_t)R.level; D.pad = 0;
+            void* const* fam[UPD_FAMILIES] = {R.data_x, R.data_y, R.mac_x, R.mac_y, R.align_x, R.align_y};
+            for (uint32_t f = 0; f < UPD_FAMILIES; f++)
+                for (uint32_t l = 0; l < l1; l++) hp[(a * UPD_FAMILIES + f) * l1 + l] = l <= (uint32_t)R.level ? fam[f][l] : nullptr;
+        }
+    }
+    if ((rc = ws->list.ensure(list_b))) return rc;
+    if ((rc = ws->scalars.ensure(k * ncols * 32))) return rc;
+    update_lds_attributes(ws);
+    if ((rc = ws->fence.enter(stream))) return rc;
+    if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
+    UpdPlan P;
+    P.d_desc = (const UpdDesc*)ws->list.p;
+    P.d_ptrs = (uint8_t* const*)((const uint8_t*)ws->list.p + desc_b);
+    P.l1 = l1; P.k = (uint32_t)k; P.ncols = (uint32_t)ncols; P.stream = stream;
+    // ---- 1. HAdd, data side
+    {
+        ProfScope ps("update_hadd", stream);
+        hipLaunchKernelGGL((k_update_hadd<Q>), dim3((unsigned)((k * ncols + 255) / 256)), dim3(256), 0, stream, P.d_desc, P.d_ptrs, l1, (uint32_t)k,
+                           (uint32_t)ncols, (uint8_t*)ws->scalars.p);
+        PORLA_HIP(hipGetLastError());
+    }
+    // ---- 2. the K commitments, then the four point slots
+    if constexpr (UpdCurve<C>::id == 0) {
+        if ((rc = kzg_commit_rows_raw((const uint8_t*)ws->scalars.p, k, stream, place_after_srs, &P))) return rc;
+    } else {
+        std::lock_guard<std::mutex> lk(fb->mu);
+        if ((rc = fb->commit_device((const uint8_t*)ws->scalars.p, k, ncols, 32 * ncols, nullptr, stream))) return rc;
+        if ((rc = launch_place<C>(P, fb->partial, fb->last_S))) return rc;
+        if ((rc = fb->fence.leave(stream))) return rc;
+    }
+    // ---- 3. the rebuild steps
+    if (lmax && (rc = launch_steps<C>(P, active, lmax, n_total))) return rc;
+    // ---- 4. the close
+    {
+        ProfScope ps("update_close", stream);
+        const size_t units = ((size_t)ncols * 4) << lmax;          // 16-byte units of the largest data copy
+        const unsigned gx = (unsigned)std::min<size_t>((units + 255) / 256, 512);
+        hipLaunchKernelGGL((k_update_close<C>), dim3(gx, (unsigned)k), dim3(256), 0, stream, P.d_desc, P.d_ptrs, l1, (uint32_t)ncols);
+        PORLA_HIP(hipGetLastError());
+    }
+    return PORLA_OK;
+}
+
+// the checks both entry points make before the device is touched
+static int update_check(const char* who, const porla_update_req* reqs, size_t k, size_t n_total) {
+    auto bad = [&](const std::string& what) { set_last_error(std::string(who) + ": " + what); return PORLA_ERR_ARG; };
+    if (k && !reqs) return bad("reqs is NULL");
+    int ln = 0;
+    while (((size_t)1 << ln) < n_total && ln < 62) ln++;
+    if (n_total < 2 || ((size_t)1 << ln) != n_total || n_total > ((size_t)1 << 30)) return bad("n_total must be a power of two, 2 .. 2^30");
+    if (k > 0xffffu) return bad("more than 65535 requests in one call");
+    std::unordered_set<const void*> seen;
+    for (size_t a = 0; a < k; a++) {
+        const porla_update_req& R = reqs[a];
+        const std::string at = "request " + std::to_string(a) + ": ";
+        if (!R.d_block || !R.d_mac) return bad(at + "a NULL block or MAC");
+        if (R.pad != 0) return bad(at + "pad must be 0");
+        if (R.level < 0 || R.level > 30 || ((size_t)1 << R.level) > n_total) return bad(at + "level must be 0 .. log2(n_total)");
+        if (R.write_step % n_total == 0) return bad(at + "write_step % n_total == 0 is CRebuild's step, not an H update");
+        void* const* fam[UPD_FAMILIES] = {R.data_x, R.data_y, R.mac_x, R.mac_y, R.align_x, R.align_y};
+        for (uint32_t f = 0; f < UPD_FAMILIES; f++) {
+            if (!fam[f]) return bad(at + "a NULL family array");
+            for (int l = 0; l <= R.level; l++) if (!fam[f][l]) return bad(at + "a NULL level pointer");
+            if (!seen.insert(fam[f][0]).second) return bad(at + "a level-0 pointer another request (or family) of this call names too: requests must be disjoint");
+        }
+    }
+    return PORLA_OK;
+}
+
+static int update_workspace(UpdateBatchWs** out) {
+    int dev = 0;
+    PORLA_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_upd_mu);
+    for (auto* w : g_upd_ws) if (w->device == dev) { *out = w; return PORLA_OK; }
+    UpdateBatchWs* w = new UpdateBatchWs();
+    w->device = dev;
+    g_upd_ws.push_back(w);
+    *out = w;
+    return PORLA_OK;
+}
+
+}  // namespace porla
+
+using namespace porla;
+
+static_assert(sizeof(porla_update_req) == PORLA_UPDATE_REQ_BYTES, "porla_update_req size");
+static_assert(offsetof(porla_update_req, d_block) == 0 && offsetof(porla_update_req, d_mac) == 8 &&
+              offsetof(porla_update_req, d_complements) == 16 && offsetof(porla_update_req, write_step) == 24 &&
+              offsetof(porla_update_req, level) == 32 && offsetof(porla_update_req, pad) == 36 &&
+              offsetof(porla_update_req, data_x) == 40 && offsetof(porla_update_req, data_y) == 48 &&
+              offsetof(porla_update_req, mac_x) == 56 && offsetof(porla_update_req, mac_y) == 64 &&
+              offsetof(porla_update_req, align_x) == 72 && offsetof(porla_update_req, align_y) == 80,
+              "porla_update_req offsets (include/porla_gpu.h)");
+
+extern "C" int porla_kzg_update_batch_device(const porla_update_req* reqs, size_t k, size_t n_total, void* hip_stream) {
+    int rc = update_check("porla_kzg_update_batch_device", reqs, k, n_total);
+    if (rc) return rc;
+    if (k == 0) return PORLA_OK;
+    if ((rc = ensure_device())) return rc;
+    size_t n = 0;
+    if ((rc = porla_kzg_row_coefficients(&n))) return rc;
+    if (n == 0) { set_last_error("porla: SRS not initialised (call init_SRS / init_SRS_from_data first)"); return PORLA_ERR_STATE; }
+    if (n > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
+    UpdateBatchWs* ws = nullptr;
+    if ((rc = update_workspace(&ws))) return rc;
+    std::lock_guard<std::mutex> lk(ws->mu);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    rc = update_enqueue<Bn254G1>(ws, nullptr, reqs, k, n, n_total, stream);
+    // the buffers of this call are behind the fence on every exit, a failing one included
+    const int rf = ws->fence.leave(stream);
+    return rc ? rc : rf;
+}
+
+extern "C" int porla_ipa_update_batch_device(porla_fixed_base* generators_fb, const porla_update_req* reqs, size_t k, size_t n_total,
+                                             void* hip_stream) {
+    static const char* who = "porla_ipa_update_batch_device";
+    int rc = update_check(who, reqs, k, n_total);
+    if (rc) return rc;
+    if (k == 0) return PORLA_OK;
+    if (!generators_fb) { set_last_error(std::string(who) + ": generators_fb is NULL"); return PORLA_ERR_ARG; }
+    if ((rc = ensure_device())) return rc;
+    // (a handle exists only where a device does: it is read after ensure_device, and still before any device work)
+    if (generators_fb->curve != 1 || generators_fb->secp.n_points < UPD_IPA_COLS) {
+        set_last_error(std::string(who) + ": generators_fb must be a secp256k1 fixed base over at least the 128 generators");
+        return PORLA_ERR_ARG;
+    }
+    UpdateBatchWs* ws = nullptr;
+    if ((rc = update_workspace(&ws))) return rc;
+    std::lock_guard<std::mutex> lk(ws->mu);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    rc = update_enqueue<Secp256k1G>(ws, &generators_fb->secp, reqs, k, UPD_IPA_COLS, n_total, stream);
+    const int rf = ws->fence.leave(stream);
+    return rc ? rc : rf;
+}

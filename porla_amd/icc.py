@@ -4,7 +4,7 @@ C ABI (include/porla_gpu.h: porla_icc_encode_*).  Rows are in the reference's ow
 little-endian chunks in (utils.h:353-364), 64-byte little-endian values mod LCM out (utils.h:473-517)."""
 import ctypes
 
-from .loader import lib
+from .loader import UpdateReq, lib
 
 CURVE = {"bn254": 0, "secp256k1": 1}
 NUM_CHUNKS = 128  # config.hpp:22
@@ -161,3 +161,37 @@ def hrebuild_host(level_bufs, level, n_total, curve="bn254", n_cols=NUM_CHUNKS):
 def mac_hrebuild_host(level_bufs, level, n_total, curve="bn254"):
     """the same for 64-byte affine points (MAC commitments, MAC alignments, the client's complements)"""
     _check(lib.porla_icc_mac_hrebuild_host(_level_ptrs(level_bufs), level, n_total, CURVE[curve]))
+
+
+# ---- Server::update's H path for K files in one asynchronous call (include/porla_gpu.h: porla_*_update_batch_device) ----
+UPDATE_FAMILIES = ("data_x", "data_y", "mac_x", "mac_y", "align_x", "align_y")
+
+
+def update_requests(reqs):
+    """a ctypes array of porla_update_req from per-write tuples (d_block, d_mac, d_complements or 0, write_step, level, data_x, data_y,
+    mac_x, mac_y, align_x, align_y): device addresses as integers, each family a sequence of level + 1 of them (None: a NULL family
+    array).  The array keeps the pointer arrays it refers to alive (arr._keep)."""
+    arr = (UpdateReq * max(len(reqs), 1))()
+    keep = []
+    for i, r in enumerate(reqs):
+        if len(r) != 11:
+            raise ValueError("update_batch_device: request %d has %d fields, want 11" % (i, len(r)))
+        fams = []
+        for f in r[5:]:
+            if f is None:
+                fams.append(None)
+                continue
+            a = (ctypes.c_void_p * max(len(f), 1))(*[(x or None) for x in f])
+            keep.append(a)
+            fams.append(ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p)))
+        arr[i] = UpdateReq(r[0] or None, r[1] or None, r[2] or None, r[3], r[4], 0, *fams)
+    arr._keep = keep
+    return arr
+
+
+def kzg_update_batch_device(reqs, n_total, stream=0):
+    """Server::update's H path (HAdd, HRebuildX / Y, the complement adds) of len(reqs) independent files in ONE asynchronous call on
+    `stream`, KZG build: the level stores named by the requests are rewritten in place on the device.  `reqs`: tuples as update_requests
+    takes them."""
+    arr = update_requests(reqs)
+    _check(lib.porla_kzg_update_batch_device(arr, len(reqs), n_total, ctypes.c_void_p(stream)))

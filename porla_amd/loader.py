@@ -37,6 +37,20 @@ class IpaVerifyReq(ctypes.Structure):
     _fields_ = KzgVerifyReq._fields_ + [("a_value", ctypes.c_uint8 * 32)]
 
 
+class UpdateReq(ctypes.Structure):
+    """porla_update_req, include/porla_gpu.h: one write of porla_kzg_update_batch_device / porla_ipa_update_batch_device
+    (PORLA_UPDATE_REQ_BYTES = 88); the six family fields are HOST arrays of level + 1 device pointers."""
+    _fields_ = [("d_block", ctypes.c_void_p), ("d_mac", ctypes.c_void_p), ("d_complements", ctypes.c_void_p),
+                ("write_step", ctypes.c_ulonglong), ("level", ctypes.c_int), ("pad", ctypes.c_int),
+                ("data_x", ctypes.POINTER(ctypes.c_void_p)), ("data_y", ctypes.POINTER(ctypes.c_void_p)),
+                ("mac_x", ctypes.POINTER(ctypes.c_void_p)), ("mac_y", ctypes.POINTER(ctypes.c_void_p)),
+                ("align_x", ctypes.POINTER(ctypes.c_void_p)), ("align_y", ctypes.POINTER(ctypes.c_void_p))]
+
+
+PORLA_UPDATE_REQ_BYTES = 88
+assert ctypes.sizeof(UpdateReq) == PORLA_UPDATE_REQ_BYTES
+
+
 def load():
     """Load the engine.  When torch is importable it is imported FIRST so that the HIP runtime the process
     ends up with is the one torch ships (both have soname libamdhip64.so.7; two runtimes in one process
@@ -143,6 +157,8 @@ def _declare(L):
     L.porla_kzg_audit_batch_device.restype = ctypes.c_int
     L.porla_ipa_audit_batch_device.argtypes = [vp, ctypes.POINTER(IpaAuditReq), sz, vp, vp, vp]
     L.porla_ipa_audit_batch_device.restype = ctypes.c_int
+    L.porla_kzg_update_batch_device.argtypes = [ctypes.POINTER(UpdateReq), sz, sz, vp]; L.porla_kzg_update_batch_device.restype = ctypes.c_int
+    L.porla_ipa_update_batch_device.argtypes = [vp, ctypes.POINTER(UpdateReq), sz, sz, vp]; L.porla_ipa_update_batch_device.restype = ctypes.c_int
     L.porla_ipa_prove_batch_device.argtypes = [vp, vp, vp, sz, vp, vp]; L.porla_ipa_prove_batch_device.restype = ctypes.c_int
     L.porla_ipa_verify_batch_device.argtypes = [vp, ctypes.POINTER(IpaVerifyReq), sz, vp, vp, vp]
     L.porla_ipa_verify_batch_device.restype = ctypes.c_int

@@ -350,6 +350,13 @@ class FixedBase:
         _check(lib.porla_ipa_audit_batch_device(self.h, arr, len(audits), ctypes.c_void_p(d_out), ctypes.c_void_p(d_b or None),
                                                 ctypes.c_void_p(stream)))
 
+    def ipa_update_batch_device(self, reqs, n_total, stream=0):
+        """Server::update's H path of len(reqs) independent files in ONE asynchronous call on `stream`, IPA build (128 columns);
+        self = a secp256k1 fixed base whose first 128 points are the generators.  `reqs`: tuples as icc.update_requests takes them."""
+        from .icc import update_requests
+        arr = update_requests(reqs)
+        _check(lib.porla_ipa_update_batch_device(self.h, arr, len(reqs), n_total, ctypes.c_void_p(stream)))
+
     def ipa_prove_batch_device(self, d_a, d_b, k, d_proofs, stream=0):
         """k proofs of Server::inner_product_prove(a, b) in ONE asynchronous call (porla_ipa_prove_batch_device): d_a, d_b = k x 128 x
         32 bytes big-endian, d_proofs = k x 556 bytes"""
