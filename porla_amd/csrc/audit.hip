@@ -13,7 +13,7 @@
 // 64 consecutive 64-byte symbols = 4 KiB per row, fully coalesced); the eight slices of a block meet in LDS; a second kernel
 // adds the blocks' partials and reduces once per column mod p_icc and mod q.  Algorithmic bytes: 8 192 B per challenged row
 // in (4 096 for a 256-bit row), 64 B per column out.
-#include "engine.hpp"
+#include "batch_host.hpp"
 #include "icc.hip.h"
 
 #include <vector>
@@ -255,8 +255,8 @@ int audit_combine_batch_launch(const KzgAuditDesc* d_desc, const uint32_t* d_blk
 }
 
 struct AuditWs { int device = -1; Buf partial; UseFence fence; };
-static std::mutex g_audit_mu;
-static std::vector<AuditWs*> g_audit_ws;
+static std::mutex g_audit_mu;   // one combine at a time enqueues
+static PerDevice<AuditWs> g_audit_ws;
 
 }  // namespace porla
 
@@ -274,11 +274,8 @@ extern "C" int porla_audit_combine_device(const void* d_rows64, const uint64_t* 
         return PORLA_ERR_ARG;
     }
     std::lock_guard<std::mutex> lk(g_audit_mu);
-    int dev = 0;
-    PORLA_HIP(hipGetDevice(&dev));
     AuditWs* ws = nullptr;
-    for (auto* w : g_audit_ws) if (w->device == dev) ws = w;
-    if (!ws) { ws = new AuditWs(); ws->device = dev; g_audit_ws.push_back(ws); }
+    if ((rc = g_audit_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     const uint32_t total = (uint32_t)(n64 + n32);
     // rows per slice: enough blocks for two per compute unit on a large challenge, never fewer than 4 rows per slice (the audit's

@@ -1,0 +1,75 @@
+// Host pieces every batched entry point is written against (the batched MSM, the KZG / IPA audit, prove and verify batches, the
+// update batch) and the older per-device workspaces share: the workspace registry, the argument refusals, the block -> owner lists
+// of a work list, the fenced call, and a commitment pass with its follow-up kernel under the table's lock.
+#pragma once
+#include "engine.hpp"
+
+namespace porla {
+
+// One workspace per device, created on first use and kept for the life of the process.  Ws has a default constructor and an
+// `int device`.  The lock is the registry's only: what serialises the use of a workspace is the owner's business.
+template <class Ws>
+struct PerDevice {
+    std::mutex mu;
+    std::vector<Ws*> all;
+    int get(Ws** out) {
+        int dev = 0;
+        PORLA_HIP(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        for (Ws* w : all) if (w->device == dev) { *out = w; return PORLA_OK; }
+        Ws* w = new Ws();
+        w->device = dev;
+        all.push_back(w);
+        *out = w;
+        return PORLA_OK;
+    }
+};
+
+static inline bool mul_ok(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
+
+// the refusal of an argument by the entry point `who`
+static inline int bad_arg(const char* who, const std::string& what) {
+    set_last_error(std::string(who) + ": " + what);
+    return PORLA_ERR_ARG;
+}
+
+// block -> owner list of a work list: blocks_of(a) times a, for a = 0 .. k - 1; returns the list's end
+template <class BlocksOf>
+static inline uint32_t* fill_owner_list(uint32_t* dst, size_t k, BlocksOf blocks_of) {
+    for (size_t a = 0; a < k; a++)
+        for (uint64_t b = blocks_of(a); b; b--) *dst++ = (uint32_t)a;
+    return dst;
+}
+
+// One call's use of a workspace (Ws: `mu`, `fence`) whose buffers later calls reuse, possibly on another stream.  The mutex is held
+// for the object's life; run() enters the fence on the call's stream BEFORE the enqueue sizes or touches any buffer, and the buffers
+// of the call are behind the fence on every exit, a failing one included.
+struct FencedCall {
+    std::unique_lock<std::mutex> lk;
+    UseFence& fence;
+    hipStream_t stream;
+    template <class Ws>
+    FencedCall(Ws* ws, hipStream_t s) : lk(ws->mu), fence(ws->fence), stream(s) {}
+    template <class Enqueue>
+    int run(Enqueue enqueue) {
+        int rc = fence.enter(stream);
+        if (rc) return rc;
+        rc = enqueue();
+        const int rf = fence.leave(stream);
+        return rc ? rc : rf;
+    }
+};
+
+// one commitment pass over n_rows contiguous rows of n_coeffs coefficients, sums left projective in the table's partials, and
+// `then(sums, S)` (row r at sums[r S]) enqueued under the table's lock before its fence is recorded again: the partials hold only the
+// LAST pass's sums, and another caller's pass may follow as soon as the lock is let go
+template <class C, class Then>
+static int commit_then(FixedBase<C>& fb, const uint8_t* d_rows, size_t n_rows, size_t n_coeffs, hipStream_t stream, Then then) {
+    std::lock_guard<std::mutex> lk(fb.mu);
+    int rc;
+    if ((rc = fb.commit_device(d_rows, n_rows, n_coeffs, 32 * n_coeffs, nullptr, stream))) return rc;
+    if ((rc = then((const XYZZ<typename C::Fp>*)fb.partial, fb.last_S))) return rc;
+    return fb.fence.leave(stream);
+}
+
+}  // namespace porla

@@ -328,20 +328,7 @@ int porla_gpu_release_msm_workspaces(void) {
                        &w->tree_m, &w->tree_mt, &w->small_part, &w->multi_acc, &w->batch_list, &w->batch_part, &w->batch_sums,
                        &w->batch_ctrl, &w->batch_out};
         for (Buf* b : bufs) b->release();
-        if (w->batch_upload) {
-            (void)hipEventSynchronize(w->batch_upload);
-            (void)hipEventDestroy(w->batch_upload);
-            w->batch_upload = nullptr;
-        }
-        if (w->h_batch) (void)hipHostFree(w->h_batch);
-        w->h_batch = nullptr;
-        w->h_batch_cap = 0;
-        for (auto& rb : w->batch_retired) {
-            (void)hipEventSynchronize(rb.second);
-            (void)hipHostFree(rb.first);
-            (void)hipEventDestroy(rb.second);
-        }
-        w->batch_retired.clear();
+        w->batch_list_h.release();
         w->batch_fence.reset();
     }
     (void)hipSetDevice(cur);

@@ -127,7 +127,7 @@ struct UseFence {
     void reset() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; used = false; last = nullptr; }
 };
 
-// A host-built work list on its way to the device (the batched audits): a pinned staging buffer, the event of its last upload, and
+// A host-built work list on its way to the device (the batched MSM, audits, verifiers and updates): a pinned staging buffer, the event of its last upload, and
 // the buffers whose upload was still queued when a later call came (freed once that copy is done, so that no call waits on the
 // host for earlier work).  Used under the mutex that serialises the owner's enqueue.
 struct PinnedList {
@@ -172,6 +172,21 @@ struct PinnedList {
         PORLA_HIP(hipEventRecord(upload, stream));
         return PORLA_OK;
     }
+    // waits for the uploads still queued and frees everything
+    void release() {
+        if (h) retired.emplace_back(h, upload);
+        for (auto& rb : retired) {
+            if (rb.second) {
+                (void)hipEventSynchronize(rb.second);
+                (void)hipEventDestroy(rb.second);
+            }
+            (void)hipHostFree(rb.first);
+        }
+        retired.clear();
+        h = nullptr;
+        cap = 0;
+        upload = nullptr;
+    }
 };
 
 struct Workspace {
@@ -198,14 +213,9 @@ struct Workspace {
     bool pair_pending = false;  // the begun launch is a pair (msm_pair_gather_begin): two result regions, msm_pair_end collects them
     bool begun = false;         // two-phase API: a begin without its end (also set for n == 0, where pend_W stays 0)
     // batched MSM (msm_batch_impl.hip.h): work list, the bucket blocks' partial + window sums, the entries' sums, counters +
-    // shapes, the host form's output; the pinned work list and the event of its upload (a call that finds that copy still queued
-    // retires the buffer -- freed once the copy is done -- and takes a new one); the fence orders the scratch between calls on
-    // different streams
+    // shapes, the host form's output; the pinned work list; the fence orders the scratch between calls on different streams
     Buf batch_list, batch_part, batch_sums, batch_ctrl, batch_out;
-    void* h_batch = nullptr;
-    size_t h_batch_cap = 0;
-    hipEvent_t batch_upload = nullptr;
-    std::vector<std::pair<void*, hipEvent_t>> batch_retired;
+    PinnedList batch_list_h;
     UseFence batch_fence;
 };
 // workspace slots per device -- 0: blocking calls, 1..3: the two-phase C ABI, 4..7: msm_host_multi's pipeline,

@@ -1,7 +1,7 @@
 // ICC encode launch logic + C ABI (include/porla_gpu.h: porla_icc_encode_device / _host).
 // Patch site in the reference (no function boundary exists there): Server::CRebuild_Cached,
 // porla/Server/Server.hpp:1544-1833; see INTEGRATION.md.
-#include "engine.hpp"
+#include "batch_host.hpp"
 #include "icc.hip.h"
 #include "icc30.hip.h"
 #include "icc30_split.hip.h"
@@ -25,20 +25,7 @@ struct IccWs {
     UseFence fence;   // work / twiddle buffers are shared between calls that may come on different streams
     std::mutex mu;    // one encode at a time per device (the column-range splitter runs one host thread per device)
 };
-static std::mutex g_icc_mu;    // the registry only
-static std::vector<IccWs*> g_icc_ws;
-
-static int get_icc_ws(IccWs** out) {
-    int dev = 0;
-    PORLA_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_icc_mu);
-    for (auto* w : g_icc_ws) if (w->device == dev) { *out = w; return PORLA_OK; }
-    IccWs* w = new IccWs();
-    w->device = dev;
-    g_icc_ws.push_back(w);
-    *out = w;
-    return PORLA_OK;
-}
+static PerDevice<IccWs> g_icc_ws;
 
 // twiddle table w^e, e < N (resident across calls with the same N and curve)
 template <class Q>
@@ -235,7 +222,7 @@ int icc_wt_residues(int curve, size_t n_total, unsigned long long write_step, ui
 }
 int icc_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** tw30) {
     IccWs* ws = nullptr;
-    int rc = get_icc_ws(&ws);
+    int rc = g_icc_ws.get(&ws);
     if (rc) return rc;
     ws->mu.lock();
     rc = curve == 0 ? icc_mix_tables<IccBn254Fr>(ws, 0, n_total, stream) : icc_mix_tables<IccSecp256k1Fn>(ws, 1, n_total, stream);
@@ -245,7 +232,7 @@ int icc_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const 
 }
 int icc_mix_tables_release(hipStream_t stream) {
     IccWs* ws = nullptr;
-    int rc = get_icc_ws(&ws);
+    int rc = g_icc_ws.get(&ws);
     if (rc) return rc;                       // (the workspace exists: acquire made it)
     rc = ws->fence.leave(stream);
     ws->mu.unlock();
@@ -266,7 +253,7 @@ int icc_network_matrix_device(int curve, size_t n, unsigned long long write_step
     int rc = ensure_device();
     if (rc) return rc;
     IccWs* ws;
-    if ((rc = get_icc_ws(&ws))) return rc;
+    if ((rc = g_icc_ws.get(&ws))) return rc;
     std::lock_guard<std::mutex> lk(ws->mu);
     if ((rc = ws->in.ensure(n * n * 32))) return rc;
     if ((rc = ws->fence.enter(stream))) return rc;
@@ -288,7 +275,7 @@ int porla_icc_encode_device(const void* d_rows_in, size_t n_rows, size_t n_cols,
     if (rc) return rc;
     if (!d_rows_in) { set_last_error("porla: null argument"); return PORLA_ERR_ARG; }
     IccWs* ws;
-    if ((rc = get_icc_ws(&ws))) return rc;
+    if ((rc = g_icc_ws.get(&ws))) return rc;
     std::lock_guard<std::mutex> lk(ws->mu);
     return icc_encode_dispatch(ws, curve, (const uint8_t*)d_rows_in, n_rows, n_cols, write_step, part, (uint8_t*)d_x_out,
                                (uint8_t*)d_aligned_out, (uint8_t*)d_scalars_out, scalar_le, (hipStream_t)stream);
@@ -301,7 +288,7 @@ int porla_icc_encode_xy_device(const void* d_rows_in, size_t n_rows, size_t n_co
     if (rc) return rc;
     if (!d_rows_in) { set_last_error("porla: null argument"); return PORLA_ERR_ARG; }
     IccWs* ws;
-    if ((rc = get_icc_ws(&ws))) return rc;
+    if ((rc = g_icc_ws.get(&ws))) return rc;
     std::lock_guard<std::mutex> lk(ws->mu);
     const IccOut oy{(uint8_t*)d_y_x_out, (uint8_t*)d_y_aligned_out, (uint8_t*)d_y_scalars_out, nullptr, scalar_le};
     return icc_encode_dispatch(ws, curve, (const uint8_t*)d_rows_in, n_rows, n_cols, write_step, 0, (uint8_t*)d_x_out,
@@ -317,7 +304,7 @@ static int icc_encode_cols_host(const uint8_t* rows_in, size_t n_rows, size_t n_
     if (rc) return rc;
     if (!rows_in || c0 >= c1 || c1 > n_cols) { set_last_error("porla: bad argument (null rows or empty / out-of-range column range)"); return PORLA_ERR_ARG; }
     IccWs* ws;
-    if ((rc = get_icc_ws(&ws))) return rc;
+    if ((rc = g_icc_ws.get(&ws))) return rc;
     std::lock_guard<std::mutex> lk(ws->mu);
     const size_t nc = c1 - c0, total = n_rows * nc;
     if ((rc = ws->in.ensure(total * 32))) return rc;
@@ -392,7 +379,7 @@ int porla_icc_hadd_host(const uint8_t* data_in, size_t n_cols, size_t n_total, u
         return PORLA_ERR_ARG;
     }
     IccWs* ws;
-    if ((rc = get_icc_ws(&ws))) return rc;
+    if ((rc = g_icc_ws.get(&ws))) return rc;
     std::lock_guard<std::mutex> lk(ws->mu);
     if ((rc = ws->in.ensure(n_cols * 32))) return rc;
     if ((rc = ws->al.ensure(n_cols * 32))) return rc;
@@ -463,7 +450,7 @@ int porla_icc_mix_device(const void* d_a0, const void* d_a1, size_t len, size_t 
         return PORLA_ERR_ARG;
     }
     IccWs* ws;
-    if ((rc = get_icc_ws(&ws))) return rc;
+    if ((rc = g_icc_ws.get(&ws))) return rc;
     std::lock_guard<std::mutex> lk(ws->mu);
     if (curve == 0) return icc_mix_core<IccBn254Fr>(ws, 0, (const uint8_t*)d_a0, (const uint8_t*)d_a1, len, n_cols, n_total, (uint8_t*)d_out, (hipStream_t)hip_stream);
     return icc_mix_core<IccSecp256k1Fn>(ws, 1, (const uint8_t*)d_a0, (const uint8_t*)d_a1, len, n_cols, n_total, (uint8_t*)d_out, (hipStream_t)hip_stream);

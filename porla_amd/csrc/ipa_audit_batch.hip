@@ -238,20 +238,7 @@ struct IpaBatchWs {
     PinnedList h_list;
     UseFence fence;
 };
-static std::mutex g_ipa_mu;
-static std::vector<IpaBatchWs*> g_ipa_ws;
-
-static int ipa_workspace(IpaBatchWs** out) {
-    int dev = 0;
-    PORLA_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_ipa_mu);
-    for (auto* w : g_ipa_ws) if (w->device == dev) { *out = w; return PORLA_OK; }
-    IpaBatchWs* w = new IpaBatchWs();
-    w->device = dev;
-    g_ipa_ws.push_back(w);
-    *out = w;
-    return PORLA_OK;
-}
+static PerDevice<IpaBatchWs> g_ipa_ws;
 
 // ws->mu held, ws->fence entered.  The k proofs of (a, b): a_src as k_ipa_open takes it, b from b_src or from a_values.
 static int prove_enqueue(IpaBatchWs* ws, FixedBase<Secp256k1G>& fb, size_t k, const uint8_t* a_src, size_t a_stride, const uint8_t* b_src,
@@ -284,77 +271,36 @@ static int prove_enqueue(IpaBatchWs* ws, FixedBase<Secp256k1G>& fb, size_t k, co
     return PORLA_OK;
 }
 
+// ws->mu held, ws->fence entered
 static int audit_enqueue(IpaBatchWs* ws, FixedBase<Secp256k1G>& fb, const porla_ipa_audit_req* reqs, size_t k, uint8_t* d_out,
                          uint8_t* d_b_out, hipStream_t stream) {
     int rc;
     const size_t n = IPA_N;
-    // ---- the plan, as the batched KZG audit's: combine blocks (the single call's rule over the batch's total rows), gather blocks,
-    // MSM offsets
-    uint64_t rows_total = 0;
-    for (size_t a = 0; a < k; a++) rows_total += reqs[a].n64 + reqs[a].n32;
-    const uint64_t spb = (uint64_t)AUDIT_BATCH_SLICES * 512;
-    uint64_t per_slice64 = (rows_total + spb - 1) / spb;
-    if (per_slice64 < 4) per_slice64 = 4;
-    if (per_slice64 > 0xffffffffull / AUDIT_BATCH_SLICES) per_slice64 = 0xffffffffull / AUDIT_BATCH_SLICES;
-    const uint32_t per_slice = (uint32_t)per_slice64, per_block = per_slice * AUDIT_BATCH_SLICES;
-    std::vector<KzgAuditDesc> desc(k);
-    std::vector<uint64_t> offsets(2 * k + 1);
-    uint64_t blocks = 0, gblocks = 0, pairs = 0;
-    for (size_t a = 0; a < k; a++) {
-        const porla_ipa_audit_req& R = reqs[a];
-        KzgAuditDesc& D = desc[a];
-        D.rows64 = (const uint8_t*)R.d_rows64; D.idx64 = R.d_idx64; D.coef64 = R.d_coef64;
-        D.rows32 = (const uint8_t*)R.d_rows32; D.idx32 = R.d_idx32; D.coef32 = R.d_coef32;
-        D.mac_store = (const uint8_t*)R.d_mac_store; D.align_store = (const uint8_t*)R.d_align_store;
-        D.mac_idx = R.d_mac_idx; D.mac_coef = R.d_mac_coef;
-        D.n64 = (uint32_t)R.n64; D.n32 = (uint32_t)R.n32; D.n_macs = (uint32_t)R.n_macs;
-        const uint64_t total = R.n64 + R.n32;
-        const uint64_t nb = total ? (total + per_block - 1) / per_block : 1;   // an empty challenge still writes B = 0
-        D.blk0 = (uint32_t)blocks; D.nblk = (uint32_t)nb;
-        D.gat0 = (uint32_t)gblocks;
-        D.z = 0;
-        D.pair0 = pairs;
-        blocks += nb;
-        gblocks += (R.n_macs + KZG_GATHER_PAIRS - 1) / KZG_GATHER_PAIRS;
-        offsets[2 * a] = pairs;
-        offsets[2 * a + 1] = pairs + R.n_macs;
-        pairs += 2 * (uint64_t)R.n_macs;
-    }
-    offsets[2 * k] = pairs;
-    if (blocks > 0xffffffffull || gblocks > 0xffffffffull) { set_last_error("porla: audit batch too large for one call"); return PORLA_ERR_ARG; }
-    size_t pt_b;
-    if (!mul_ok((size_t)pairs, 64, &pt_b)) { set_last_error("porla: audit batch byte size overflows"); return PORLA_ERR_ARG; }
-    const size_t sc_b = (size_t)pairs * 32, rows2_b = 2 * k * 32 * n;
-    const size_t part_b = audit_combine_partial_bytes((uint32_t)blocks, (uint32_t)n);
+    AuditPlan P;
+    if ((rc = audit_batch_plan(reqs, k, [](size_t) { return 0ull; }, &P))) return rc;
+    const uint64_t blocks = P.blocks, gblocks = P.gblocks;
     // ---- the work list: a_values | descriptors | combine block -> audit | gather block -> audit, one pinned buffer, one copy
-    const size_t av_b = 32 * k, desc_b = k * sizeof(KzgAuditDesc);
-    const size_t list_b = av_b + desc_b + 4 * (size_t)(blocks + gblocks);
+    const size_t av_b = 32 * k, list_b = av_b + P.list_bytes();
     if ((rc = ws->h_list.stage(list_b))) return rc;
     {
         uint8_t* h = (uint8_t*)ws->h_list.h;
         for (size_t a = 0; a < k; a++) memcpy(h + 32 * a, reqs[a].a_value, 32);
-        memcpy(h + av_b, desc.data(), desc_b);
-        uint32_t* bl = (uint32_t*)(h + av_b + desc_b);
-        uint32_t* gl = bl + blocks;
-        for (size_t a = 0; a < k; a++) {
-            for (uint32_t b = 0; b < desc[a].nblk; b++) *bl++ = (uint32_t)a;
-            for (uint32_t b = 0; b < (desc[a].n_macs + KZG_GATHER_PAIRS - 1) / KZG_GATHER_PAIRS; b++) *gl++ = (uint32_t)a;
-        }
+        P.write(h + av_b);
     }
     if ((rc = ws->list.ensure(list_b))) return rc;
-    if ((rc = ws->partial.ensure(part_b))) return rc;
-    if ((rc = ws->rows2.ensure(rows2_b))) return rc;
-    if ((rc = ws->msm_sc.ensure(sc_b + 64))) return rc;
-    if ((rc = ws->msm_pt.ensure(pt_b + 64))) return rc;
+    if ((rc = ws->partial.ensure(audit_combine_partial_bytes((uint32_t)blocks, (uint32_t)n)))) return rc;
+    if ((rc = ws->rows2.ensure(2 * k * 32 * n))) return rc;
+    if ((rc = ws->msm_sc.ensure((size_t)P.pairs * 32 + 64))) return rc;
+    if ((rc = ws->msm_pt.ensure((size_t)P.pairs * 64 + 64))) return rc;
     if ((rc = ws->msm_sums.ensure(2 * k * sizeof(XYZZ<Secp256k1Fp>)))) return rc;
     if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
     const uint8_t* d_av = (const uint8_t*)ws->list.p;
     const KzgAuditDesc* d_desc = (const KzgAuditDesc*)(d_av + av_b);
-    const uint32_t* d_blk = (const uint32_t*)(d_av + av_b + desc_b);
+    const uint32_t* d_blk = (const uint32_t*)(d_av + av_b + P.desc_bytes());
     const uint32_t* d_gat = d_blk + blocks;
     uint8_t* rows2 = (uint8_t*)ws->rows2.p;
     // ---- 1. the row combine: c_k (mod n) and B_k into the rows [c_k, B_k]
-    if ((rc = audit_combine_batch_launch(d_desc, d_blk, (uint32_t)blocks, (uint32_t)k, (uint32_t)n, per_slice, ws->partial.p, 1, rows2,
+    if ((rc = audit_combine_batch_launch(d_desc, d_blk, (uint32_t)blocks, (uint32_t)k, (uint32_t)n, P.per_slice, ws->partial.p, 1, rows2,
                                          rows2 + 32 * n, 2 * 32 * n, stream)))
         return rc;
     // ---- 2. the MSM pairs: gather, then the batched MSM over the 2K entries, sums left projective
@@ -365,7 +311,7 @@ static int audit_enqueue(IpaBatchWs* ws, FixedBase<Secp256k1G>& fb, const porla_
         PORLA_HIP(hipGetLastError());
     }
     XYZZ<Secp256k1Fp>* msm_sums = (XYZZ<Secp256k1Fp>*)ws->msm_sums.p;
-    if ((rc = msm_batch_sums_device<Secp256k1G>((const uint8_t*)ws->msm_sc.p, (const uint8_t*)ws->msm_pt.p, offsets.data(), 2 * k, msm_sums,
+    if ((rc = msm_batch_sums_device<Secp256k1G>((const uint8_t*)ws->msm_sc.p, (const uint8_t*)ws->msm_pt.p, P.offsets.data(), 2 * k, msm_sums,
                                                 stream)))
         return rc;
     // ---- 3. the 2K Pedersen commitments and the record's points: the prover's first pass overwrites these sums
@@ -397,57 +343,41 @@ static_assert(offsetof(porla_ipa_audit_req, d_rows64) == 0 && offsetof(porla_ipa
 extern "C" int porla_ipa_audit_batch_device(porla_fixed_base* gens_u_fb, const porla_ipa_audit_req* reqs, size_t k, void* d_out,
                                             void* d_b_out, void* hip_stream) {
     static const char* who = "porla_ipa_audit_batch_device";
-    auto bad = [](const char* what) { set_last_error(std::string(who) + ": " + what); return PORLA_ERR_ARG; };
-    if (k && (!reqs || !d_out || !gens_u_fb)) return bad("reqs, d_out or gens_u_fb is NULL");
+    if (k && (!reqs || !d_out || !gens_u_fb)) return bad_arg(who, "reqs, d_out or gens_u_fb is NULL");
     size_t out_b;
-    if (!mul_ok(k, IPA_RECORD, &out_b)) return bad("k records overflow a byte size");
+    if (!mul_ok(k, IPA_RECORD, &out_b)) return bad_arg(who, "k records overflow a byte size");
     uint64_t pairs = 0;
-    for (size_t a = 0; a < k; a++) {
-        const porla_ipa_audit_req& R = reqs[a];
-        if (R.n64 && (!R.d_rows64 || !R.d_idx64 || !R.d_coef64)) return bad("a NULL 64-byte-row array with n64 > 0");
-        if (R.n32 && (!R.d_rows32 || !R.d_idx32 || !R.d_coef32)) return bad("a NULL 32-byte-row array with n32 > 0");
-        if (R.n_macs && (!R.d_mac_store || !R.d_align_store || !R.d_mac_idx || !R.d_mac_coef)) return bad("a NULL MAC array with n_macs > 0");
-        if (R.n_macs > IPA_AUDIT_MAX_MACS) return bad("n_macs > 32768 (the batched MSM's entry limit; use porla_ipa_audit_device)");
-        if (R.n64 >= (1ull << 32) || R.n32 >= (1ull << 32) || R.n64 + R.n32 >= (1ull << 32)) return bad("n64 + n32 >= 2^32");
-        pairs += 2 * (uint64_t)R.n_macs;
-    }
+    int rc = audit_batch_check(who, "porla_ipa_audit_device", reqs, k, &pairs);
+    if (rc) return rc;
     size_t b;
     if (!mul_ok(k, (size_t)ST_WORDS * 4 + 2 * IPA_ROW_COEFFS * 32 + 3 * 32 * IPA_N, &b) || !mul_ok((size_t)pairs, 96, &b))
-        return bad("the batch's byte size overflows");
+        return bad_arg(who, "the batch's byte size overflows");
     if (k == 0) return PORLA_OK;
-    int rc = ensure_device();
-    if (rc) return rc;
+    if ((rc = ensure_device())) return rc;
     if ((rc = ipa_check_base(gens_u_fb, who))) return rc;
     IpaBatchWs* ws = nullptr;
-    if ((rc = ipa_workspace(&ws))) return rc;
-    std::lock_guard<std::mutex> lk(ws->mu);
+    if ((rc = g_ipa_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if ((rc = ws->fence.enter(stream))) return rc;
-    rc = audit_enqueue(ws, gens_u_fb->secp, reqs, k, (uint8_t*)d_out, (uint8_t*)d_b_out, stream);
-    // the buffers of this call are behind the fence on every exit, a failing one included
-    const int rf = ws->fence.leave(stream);
-    return rc ? rc : rf;
+    return FencedCall(ws, stream).run(
+        [&] { return audit_enqueue(ws, gens_u_fb->secp, reqs, k, (uint8_t*)d_out, (uint8_t*)d_b_out, stream); });
 }
 
 extern "C" int porla_ipa_prove_batch_device(porla_fixed_base* gens_u_fb, const void* d_a, const void* d_b, size_t k, void* d_proofs,
                                             void* hip_stream) {
     static const char* who = "porla_ipa_prove_batch_device";
-    auto bad = [](const char* what) { set_last_error(std::string(who) + ": " + what); return PORLA_ERR_ARG; };
-    if (k && (!gens_u_fb || !d_a || !d_b || !d_proofs)) return bad("gens_u_fb, d_a, d_b or d_proofs is NULL");
+    if (k && (!gens_u_fb || !d_a || !d_b || !d_proofs)) return bad_arg(who, "gens_u_fb, d_a, d_b or d_proofs is NULL");
     size_t b;
-    if (!mul_ok(k, (size_t)ST_WORDS * 4 + 2 * IPA_ROW_COEFFS * 32, &b)) return bad("k proofs overflow a byte size");
-    if (k > 0x7fffffffu) return bad("more than 2^31 - 1 proofs in one call");
+    if (!mul_ok(k, (size_t)ST_WORDS * 4 + 2 * IPA_ROW_COEFFS * 32, &b)) return bad_arg(who, "k proofs overflow a byte size");
+    if (k > 0x7fffffffu) return bad_arg(who, "more than 2^31 - 1 proofs in one call");
     if (k == 0) return PORLA_OK;
     int rc = ensure_device();
     if (rc) return rc;
     if ((rc = ipa_check_base(gens_u_fb, who))) return rc;
     IpaBatchWs* ws = nullptr;
-    if ((rc = ipa_workspace(&ws))) return rc;
-    std::lock_guard<std::mutex> lk(ws->mu);
+    if ((rc = g_ipa_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if ((rc = ws->fence.enter(stream))) return rc;
-    rc = prove_enqueue(ws, gens_u_fb->secp, k, (const uint8_t*)d_a, 32 * IPA_N, (const uint8_t*)d_b, nullptr, (uint8_t*)d_proofs, IPA_PROOF,
-                       nullptr, stream);
-    const int rf = ws->fence.leave(stream);
-    return rc ? rc : rf;
+    return FencedCall(ws, stream).run([&] {
+        return prove_enqueue(ws, gens_u_fb->secp, k, (const uint8_t*)d_a, 32 * IPA_N, (const uint8_t*)d_b, nullptr, (uint8_t*)d_proofs, IPA_PROOF,
+                             nullptr, stream);
+    });
 }

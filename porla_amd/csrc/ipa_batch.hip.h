@@ -1,6 +1,6 @@
 // Pieces the batched IPA audit (ipa_audit_batch.hip) and the batched IPA verifier (ipa_verify_batch.hip) share: the record's layout,
-// the transcript's compression function, the arithmetic mod n of a block of 128 lanes, and the host helpers around the generators'
-// fixed base.
+// the transcript's compression function, the arithmetic mod n of a block of 128 lanes, and the check of the generators' fixed base
+// (the host scaffold of the calls is batch_host.hpp's).
 #pragma once
 #include "engine.hpp"
 #include "icc.hip.h"
@@ -18,7 +18,6 @@ constexpr size_t IPA_PROOF = PORLA_IPA_PROOF_BYTES;
 constexpr uint32_t IPA_N = 128;                    // NUM_CHUNKS: the prover's index pattern is written for it
 constexpr uint32_t IPA_ROUNDS = 6;                 // half_width = 64 .. 2
 constexpr uint32_t IPA_ROW_COEFFS = IPA_N + 1;     // the generators' coefficients, then u's
-constexpr uint32_t IPA_AUDIT_MAX_MACS = 32768;     // the batched MSM's entry limit (SMALL_MAX_N)
 static_assert(IPA_PROOF == 32 + IPA_ROUNDS * 66 + 128 && IPA_RECORD == 99 + IPA_PROOF, "the reply of Server.hpp:856, :880-892");
 
 using Fn = IccSecp256k1Fn;
@@ -91,20 +90,6 @@ __device__ __forceinline__ Fe<Fn> load_scalar_mont(const uint8_t* src) {
     fe_reduce_plain<Fn>(f.v, Fn::MAX_Q_IN);
     return fe_to_mont<Fn>(f);
 }
-
-// one commitment pass over n_rows contiguous rows of n_coeffs coefficients, sums left projective in the table's partials, and
-// `then(sums, S)` (row r at sums[r S]) enqueued under the table's lock before its fence is recorded again: the partials hold only the
-// LAST pass's sums, and another caller's pass may follow as soon as the lock is let go
-template <class Then>
-static int commit_then(FixedBase<Secp256k1G>& fb, const uint8_t* d_rows, size_t n_rows, size_t n_coeffs, hipStream_t stream, Then then) {
-    std::lock_guard<std::mutex> lk(fb.mu);
-    int rc;
-    if ((rc = fb.commit_device(d_rows, n_rows, n_coeffs, 32 * n_coeffs, nullptr, stream))) return rc;
-    if ((rc = then((const XYZZ<Secp256k1Fp>*)fb.partial, fb.last_S))) return rc;
-    return fb.fence.leave(stream);
-}
-
-static inline bool mul_ok(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
 
 // the fixed base of an IPA batch call: secp256k1, the 128 generators and u.  (A handle exists only where a device does, so this comes
 // after ensure_device: without a device every non-NULL handle is refused as PORLA_ERR_NO_DEVICE before it is read.)

@@ -290,8 +290,7 @@ struct IpaVerifyWs {
     PinnedList h_list;
     UseFence fence;
 };
-static std::mutex g_ivb_mu;
-static std::vector<IpaVerifyWs*> g_ivb_ws;
+static PerDevice<IpaVerifyWs> g_ivb_ws;
 
 // ws->mu held, ws->fence entered.  Every buffer is sized before the first launch, so a k whose buffers cannot exist fails there.
 static int verify_enqueue(IpaVerifyWs* ws, FixedBase<Secp256k1G>& fb, const porla_ipa_verify_req* reqs, size_t k, const uint8_t* d_records,
@@ -322,7 +321,7 @@ static int verify_enqueue(IpaVerifyWs* ws, FixedBase<Secp256k1G>& fb, const porl
         offsets[3 * a + 1] = pairs + R.n;
         offsets[3 * a + 2] = pairs + R.n + 3;
         pairs += R.n + IPA_VERIFY_PAIRS;
-        gblocks += (R.n + KZG_GATHER_PAIRS - 1) / KZG_GATHER_PAIRS;
+        gblocks += gather_blocks(R.n);
     }
     offsets[3 * k] = pairs;
     if (gblocks > 0xffffffffull) { set_last_error("porla: verify batch too large for one call"); return PORLA_ERR_ARG; }
@@ -333,9 +332,7 @@ static int verify_enqueue(IpaVerifyWs* ws, FixedBase<Secp256k1G>& fb, const porl
     {
         uint8_t* h = (uint8_t*)ws->h_list.h;
         memcpy(h, desc.data(), desc_b);
-        uint32_t* gl = (uint32_t*)(h + desc_b);
-        for (size_t a = 0; a < k; a++)
-            for (uint32_t b = 0; b < (desc[a].n + KZG_GATHER_PAIRS - 1) / KZG_GATHER_PAIRS; b++) *gl++ = (uint32_t)a;
+        fill_owner_list((uint32_t*)(h + desc_b), k, [&](size_t a) { return gather_blocks(desc[a].n); });
     }
     if ((rc = ws->list.ensure(list_b))) return rc;
     if ((rc = ws->msm_sc.ensure((size_t)pairs * 32 + 64))) return rc;
@@ -384,37 +381,26 @@ static_assert(offsetof(porla_ipa_verify_req, d_comp_store) == 0 && offsetof(porl
 extern "C" int porla_ipa_verify_batch_device(porla_fixed_base* gens_u_fb, const porla_ipa_verify_req* reqs, size_t k, const void* d_records,
                                              uint8_t* d_status, void* hip_stream) {
     static const char* who = "porla_ipa_verify_batch_device";
-    auto bad = [](const char* what) { set_last_error(std::string(who) + ": " + what); return PORLA_ERR_ARG; };
-    if (k && (!reqs || !d_records || !d_status || !gens_u_fb)) return bad("reqs, d_records, d_status or gens_u_fb is NULL");
+    if (k && (!reqs || !d_records || !d_status || !gens_u_fb)) return bad_arg(who, "reqs, d_records, d_status or gens_u_fb is NULL");
     size_t bytes;
     if (!mul_ok(k, IPA_RECORD + (size_t)IPA_ROW_COEFFS * 32 + 3 * sizeof(XYZZ<Secp256k1Fp>) + sizeof(IpaVerifyDesc) + 96 * IPA_VERIFY_PAIRS,
                 &bytes))
-        return bad("k replies overflow a byte size");
+        return bad_arg(who, "k replies overflow a byte size");
     uint64_t pairs = 0;
     for (size_t a = 0; a < k; a++) {
         const porla_ipa_verify_req& R = reqs[a];
-        if (R.n && (!R.d_comp_store || !R.d_idx || !R.d_coef)) return bad("a NULL complement or challenge array with n > 0");
-        if (R.n > IPA_VERIFY_MAX_N) return bad("n > 32768 (the batched MSM's entry limit)");
+        if (R.n && (!R.d_comp_store || !R.d_idx || !R.d_coef)) return bad_arg(who, "a NULL complement or challenge array with n > 0");
+        if (R.n > IPA_VERIFY_MAX_N) return bad_arg(who, "n > 32768 (the batched MSM's entry limit)");
         pairs += R.n + IPA_VERIFY_PAIRS;
     }
-    if (!mul_ok((size_t)pairs, 96, &bytes)) return bad("the batch's byte size overflows");
+    if (!mul_ok((size_t)pairs, 96, &bytes)) return bad_arg(who, "the batch's byte size overflows");
     if (k == 0) return PORLA_OK;
     int rc = ensure_device();
     if (rc) return rc;
     if ((rc = ipa_check_base(gens_u_fb, who))) return rc;
-    int dev = 0;
-    PORLA_HIP(hipGetDevice(&dev));
     IpaVerifyWs* ws = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_ivb_mu);
-        for (auto* w : g_ivb_ws) if (w->device == dev) ws = w;
-        if (!ws) { ws = new IpaVerifyWs(); ws->device = dev; g_ivb_ws.push_back(ws); }
-    }
-    std::lock_guard<std::mutex> lk(ws->mu);
+    if ((rc = g_ivb_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    if ((rc = ws->fence.enter(stream))) return rc;
-    rc = verify_enqueue(ws, gens_u_fb->secp, reqs, k, (const uint8_t*)d_records, d_status, stream);
-    // the buffers of this call are behind the fence on every exit, a failing one included
-    const int rf = ws->fence.leave(stream);
-    return rc ? rc : rf;
+    return FencedCall(ws, stream).run(
+        [&] { return verify_enqueue(ws, gens_u_fb->secp, reqs, k, (const uint8_t*)d_records, d_status, stream); });
 }

@@ -25,7 +25,6 @@
 namespace porla {
 
 constexpr size_t KZG_AUDIT_RECORD = PORLA_KZG_AUDIT_RECORD_BYTES;
-constexpr uint32_t KZG_AUDIT_MAX_MACS = 32768;     // the batched MSM's entry limit (SMALL_MAX_N)
 constexpr uint32_t KZG_OPEN_WAVES = 4;             // audits per block of k_kzg_open
 
 // ---- the KZG opening, a wave per audit.  f = B_k reduced mod r (fr.SetBytes), n >= 1 coefficients.  C_j = sum_{i >= j} f_i z^(i-j)
@@ -140,8 +139,7 @@ struct KzgAuditBatchWs {
     PinnedList h_list;
     UseFence fence;
 };
-static std::mutex g_kab_mu;
-static std::vector<KzgAuditBatchWs*> g_kab_ws;
+static PerDevice<KzgAuditBatchWs> g_kab_ws;
 
 struct JoinArgs { const XYZZ<Bn254Fp>* msm; uint32_t k; uint8_t* out; hipStream_t stream; };
 static int launch_join(const XYZZ<Bn254Fp>* sums, uint32_t S, void* ctx) {
@@ -152,79 +150,32 @@ static int launch_join(const XYZZ<Bn254Fp>* sums, uint32_t S, void* ctx) {
     return PORLA_OK;
 }
 
-static bool mul_ok(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
-
+// ws->mu held, ws->fence entered
 static int audit_batch_enqueue(KzgAuditBatchWs* ws, const porla_kzg_audit_req* reqs, size_t k, size_t n, uint8_t* d_out, uint8_t* d_b_out,
                                hipStream_t stream) {
     int rc;
-    // ---- the plan: combine blocks (the single call's rule over the batch's total rows), gather blocks, MSM offsets
-    uint64_t rows_total = 0;
-    for (size_t a = 0; a < k; a++) rows_total += reqs[a].n64 + reqs[a].n32;
-    const uint64_t spb = (uint64_t)AUDIT_BATCH_SLICES * 512;
-    uint64_t per_slice64 = (rows_total + spb - 1) / spb;
-    if (per_slice64 < 4) per_slice64 = 4;
-    if (per_slice64 > 0xffffffffull / AUDIT_BATCH_SLICES) per_slice64 = 0xffffffffull / AUDIT_BATCH_SLICES;
-    const uint32_t per_slice = (uint32_t)per_slice64, per_block = per_slice * AUDIT_BATCH_SLICES;
-    std::vector<KzgAuditDesc> desc(k);
-    std::vector<uint64_t> offsets(2 * k + 1);
-    uint64_t blocks = 0, gblocks = 0, pairs = 0;
-    for (size_t a = 0; a < k; a++) {
-        const porla_kzg_audit_req& R = reqs[a];
-        KzgAuditDesc& D = desc[a];
-        D.rows64 = (const uint8_t*)R.d_rows64; D.idx64 = R.d_idx64; D.coef64 = R.d_coef64;
-        D.rows32 = (const uint8_t*)R.d_rows32; D.idx32 = R.d_idx32; D.coef32 = R.d_coef32;
-        D.mac_store = (const uint8_t*)R.d_mac_store; D.align_store = (const uint8_t*)R.d_align_store;
-        D.mac_idx = R.d_mac_idx; D.mac_coef = R.d_mac_coef;
-        D.n64 = (uint32_t)R.n64; D.n32 = (uint32_t)R.n32; D.n_macs = (uint32_t)R.n_macs;
-        const uint64_t total = R.n64 + R.n32;
-        const uint64_t nb = total ? (total + per_block - 1) / per_block : 1;   // an empty challenge still writes B = 0
-        D.blk0 = (uint32_t)blocks; D.nblk = (uint32_t)nb;
-        D.gat0 = (uint32_t)gblocks;
-        D.z = R.random_point;
-        D.pair0 = pairs;
-        blocks += nb;
-        gblocks += (R.n_macs + KZG_GATHER_PAIRS - 1) / KZG_GATHER_PAIRS;
-        offsets[2 * a] = pairs;
-        offsets[2 * a + 1] = pairs + R.n_macs;
-        pairs += 2 * (uint64_t)R.n_macs;
-    }
-    offsets[2 * k] = pairs;
-    if (blocks > 0xffffffffull || gblocks > 0xffffffffull) { set_last_error("porla: audit batch too large for one call"); return PORLA_ERR_ARG; }
-    size_t rows3_b, part_b, sc_b, pt_b;
-    if (!mul_ok(3 * k, 32 * n, &rows3_b) || !mul_ok((size_t)pairs, 64, &pt_b)) {
-        set_last_error("porla: audit batch byte size overflows");
-        return PORLA_ERR_ARG;
-    }
-    sc_b = (size_t)pairs * 32;
-    part_b = audit_combine_partial_bytes((uint32_t)blocks, (uint32_t)n);
+    AuditPlan P;
+    if ((rc = audit_batch_plan(reqs, k, [&](size_t a) { return reqs[a].random_point; }, &P))) return rc;
+    size_t rows3_b;
+    if (!mul_ok(3 * k, 32 * n, &rows3_b)) { set_last_error("porla: audit batch byte size overflows"); return PORLA_ERR_ARG; }
+    const uint64_t blocks = P.blocks, gblocks = P.gblocks;
     // ---- the work list: descriptors | combine block -> audit | gather block -> audit, one pinned buffer, one copy
-    const size_t desc_b = k * sizeof(KzgAuditDesc);
-    const size_t list_b = desc_b + 4 * (size_t)(blocks + gblocks);
+    const size_t list_b = P.list_bytes();
     if ((rc = ws->h_list.stage(list_b))) return rc;
-    {
-        uint8_t* h = (uint8_t*)ws->h_list.h;
-        memcpy(h, desc.data(), desc_b);
-        uint32_t* bl = (uint32_t*)(h + desc_b);
-        uint32_t* gl = bl + blocks;
-        for (size_t a = 0; a < k; a++) {
-            for (uint32_t b = 0; b < desc[a].nblk; b++) *bl++ = (uint32_t)a;
-            for (uint32_t b = 0; b < (desc[a].n_macs + KZG_GATHER_PAIRS - 1) / KZG_GATHER_PAIRS; b++) *gl++ = (uint32_t)a;
-        }
-    }
+    P.write((uint8_t*)ws->h_list.h);
     if ((rc = ws->list.ensure(list_b))) return rc;
-    if ((rc = ws->partial.ensure(part_b))) return rc;
+    if ((rc = ws->partial.ensure(audit_combine_partial_bytes((uint32_t)blocks, (uint32_t)n)))) return rc;
     if ((rc = ws->rows3.ensure(rows3_b))) return rc;
-    if ((rc = ws->msm_sc.ensure(sc_b + 64))) return rc;
-    if ((rc = ws->msm_pt.ensure(pt_b + 64))) return rc;
+    if ((rc = ws->msm_sc.ensure((size_t)P.pairs * 32 + 64))) return rc;
+    if ((rc = ws->msm_pt.ensure((size_t)P.pairs * 64 + 64))) return rc;
     if ((rc = ws->msm_sums.ensure(2 * k * sizeof(XYZZ<Bn254Fp>)))) return rc;
-    if ((rc = ws->fence.enter(stream))) return rc;
     if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
     const KzgAuditDesc* d_desc = (const KzgAuditDesc*)ws->list.p;
-    const uint32_t* d_blk = (const uint32_t*)((const uint8_t*)ws->list.p + desc_b);
+    const uint32_t* d_blk = (const uint32_t*)((const uint8_t*)ws->list.p + P.desc_bytes());
     const uint32_t* d_gat = d_blk + blocks;
     uint8_t* rows3 = (uint8_t*)ws->rows3.p;
     // ---- 1. the row combine: c_k and B_k into the commit rows
-    if ((rc = audit_combine_batch_launch(d_desc, d_blk, (uint32_t)blocks, (uint32_t)k, (uint32_t)n, per_slice, ws->partial.p, 0, rows3,
+    if ((rc = audit_combine_batch_launch(d_desc, d_blk, (uint32_t)blocks, (uint32_t)k, (uint32_t)n, P.per_slice, ws->partial.p, 0, rows3,
                                          rows3 + 32 * n, 3 * 32 * n, stream)))
         return rc;
     // ---- 2. the opening: h_k, point, claim (and B into d_b_out)
@@ -242,7 +193,7 @@ static int audit_batch_enqueue(KzgAuditBatchWs* ws, const porla_kzg_audit_req* r
         PORLA_HIP(hipGetLastError());
     }
     XYZZ<Bn254Fp>* msm_sums = (XYZZ<Bn254Fp>*)ws->msm_sums.p;
-    if ((rc = msm_batch_sums_device<Bn254G1>((const uint8_t*)ws->msm_sc.p, (const uint8_t*)ws->msm_pt.p, offsets.data(), 2 * k, msm_sums, stream)))
+    if ((rc = msm_batch_sums_device<Bn254G1>((const uint8_t*)ws->msm_sc.p, (const uint8_t*)ws->msm_pt.p, P.offsets.data(), 2 * k, msm_sums, stream)))
         return rc;
     // ---- 4. the 3K commitments, then 5. the join into the records
     JoinArgs j = {msm_sums, (uint32_t)k, d_out, stream};
@@ -264,41 +215,23 @@ static_assert(offsetof(porla_kzg_audit_req, d_rows64) == 0 && offsetof(porla_kzg
               "porla_kzg_audit_req offsets (include/porla_gpu.h)");
 
 extern "C" int porla_kzg_audit_batch_device(const porla_kzg_audit_req* reqs, size_t k, void* d_out, void* d_b_out, void* hip_stream) {
-    auto bad = [](const char* what) { set_last_error(std::string("porla_kzg_audit_batch_device: ") + what); return PORLA_ERR_ARG; };
-    if (k && (!reqs || !d_out)) return bad("reqs or d_out is NULL");
+    static const char* who = "porla_kzg_audit_batch_device";
+    if (k && (!reqs || !d_out)) return bad_arg(who, "reqs or d_out is NULL");
     size_t out_b;
-    if (!mul_ok(k, KZG_AUDIT_RECORD, &out_b)) return bad("k records overflow a byte size");
+    if (!mul_ok(k, KZG_AUDIT_RECORD, &out_b)) return bad_arg(who, "k records overflow a byte size");
     uint64_t pairs = 0;
-    for (size_t a = 0; a < k; a++) {
-        const porla_kzg_audit_req& R = reqs[a];
-        if (R.n64 && (!R.d_rows64 || !R.d_idx64 || !R.d_coef64)) return bad("a NULL 64-byte-row array with n64 > 0");
-        if (R.n32 && (!R.d_rows32 || !R.d_idx32 || !R.d_coef32)) return bad("a NULL 32-byte-row array with n32 > 0");
-        if (R.n_macs && (!R.d_mac_store || !R.d_align_store || !R.d_mac_idx || !R.d_mac_coef)) return bad("a NULL MAC array with n_macs > 0");
-        if (R.n_macs > KZG_AUDIT_MAX_MACS) return bad("n_macs > 32768 (the batched MSM's entry limit; use porla_kzg_audit_device)");
-        if (R.n64 >= (1ull << 32) || R.n32 >= (1ull << 32) || R.n64 + R.n32 >= (1ull << 32)) return bad("n64 + n32 >= 2^32");
-        pairs += 2 * (uint64_t)R.n_macs;
-    }
-    size_t pt_b;
-    if (!mul_ok(k, 3 * 32 * 65536, &pt_b) || !mul_ok((size_t)pairs, 96, &pt_b)) return bad("the batch's byte size overflows");
-    if (k == 0) return PORLA_OK;
-    int rc = ensure_device();
+    int rc = audit_batch_check(who, "porla_kzg_audit_device", reqs, k, &pairs);
     if (rc) return rc;
+    size_t pt_b;
+    if (!mul_ok(k, 3 * 32 * 65536, &pt_b) || !mul_ok((size_t)pairs, 96, &pt_b)) return bad_arg(who, "the batch's byte size overflows");
+    if (k == 0) return PORLA_OK;
+    if ((rc = ensure_device())) return rc;
     size_t n = 0;
     if ((rc = porla_kzg_row_coefficients(&n))) return rc;
     if (n == 0) { set_last_error("porla: SRS not initialised (call init_SRS / init_SRS_from_data first)"); return PORLA_ERR_STATE; }
     if (n > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
-    int dev = 0;
-    PORLA_HIP(hipGetDevice(&dev));
     KzgAuditBatchWs* ws = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_kab_mu);
-        for (auto* w : g_kab_ws) if (w->device == dev) ws = w;
-        if (!ws) { ws = new KzgAuditBatchWs(); ws->device = dev; g_kab_ws.push_back(ws); }
-    }
-    std::lock_guard<std::mutex> lk(ws->mu);
+    if ((rc = g_kab_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    rc = audit_batch_enqueue(ws, reqs, k, n, (uint8_t*)d_out, (uint8_t*)d_b_out, stream);
-    // the buffers of this call are behind the fence on every exit, a failing one included
-    const int rf = ws->fence.leave(stream);
-    return rc ? rc : rf;
+    return FencedCall(ws, stream).run([&] { return audit_batch_enqueue(ws, reqs, k, n, (uint8_t*)d_out, (uint8_t*)d_b_out, stream); });
 }

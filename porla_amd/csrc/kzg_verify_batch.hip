@@ -145,27 +145,15 @@ struct KzgVerifyBatchWs {
     std::mutex mu;
     int device = -1;
     Buf list, msm_sc, msm_pt, msm_sums, out;
-    void* h_list = nullptr;
-    size_t h_list_cap = 0;
+    PinnedList h_list;
     void* h_out = nullptr;
     size_t h_out_cap = 0;
     hipEvent_t done = nullptr;
     UseFence fence;
 };
-static std::mutex g_kvb_mu;
-static std::vector<KzgVerifyBatchWs*> g_kvb_ws;
+static PerDevice<KzgVerifyBatchWs> g_kvb_ws;
 
-static int pinned(void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return PORLA_OK;
-    if (*p) PORLA_HIP(hipHostFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    PORLA_HIP(hipHostMalloc(p, bytes + bytes / 4 + 4096, hipHostMallocDefault));
-    *cap = bytes + bytes / 4 + 4096;
-    return PORLA_OK;
-}
-
-// ws->mu held: everything up to the copy back of P | Q | flags into ws->h_out, then ws->done recorded
+// ws->mu held, ws->fence entered: everything up to the copy back of P | Q | flags into ws->h_out, then ws->done recorded
 static int verify_batch_enqueue(KzgVerifyBatchWs* ws, const porla_kzg_verify_req* reqs, size_t k, const uint8_t* d_records,
                                 const uint8_t* weights, const uint8_t g_be[64], hipStream_t stream) {
     int rc;
@@ -189,7 +177,7 @@ static int verify_batch_enqueue(KzgVerifyBatchWs* ws, const porla_kzg_verify_req
         offsets[2 * a] = pairs;
         offsets[2 * a + 1] = pairs + R.n;
         pairs += R.n + 3;
-        gblocks += (R.n + KZG_GATHER_PAIRS - 1) / KZG_GATHER_PAIRS;
+        gblocks += gather_blocks(R.n);
     }
     const uint64_t p0 = pairs, q0 = p0 + 3 * (uint64_t)k;
     offsets[2 * k] = p0;
@@ -200,15 +188,19 @@ static int verify_batch_enqueue(KzgVerifyBatchWs* ws, const porla_kzg_verify_req
     const size_t desc_b = (k * sizeof(KzgVerifyDesc) + 63) & ~(size_t)63;    // G 16-byte aligned for its uint4 loads
     const size_t list_b = desc_b + 64 + 4 * (size_t)gblocks;
     const size_t out_b = 128 + k;
-    if ((rc = pinned(&ws->h_list, &ws->h_list_cap, list_b))) return rc;
-    if ((rc = pinned(&ws->h_out, &ws->h_out_cap, out_b))) return rc;
+    if ((rc = ws->h_list.stage(list_b))) return rc;
+    if (ws->h_out_cap < out_b) {           // read only after this call's own `done`
+        if (ws->h_out) PORLA_HIP(hipHostFree(ws->h_out));
+        ws->h_out = nullptr;
+        ws->h_out_cap = 0;
+        PORLA_HIP(hipHostMalloc(&ws->h_out, out_b + out_b / 4 + 4096, hipHostMallocDefault));
+        ws->h_out_cap = out_b + out_b / 4 + 4096;
+    }
     {
-        uint8_t* h = (uint8_t*)ws->h_list;
+        uint8_t* h = (uint8_t*)ws->h_list.h;
         memcpy(h, desc.data(), k * sizeof(KzgVerifyDesc));
         memcpy(h + desc_b, g_be, 64);
-        uint32_t* gl = (uint32_t*)(h + desc_b + 64);
-        for (size_t a = 0; a < k; a++)
-            for (uint32_t b = 0; b < (desc[a].n + KZG_GATHER_PAIRS - 1) / KZG_GATHER_PAIRS; b++) *gl++ = (uint32_t)a;
+        fill_owner_list((uint32_t*)(h + desc_b + 64), k, [&](size_t a) { return gather_blocks(desc[a].n); });
     }
     if ((rc = ws->list.ensure(list_b))) return rc;
     if ((rc = ws->msm_sc.ensure((size_t)pairs * 32 + 64))) return rc;
@@ -216,8 +208,7 @@ static int verify_batch_enqueue(KzgVerifyBatchWs* ws, const porla_kzg_verify_req
     if ((rc = ws->msm_sums.ensure((2 * k + 2) * sizeof(XYZZ<Bn254Fp>)))) return rc;
     if ((rc = ws->out.ensure(out_b))) return rc;
     if (!ws->done) PORLA_HIP(hipEventCreateWithFlags(&ws->done, hipEventDisableTiming));
-    if ((rc = ws->fence.enter(stream))) return rc;
-    PORLA_HIP(hipMemcpyAsync(ws->list.p, ws->h_list, list_b, hipMemcpyHostToDevice, stream));
+    if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
     const KzgVerifyDesc* d_desc = (const KzgVerifyDesc*)ws->list.p;
     const uint8_t* d_g = (const uint8_t*)ws->list.p + desc_b;
     const uint32_t* d_gat = (const uint32_t*)(d_g + 64);
@@ -247,8 +238,6 @@ static int verify_batch_enqueue(KzgVerifyBatchWs* ws, const porla_kzg_verify_req
     PORLA_HIP(hipEventRecord(ws->done, stream));
     return PORLA_OK;
 }
-
-static bool mul_ok(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
 
 // k x 16 bytes from the operating system's random source, every weight nonzero
 static int draw_weights(uint8_t* w, size_t k) {
@@ -281,20 +270,20 @@ static_assert(3 * PORLA_KZG_VERIFY_MAX_K <= KZG_VERIFY_MAX_N && 3 * (PORLA_KZG_V
 
 extern "C" int porla_kzg_verify_batch_device(const porla_kzg_verify_req* reqs, size_t k, const void* d_records, const uint8_t* weights,
                                              uint8_t* status, void* hip_stream) {
-    auto bad = [](const char* what) { set_last_error(std::string("porla_kzg_verify_batch_device: ") + what); return PORLA_ERR_ARG; };
-    if (k && (!reqs || !d_records || !status)) return bad("reqs, d_records or status is NULL");
-    if (k > PORLA_KZG_VERIFY_MAX_K) return bad("k > 10922 (the folded entry P holds 3 pairs per reply, at most 32768): split the batch");
+    static const char* who = "porla_kzg_verify_batch_device";
+    if (k && (!reqs || !d_records || !status)) return bad_arg(who, "reqs, d_records or status is NULL");
+    if (k > PORLA_KZG_VERIFY_MAX_K) return bad_arg(who, "k > 10922 (the folded entry P holds 3 pairs per reply, at most 32768): split the batch");
     uint64_t pairs = 4 * (uint64_t)k;
     for (size_t a = 0; a < k; a++) {
         const porla_kzg_verify_req& R = reqs[a];
-        if (R.n && (!R.d_comp_store || !R.d_idx || !R.d_coef)) return bad("a NULL complement or challenge array with n > 0");
-        if (R.n > KZG_VERIFY_MAX_N) return bad("n > 32768 (the batched MSM's entry limit)");
+        if (R.n && (!R.d_comp_store || !R.d_idx || !R.d_coef)) return bad_arg(who, "a NULL complement or challenge array with n > 0");
+        if (R.n > KZG_VERIFY_MAX_N) return bad_arg(who, "n > 32768 (the batched MSM's entry limit)");
         pairs += R.n + 3;
         if (weights && std::all_of(weights + 16 * a, weights + 16 * a + 16, [](uint8_t b) { return b == 0; }))
-            return bad("an all-zero weight");
+            return bad_arg(who, "an all-zero weight");
     }
     size_t bytes;
-    if (!mul_ok((size_t)pairs, 96, &bytes) || !mul_ok(k, KZG_VERIFY_RECORD, &bytes)) return bad("the batch's byte size overflows");
+    if (!mul_ok((size_t)pairs, 96, &bytes) || !mul_ok(k, KZG_VERIFY_RECORD, &bytes)) return bad_arg(who, "the batch's byte size overflows");
     if (k == 0) return PORLA_OK;
     int rc = ensure_device();
     if (rc) return rc;
@@ -306,22 +295,13 @@ extern "C" int porla_kzg_verify_batch_device(const porla_kzg_verify_req* reqs, s
         if ((rc = draw_weights(drawn.data(), k))) return rc;
         weights = drawn.data();
     }
-    int dev = 0;
-    PORLA_HIP(hipGetDevice(&dev));
     KzgVerifyBatchWs* ws = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_kvb_mu);
-        for (auto* w : g_kvb_ws) if (w->device == dev) ws = w;
-        if (!ws) { ws = new KzgVerifyBatchWs(); ws->device = dev; g_kvb_ws.push_back(ws); }
-    }
+    if ((rc = g_kvb_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     uint8_t pq[128];
     {
-        std::lock_guard<std::mutex> lk(ws->mu);
-        rc = verify_batch_enqueue(ws, reqs, k, (const uint8_t*)d_records, weights, g_be, stream);
-        // the buffers of this call are behind the fence on every exit, a failing one included
-        const int rf = ws->fence.leave(stream);
-        if (rc || rf) return rc ? rc : rf;
+        FencedCall call(ws, stream);       // mu stays held for the wait: h_out and `done` are the workspace's
+        if ((rc = call.run([&] { return verify_batch_enqueue(ws, reqs, k, (const uint8_t*)d_records, weights, g_be, stream); }))) return rc;
         PORLA_HIP(hipEventSynchronize(ws->done));
         memcpy(pq, ws->h_out, 128);
         memcpy(status, (const uint8_t*)ws->h_out + 128, k);

@@ -11,7 +11,7 @@
 //          N^2 * 32 independent mixed additions instead of log2(N) dependent ladders -- throughput- not latency-bound.
 // Patch site in the reference (no function boundary exists there): the MAC halves of Server::CRebuild_Cached,
 // porla/Server/Server.hpp:1523-1536, 1590-1609, 1658-1676 and the Y-part twins; see INTEGRATION.md.
-#include "engine.hpp"
+#include "batch_host.hpp"
 #include <cstring>
 #include "mac_fft.hip.h"
 #include "icc_host.hpp"
@@ -48,18 +48,7 @@ static int macq_max_log(int own) {
     static const int v = getenv("PORLA_MAC_QUAD_MAX") ? atoi(getenv("PORLA_MAC_QUAD_MAX")) : 16;
     return v < own ? v : own;
 }
-static std::vector<MacWs*> g_mac_ws;
-
-static int get_mac_ws(MacWs** out) {
-    int dev = 0;
-    PORLA_HIP(hipGetDevice(&dev));
-    for (auto* w : g_mac_ws) if (w->device == dev) { *out = w; return PORLA_OK; }
-    MacWs* w = new MacWs();
-    w->device = dev;
-    g_mac_ws.push_back(w);
-    *out = w;
-    return PORLA_OK;
-}
+static PerDevice<MacWs> g_mac_ws;   // used under g_mac_mu
 
 // plain scalars (w^e mod p_icc) mod q for e < N, resident across calls with the same N and curve
 template <class Q>
@@ -300,7 +289,7 @@ static int mac_encode_core(MacWs* ws, int curve, const uint8_t* d_in, size_t n, 
 int mac_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** tws, int* quad_max_log) {
     g_mac_mu.lock();
     MacWs* ws = nullptr;
-    int rc = get_mac_ws(&ws);
+    int rc = g_mac_ws.get(&ws);
     if (!rc) rc = ws->fence.enter(stream);
     if (!rc) rc = curve == 0 ? ensure_mac_twiddles<IccBn254Fr>(ws, 0, n_total, stream) : ensure_mac_twiddles<IccSecp256k1Fn>(ws, 1, n_total, stream);
     if (rc) { g_mac_mu.unlock(); return rc; }
@@ -310,7 +299,7 @@ int mac_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const 
 }
 int mac_mix_tables_release(hipStream_t stream) {
     MacWs* ws = nullptr;
-    int rc = get_mac_ws(&ws);
+    int rc = g_mac_ws.get(&ws);
     if (!rc) rc = ws->fence.leave(stream);
     g_mac_mu.unlock();
     return rc;
@@ -349,7 +338,7 @@ int porla_icc_mac_encode_device(const void* d_macs_in, size_t n_rows, int curve,
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(g_mac_mu);
     MacWs* ws;
-    if ((rc = get_mac_ws(&ws))) return rc;
+    if ((rc = g_mac_ws.get(&ws))) return rc;
     return mac_dispatch(ws, curve, (const uint8_t*)d_macs_in, n_rows, write_step, part, (uint8_t*)d_macs_out, (hipStream_t)hip_stream);
 }
 
@@ -360,7 +349,7 @@ int porla_icc_mac_encode_xy_device(const void* d_macs_in, size_t n_rows, int cur
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(g_mac_mu);
     MacWs* ws;
-    if ((rc = get_mac_ws(&ws))) return rc;
+    if ((rc = g_mac_ws.get(&ws))) return rc;
     return mac_dispatch(ws, curve, (const uint8_t*)d_macs_in, n_rows, write_step, 0, (uint8_t*)d_macs_x_out, (hipStream_t)hip_stream,
                         (uint8_t*)d_macs_y_out);
 }
@@ -371,7 +360,7 @@ int porla_icc_mac_encode_xy_host(const uint8_t* macs_in, size_t n_rows, int curv
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(g_mac_mu);
     MacWs* ws;
-    if ((rc = get_mac_ws(&ws))) return rc;
+    if ((rc = g_mac_ws.get(&ws))) return rc;
     if ((rc = ws->in.ensure(n_rows * 64)) || (rc = ws->out.ensure(n_rows * 64)) || (rc = ws->out_y.ensure(n_rows * 64))) return rc;
     hipStream_t s = engine_stream();
     PORLA_HIP(hipMemcpyAsync(ws->in.p, macs_in, n_rows * 64, hipMemcpyHostToDevice, s));
@@ -394,7 +383,7 @@ int porla_icc_mac_mix_device(const void* d_a0, const void* d_a1, size_t len, siz
     }
     std::lock_guard<std::mutex> lk(g_mac_mu);
     MacWs* ws;
-    if ((rc = get_mac_ws(&ws))) return rc;
+    if ((rc = g_mac_ws.get(&ws))) return rc;
     if ((rc = ws->fence.enter((hipStream_t)hip_stream))) return rc;
     rc = curve == 0 ? mac_mix_core<Bn254G1, IccBn254Fr>(ws, 0, (const uint8_t*)d_a0, (const uint8_t*)d_a1, len, n_total, (uint8_t*)d_out, (hipStream_t)hip_stream)
                     : mac_mix_core<Secp256k1G, IccSecp256k1Fn>(ws, 1, (const uint8_t*)d_a0, (const uint8_t*)d_a1, len, n_total, (uint8_t*)d_out, (hipStream_t)hip_stream);
@@ -415,7 +404,7 @@ int porla_icc_mac_mix_pair_device(const void* d_a0, const void* d_a1, const void
     }
     std::lock_guard<std::mutex> lk(g_mac_mu);
     MacWs* ws;
-    if ((rc = get_mac_ws(&ws))) return rc;
+    if ((rc = g_mac_ws.get(&ws))) return rc;
     if ((rc = ws->fence.enter((hipStream_t)hip_stream))) return rc;
     rc = curve == 0 ? mac_mix_core<Bn254G1, IccBn254Fr>(ws, 0, (const uint8_t*)d_a0, (const uint8_t*)d_a1, len, n_total, (uint8_t*)d_out_a,
                                                         (hipStream_t)hip_stream, (const uint8_t*)d_b0, (const uint8_t*)d_b1, (uint8_t*)d_out_b)
@@ -489,7 +478,7 @@ int porla_icc_mac_encode_host(const uint8_t* macs_in, size_t n_rows, int curve, 
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(g_mac_mu);
     MacWs* ws;
-    if ((rc = get_mac_ws(&ws))) return rc;
+    if ((rc = g_mac_ws.get(&ws))) return rc;
     if ((rc = ws->in.ensure(n_rows * 64))) return rc;
     if ((rc = ws->out.ensure(n_rows * 64))) return rc;
     hipStream_t s = engine_stream();

@@ -81,37 +81,9 @@ static int msm_batch_locked(Workspace* ws, const uint8_t* d_scalars, const uint8
         words += 4 * R.k + R.nb + R.nf + R.nq;
     }
     {
-        // ---- the work list into pinned memory.  The buffer is reused when the previous call's upload from it has happened; while
-        // that copy is still queued (behind whatever its stream held) the buffer is retired -- freed by a later call once its copy is
-        // done -- and a new one taken, so that a call never waits for earlier work
-        const size_t bytes = words * 4;
-        for (size_t i = 0; i < ws->batch_retired.size();) {
-            const hipError_t q = hipEventQuery(ws->batch_retired[i].second);
-            if (q == hipErrorNotReady) { i++; continue; }
-            PORLA_HIP(q);
-            PORLA_HIP(hipHostFree(ws->batch_retired[i].first));
-            PORLA_HIP(hipEventDestroy(ws->batch_retired[i].second));
-            ws->batch_retired.erase(ws->batch_retired.begin() + (long)i);
-        }
-        if (ws->batch_upload) {
-            const hipError_t q = hipEventQuery(ws->batch_upload);
-            if (q == hipErrorNotReady) {
-                ws->batch_retired.emplace_back(ws->h_batch, ws->batch_upload);
-                ws->h_batch = nullptr;
-                ws->h_batch_cap = 0;
-                ws->batch_upload = nullptr;
-            } else {
-                PORLA_HIP(q);
-            }
-        }
-        if (ws->h_batch_cap < bytes) {
-            if (ws->h_batch) PORLA_HIP(hipHostFree(ws->h_batch));
-            ws->h_batch = nullptr;
-            ws->h_batch_cap = 0;
-            PORLA_HIP(hipHostMalloc(&ws->h_batch, bytes + bytes / 4 + 4096, hipHostMallocDefault));
-            ws->h_batch_cap = bytes + bytes / 4 + 4096;
-        }
-        uint32_t* h = (uint32_t*)ws->h_batch;
+        // ---- the work list into pinned memory (a buffer whose previous upload is still queued is retired, not waited for)
+        if ((rc = ws->batch_list_h.stage(words * 4))) return rc;
+        uint32_t* h = (uint32_t*)ws->batch_list_h.h;
         for (size_t ri = 0; ri < rounds.size(); ri++) {
             BatchRound& R = rounds[ri];
             BatchEntry* ents = (BatchEntry*)(h + R.words);
@@ -162,9 +134,7 @@ static int msm_batch_locked(Workspace* ws, const uint8_t* d_scalars, const uint8
     if ((rc = ws->batch_part.ensure(2 * part_bytes + 256))) return rc;
     if ((rc = ws->batch_sums.ensure(max_k * sizeof(XYZZ<M>) + 256))) return rc;
     if ((rc = ws->batch_ctrl.ensure(((size_t)max_nb + max_k) * 4 + 256))) return rc;
-    PORLA_HIP(hipMemcpyAsync(ws->batch_list.p, ws->h_batch, list_words * 4, hipMemcpyHostToDevice, stream));
-    if (!ws->batch_upload) PORLA_HIP(hipEventCreateWithFlags(&ws->batch_upload, hipEventDisableTiming));
-    PORLA_HIP(hipEventRecord(ws->batch_upload, stream));
+    if ((rc = ws->batch_list_h.send(ws->batch_list.p, list_words * 4, stream))) return rc;
     const uint32_t* d_list = (const uint32_t*)ws->batch_list.p;
     XYZZ<M>* part = (XYZZ<M>*)ws->batch_part.p;
     XYZZ<M>* fin = (XYZZ<M>*)((uint8_t*)ws->batch_part.p + part_bytes);

@@ -10,7 +10,7 @@
 //   k_update_place           MAC X, MAC Y = wt * MAC, align X = infinity, align Y = Commit(c)
 //   for i < Lmax:            k_update_mix_data (both parts) and k_update_mix_points (the four point families) of the requests with level > i
 //   k_update_close           incoming half over resident half at the request's level, then the complements onto MAC X / MAC Y
-#include "engine.hpp"
+#include "batch_host.hpp"
 #include "update_batch.hip.h"
 #include "../../include/porla_gpu.h"
 
@@ -34,8 +34,7 @@ struct UpdateBatchWs {
     UseFence fence;
     bool lds_set = false;
 };
-static std::mutex g_upd_mu;
-static std::vector<UpdateBatchWs*> g_upd_ws;
+static PerDevice<UpdateBatchWs> g_upd_ws;
 
 // dynamic LDS above 64 KiB: a kernel must be told once per device (as mac_fft.hip does for the kernels these are forms of)
 static void update_lds_attributes(UpdateBatchWs* ws) {
@@ -107,7 +106,7 @@ static int launch_steps(const UpdPlan& P, const std::vector<uint32_t>& active, u
     return rc ? rc : (r1 ? r1 : r2);
 }
 
-// ws->mu held.  fb == nullptr: the resident SRS (KZG).
+// ws->mu held, ws->fence entered.  fb == nullptr: the resident SRS (KZG).
 template <class C>
 static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_update_req* reqs, size_t k, size_t ncols, size_t n_total,
                           hipStream_t stream) {
@@ -147,7 +146,6 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
     if ((rc = ws->list.ensure(list_b))) return rc;
     if ((rc = ws->scalars.ensure(k * ncols * 32))) return rc;
     update_lds_attributes(ws);
-    if ((rc = ws->fence.enter(stream))) return rc;
     if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
     UpdPlan P;
     P.d_desc = (const UpdDesc*)ws->list.p;
@@ -164,10 +162,9 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
     if constexpr (UpdCurve<C>::id == 0) {
         if ((rc = kzg_commit_rows_raw((const uint8_t*)ws->scalars.p, k, stream, place_after_srs, &P))) return rc;
     } else {
-        std::lock_guard<std::mutex> lk(fb->mu);
-        if ((rc = fb->commit_device((const uint8_t*)ws->scalars.p, k, ncols, 32 * ncols, nullptr, stream))) return rc;
-        if ((rc = launch_place<C>(P, fb->partial, fb->last_S))) return rc;
-        if ((rc = fb->fence.leave(stream))) return rc;
+        rc = commit_then(*fb, (const uint8_t*)ws->scalars.p, k, ncols, stream,
+                         [&](const XYZZ<typename C::Fp>* sums, uint32_t S) { return launch_place<C>(P, sums, S); });
+        if (rc) return rc;
     }
     // ---- 3. the rebuild steps
     if (lmax && (rc = launch_steps<C>(P, active, lmax, n_total))) return rc;
@@ -184,7 +181,7 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
 
 // the checks both entry points make before the device is touched
 static int update_check(const char* who, const porla_update_req* reqs, size_t k, size_t n_total) {
-    auto bad = [&](const std::string& what) { set_last_error(std::string(who) + ": " + what); return PORLA_ERR_ARG; };
+    auto bad = [&](const std::string& what) { return bad_arg(who, what); };
     if (k && !reqs) return bad("reqs is NULL");
     int ln = 0;
     while (((size_t)1 << ln) < n_total && ln < 62) ln++;
@@ -205,18 +202,6 @@ static int update_check(const char* who, const porla_update_req* reqs, size_t k,
             if (!seen.insert(fam[f][0]).second) return bad(at + "a level-0 pointer another request (or family) of this call names too: requests must be disjoint");
         }
     }
-    return PORLA_OK;
-}
-
-static int update_workspace(UpdateBatchWs** out) {
-    int dev = 0;
-    PORLA_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_upd_mu);
-    for (auto* w : g_upd_ws) if (w->device == dev) { *out = w; return PORLA_OK; }
-    UpdateBatchWs* w = new UpdateBatchWs();
-    w->device = dev;
-    g_upd_ws.push_back(w);
-    *out = w;
     return PORLA_OK;
 }
 
@@ -243,13 +228,9 @@ extern "C" int porla_kzg_update_batch_device(const porla_update_req* reqs, size_
     if (n == 0) { set_last_error("porla: SRS not initialised (call init_SRS / init_SRS_from_data first)"); return PORLA_ERR_STATE; }
     if (n > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
     UpdateBatchWs* ws = nullptr;
-    if ((rc = update_workspace(&ws))) return rc;
-    std::lock_guard<std::mutex> lk(ws->mu);
+    if ((rc = g_upd_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    rc = update_enqueue<Bn254G1>(ws, nullptr, reqs, k, n, n_total, stream);
-    // the buffers of this call are behind the fence on every exit, a failing one included
-    const int rf = ws->fence.leave(stream);
-    return rc ? rc : rf;
+    return FencedCall(ws, stream).run([&] { return update_enqueue<Bn254G1>(ws, nullptr, reqs, k, n, n_total, stream); });
 }
 
 extern "C" int porla_ipa_update_batch_device(porla_fixed_base* generators_fb, const porla_update_req* reqs, size_t k, size_t n_total,
@@ -258,18 +239,14 @@ extern "C" int porla_ipa_update_batch_device(porla_fixed_base* generators_fb, co
     int rc = update_check(who, reqs, k, n_total);
     if (rc) return rc;
     if (k == 0) return PORLA_OK;
-    if (!generators_fb) { set_last_error(std::string(who) + ": generators_fb is NULL"); return PORLA_ERR_ARG; }
+    if (!generators_fb) return bad_arg(who, "generators_fb is NULL");
     if ((rc = ensure_device())) return rc;
     // (a handle exists only where a device does: it is read after ensure_device, and still before any device work)
-    if (generators_fb->curve != 1 || generators_fb->secp.n_points < UPD_IPA_COLS) {
-        set_last_error(std::string(who) + ": generators_fb must be a secp256k1 fixed base over at least the 128 generators");
-        return PORLA_ERR_ARG;
-    }
+    if (generators_fb->curve != 1 || generators_fb->secp.n_points < UPD_IPA_COLS)
+        return bad_arg(who, "generators_fb must be a secp256k1 fixed base over at least the 128 generators");
     UpdateBatchWs* ws = nullptr;
-    if ((rc = update_workspace(&ws))) return rc;
-    std::lock_guard<std::mutex> lk(ws->mu);
+    if ((rc = g_upd_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    rc = update_enqueue<Secp256k1G>(ws, &generators_fb->secp, reqs, k, UPD_IPA_COLS, n_total, stream);
-    const int rf = ws->fence.leave(stream);
-    return rc ? rc : rf;
+    return FencedCall(ws, stream).run(
+        [&] { return update_enqueue<Secp256k1G>(ws, &generators_fb->secp, reqs, k, UPD_IPA_COLS, n_total, stream); });
 }
