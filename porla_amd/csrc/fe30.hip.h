@@ -373,7 +373,10 @@ struct KP30 {
 template <class M, int K>
 constexpr typename KP30<M, K>::Tab KP30<M, K>::T;
 
-// a - b + K p, normal result.  a normal (or any limbs < 2^30 + 2^29), b normal with value <= (K-1) p + 2^247.
+// a - b + K p, normal result.  a normal (or any limbs < 2^30 + 2^29), b normal with value <= (K-1) p + 2^247.  What the table needs is
+// only that its limb 8 (limb 8 of K p, minus 1) is at least limb 8 of b; icc30.hip.h:icc30_sub leans on exactly that with wider
+// operands (a: limb 8 < 2^23; b up to p + 2^250 for K = 2, 2 (p + 2^248) for K = 4, 2^256 for K = 7) for the three ICC moduli,
+// proved for those by tools/check_fe30_bounds.py:check_sub_tables and fed at those values by tests/test_icc30_gpu.py.
 template <class M, int K>
 __device__ __forceinline__ F30<M> f30_sub(const F30<M>& a, const F30<M>& b) {
     F30<M> r;

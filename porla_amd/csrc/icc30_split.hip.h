@@ -77,16 +77,18 @@ k_icc_twiddles30_planes(const IccElem<Q>* __restrict__ tw, uint32_t n, uint32_t*
     icc30_st_pslot<Q>(twq + (size_t)e * ICC30_PSLOT_WORDS, t.q);
 }
 
-// one butterfly on one plane: (a, b) <- (a + w b, a - w b + 2 p); the product brings b below p + 2^248 whatever it was
+// one butterfly on one plane: (a, b) <- (a + w b, a - w b + 2 p); the product brings b below p + 2^250 whatever it was (b < 2^263,
+// w < 2^257; icc30.hip.h)
 template <class M>
 __device__ __forceinline__ void icc30_bfly(F30<M>& a, F30<M>& b, const F30<M>& w) {
     const F30<M> t = icc30_mul<M>(w, b);
     b = icc30_sub<M, 2>(a, t);
     a = icc30_add<M>(a, t);
 }
-// a butterfly whose twiddle is w^0 and whose lower operand is known to be small: (a, b) <- (a + b, a - b + K p), b <= (K - 1) p
-// + 2^240.  Stage 1 of the first pass: operands straight from the load step -- products of it (K = 2: b < p + 2^248) or RAW 256-bit
-// chunks (K = 7: b < 2^256 < 6 p + 2^240 for all three moduli, the smallest being the BN254 group order at 0.189 x 2^256)
+// a butterfly whose twiddle is w^0 and whose lower operand is known to be small: (a, b) <- (a + b, a - b + K p), with limb 8 of b
+// below limb 8 of K p (icc30.hip.h:icc30_sub).  The first round of the first pass: operands straight from the load step -- products
+// of it (K = 2: b < p + 2^248; K = 4: b < 2 (p + 2^248), the sum of two), RAW 256-bit chunks (K = 7: b < 2^256 < 6 p + 2^240 for
+// all three moduli, the smallest being the BN254 group order at 0.189 x 2^256) or icc30_reduce_top's result (K = 3: b < 2 p)
 template <class M, int K>
 __device__ __forceinline__ void icc30_bfly_plain(F30<M>& a, F30<M>& b) {
     static_assert(K <= 4 || (unsigned __int128)(K - 1) * ((((unsigned __int128)M::P[7]) << 32) | M::P[6]) >= ((unsigned __int128)1 << 64),
@@ -103,11 +105,12 @@ struct IccTile {           // what a block knows about its tile (the same for bo
 };
 
 // a tile symbol from where the pass finds it.  FIRST: the raw 32-byte chunk x.  The stream is made of PLAIN residues and nothing
-// in the network needs them reduced -- a product with a twiddle brings any operand below 2^263 under p + 2^248, sums and
+// in the network needs them reduced -- a product with a twiddle brings any operand below 2^263 under p + 2^250, sums and
 // differences stay unreduced anyway -- so without an init scaling (the X part: T.raw) the 256-bit chunk enters as it is: nine
-// normal limbs, value below 2^256 (the first stage's difference then adds 7 p instead of 2 p, and a symbol is bounded by
-// 8.3 p + 2 p per later stage: 66.3 p < 2^263 after 30 stages -- limb 8 below 2^23, the column bound tools/check_fe30_bounds.py proves -- like the
-// 63 p of the scaled form).  With an init scaling (the Y part) the load step is the product x * (wt 2^270) / 2^270 = x wt.
+// normal limbs, value below 2^256 (the first stage's difference then adds 7 p instead of 2 p: a symbol is below 2^256 + 7 p after
+// stage 1, below 2^256 + 9 p after stage 2 -- 10.3 p for p_icc, 10 p for the secp256k1 order, 14.3 p for the BN254 order -- and gains
+// 2 p per later stage: at most 0.52 x 2^263 after 30 stages (the secp256k1 order at 66 p) -- limb 8 below 2^23, the column bound
+// tools/check_fe30_bounds.py proves; its check_icc_chain walks this chain -- like the 62.1 p of the scaled form).  With an init scaling (the Y part) the load step is the product x * (wt 2^270) / 2^270 = x wt.
 // (icc30.hip.h:icc30_load_raw multiplies by the Montgomery unit in the unscaled case: two products per symbol that only reduce.)
 // Not FIRST: the plane's work array.
 template <class M, bool FIRST>
@@ -162,7 +165,7 @@ __device__ __forceinline__ void icc30_round(uint32_t* lds, const IccTile& T, int
                 // the encode's first round: j = 0 for EVERY unit, the twiddle of pair (0, 2) is w^0 -- a product with the
                 // Montgomery unit would only reduce a[2].  Whole waves skip it: a[2] = a2 + a3 is below 2^257 (raw chunks; a short
                 // reduction brings it under 2 p, K = 3) or below 2 (p + 2^248) (scaled chunks, K = 4); the outputs stay under
-                // 2^257 + 3 p, inside the bound icc30_fetch states
+                // 2^257 + 3 p (raw) and 2 (p + 2^248) + 4 p (scaled), inside the bounds icc30_fetch states
                 if (T.raw) { a[2] = icc30_reduce_top<M>(a[2]); icc30_bfly_plain<M, 3>(a[0], a[2]); }
                 else icc30_bfly_plain<M, 4>(a[0], a[2]);
             } else {

@@ -143,3 +143,56 @@ def test_both_parts_from_one_network(curve, n, ncols, ws):
             icc.crebuild_xy_device(d_in.data_ptr(), n, ncols, curve, ws, stream=stream, **{name: t.data_ptr()})
             torch.cuda.synchronize()
             assert bytes(t.cpu().numpy()) == want[k // 3][k % 3], name
+
+
+# ---------------------------------------------------------------- every corner of the first round, through the real kernel
+@pytest.fixture(scope="module")
+def corner_rows():
+    """(curve, n) -> (rows, ncols): the columns enumerate every combination of the row values {0, 1, 2^256 - 1, p_icc - 1, p_icc,
+    q - 1, q}: 7^4 = 2 401 columns of 4 rows, 7^2 = 49 columns of 2.  The only way through icc30_split.hip.h:icc30_round's first-round
+    branches (K = 7, icc30_reduce_top, K = 3 on raw chunks; K = 2, K = 4 on scaled ones) with every operand at its ends."""
+    import icc_py
+    cache = {}
+
+    def make(curve, n):
+        if (curve, n) not in cache:
+            q = icc_py.Q[curve]
+            vals = [0, 1, 2**256 - 1, icc_py.P_ICC - 1, icc_py.P_ICC, q - 1, q]
+            ncols = len(vals) ** n
+            cache[(curve, n)] = (b"".join(vals[(c // len(vals) ** r) % len(vals)].to_bytes(32, "little") for r in range(n) for c in range(ncols)), ncols)
+        return cache[(curve, n)]
+    return make
+
+
+@pytest.mark.parametrize("curve", ["bn254", "secp256k1"])
+@pytest.mark.parametrize("n", [4, 2])
+@pytest.mark.parametrize("part,ws", [(0, 0), (1, 1), (1, 3)])
+def test_first_round_corners(corner_rows, curve, n, part, ws):
+    """part 0 with write_step 0 takes the raw first round, part 1 with write_step 1 and 3 the scaled one; byte for byte"""
+    from porla_amd import icc
+    rows, ncols = corner_rows(curve, n)
+    assert ncols == 7 ** n
+    got = icc.crebuild_host(rows, n, ncols, curve, ws, part)
+    want = oracle_crebuild(rows, n, ncols, icc.CURVE[curve], part, ws)
+    assert got[0] == want[0]      # values mod LCM
+    assert got[1] == want[1]      # values mod p_icc
+    assert got[2] == want[2]      # alignment scalars
+
+
+@pytest.mark.parametrize("curve", ["bn254", "secp256k1"])
+@pytest.mark.parametrize("n", [4, 2])
+@pytest.mark.parametrize("ws", [1, 3])
+def test_first_round_corners_both_parts_from_one_network(corner_rows, curve, n, ws):
+    """the XY entry point on the same rows: the raw first round, then one product per residue with a symbol at the top of its range"""
+    import torch
+    from porla_amd import icc
+    rows, ncols = corner_rows(curve, n)
+    want = [oracle_crebuild(rows, n, ncols, icc.CURVE[curve], part, ws) for part in (0, 1)]
+    d_in = torch.frombuffer(bytearray(rows), dtype=torch.uint8).cuda()
+    outs = [[torch.empty(w * n * ncols, dtype=torch.uint8, device="cuda") for w in (64, 32, 32)] for _ in (0, 1)]
+    icc.crebuild_xy_device(d_in.data_ptr(), n, ncols, curve, ws, *[t.data_ptr() for t in outs[0]], *[t.data_ptr() for t in outs[1]],
+                           stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    for part in (0, 1):
+        for k, what in enumerate(("values mod LCM", "values mod p_icc", "alignment scalars")):
+            assert bytes(outs[part][k].cpu().numpy()) == want[part][k], "%s, part %d" % (what, part)

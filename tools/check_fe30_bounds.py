@@ -7,7 +7,8 @@ MODULI = {
     "p_icc": 207 * 2**248 + 1,
 }
 # the ICC kernel of icc30.hip.h multiplies an UNREDUCED butterfly output (< 2^263: limb 8 < 2^23) by a twiddle (a product's result,
-# < p + 2^248: limb 8 < 2^17) modulo p_icc, the BN254 group order and the secp256k1 group order
+# in the table below p + 2^242; as an operand anything with limb 8 < 2^17, i.e. < 2^257) modulo p_icc, the BN254 group order and the
+# secp256k1 group order.  The numbers of check_icc_chain are the ones tests/icc_vectors.py feeds.
 ICC_MODULI = {
     "p_icc": 207 * 2**248 + 1,
     "bn254_r": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
@@ -106,7 +107,8 @@ def check_value_ranges():
 def check_sub_tables():
     """borrow-free subtractions a + (K p' - b) of fe30.hip.h: every limb of the K p table of f30_sub exceeds a normal limb of b
     (limbs 0..7) and the top limb exceeds b's for b <= (K - 1) p + 2^247; f30_sub_twice (a - 2 b, allowance doubled) stays
-    inside 32 bits per limb, carries included"""
+    inside 32 bits per limb, carries included.  The ICC stream uses the same tables with wider operands (icc30.hip.h:icc30_sub):
+    those are checked at the call sites' own bounds (icc_sub_operands)"""
     ok = True
     for name, p in (("bn254_p", MODULI["bn254_p"]), ("secp256k1_p", SECP_P)):
         for K in (2, 3, 4, 5, 6):
@@ -129,6 +131,96 @@ def check_sub_tables():
         good = all(T2[i] >= 2 * MASK for i in range(8)) and T2[8] >= two_b_top and max(T2[:8]) + MASK + 3 < 2**32          # + a normal limb of a + a carry of at most 3
         print("%-12s subtraction tables (K = 2..6, and the doubled one of f30_sub_twice<3>): %s" % (name, "ok" if ok and good else "BAD"))
         ok = ok and good
+    # the ICC stream (icc30.hip.h:icc30_sub, icc30_split.hip.h:icc30_bfly_plain): the three ICC moduli, K as the call sites use it,
+    # b at the largest value each call site can hand over.  a is a symbol of the stream: limb 8 < 2^23, so the limb-wise sum
+    # a + (K p' - b) stays far inside 32 bits
+    for name, p in ICC_MODULI.items():
+        good = True
+        for K, b_max in icc_sub_operands(p).items():
+            kp = K * p
+            T = [(kp >> (30 * i)) & MASK for i in range(8)] + [kp >> 240]
+            T[0] += 2**30
+            for i in range(1, 8):
+                T[i] += 2**30 - 1
+            T[8] -= 1
+            assert sum(t << (30 * i) for i, t in enumerate(T)) == kp
+            good = good and all(T[i] >= MASK for i in range(8)) and T[8] >= b_max >> 240 and max(T[:8]) + MASK + 3 < 2**32 \
+                and T[8] + 2**23 < 2**32
+        print("icc:%-11s subtraction tables (K = 2, 3, 4, 7 at the call sites' operand bounds): %s" % (name, "ok" if good else "BAD"))
+        ok = ok and good
+    return ok
+
+
+# ---------------------------------------------------------------- the ICC stream's bound chain
+ICC_A_BITS, ICC_W_BITS, ICC_STAGES = 263, 257, 30    # a symbol: limb 8 < 2^23; a twiddle as an operand: limb 8 < 2^17; stages without a reduction
+
+
+def icc_product_top(p):
+    """exclusive bound of a product a w / 2^270 (+ m p / 2^270, m < 2^270) over the whole operand domain: p + 2^250"""
+    return p + (((2**ICC_A_BITS - 1) * (2**ICC_W_BITS - 1)) >> 270) + 1
+
+
+def icc_load_top(p):
+    """exclusive bound the comments state for a load-step product (256-bit chunk times a table twiddle below p + 2^242)"""
+    return p + 2**248
+
+
+def icc_sub_operands(p):
+    """K -> the largest b of a - b + K p at its call site"""
+    return {2: icc_product_top(p) - 1,               # icc30_bfly, icc30_mix_elem: a product; icc30_bfly_plain<2>: a load-step product
+            3: 2 * p - 1,                            # raw first round, pair (0, 2): icc30_reduce_top's result
+            4: 2 * icc_load_top(p) - 1,              # scaled first round, pair (0, 2): the sum of two load-step products
+            7: 2**256 - 1}                           # raw first round: a 256-bit chunk
+
+
+def icc_reduce_top_ok(p, bits=ICC_A_BITS):
+    """icc30.hip.h:icc30_reduce_top for EVERY v < 2^bits: qh = floor(v[8] MU / 2^40) depends on limb 8 alone and is monotone in it,
+    so the extremes of v - qh p sit at the first and the last limb 8 of each qh"""
+    MU = 2**88 // ((p >> 192) + 1)
+    top8 = 2**(bits - 240) - 1
+    if MU >= 2**32:
+        return False
+    for qh in range(((top8 * MU) >> 40) + 1):
+        lo8 = -(-(qh << 40) // MU)
+        hi8 = min(-(-((qh + 1) << 40) // MU) - 1, top8)
+        if lo8 <= hi8 and not ((lo8 << 240) - qh * p >= 0 and ((hi8 + 1) << 240) - 1 - qh * p < 2 * p):
+            return False
+    return True
+
+
+def check_icc_chain(stages=ICC_STAGES):
+    """the symbol bound chain of icc30_split.hip.h closes: load step -> first round -> `stages` stages in all -> limb 8 < 2^23 (the
+    operand range of a product and of icc30_reduce_top) -> [0, 2 p) (icc30_canonical's range), raw and scaled, all three moduli.
+    Bounds are exclusive."""
+    ok = True
+    for name, p in ICC_MODULI.items():
+        T = icc_product_top(p)
+        grow = max(T, 2 * p)                         # X[k] + t < X[k] + T;  X[k] - t + 2 p <= X[k] + 2 p
+        tw = p + 2**242                              # a table twiddle: icc30_from_elem's product of two values below 2^256
+        good = p + (((2**256 - 1) ** 2) >> 270) + 1 <= tw and tw <= 2**ICC_W_BITS
+        good = good and p + (((2**256 - 1) * (tw - 1)) >> 270) + 1 <= icc_load_top(p)                  # the scaled load step
+        for form in ("raw", "scaled"):
+            if form == "raw":
+                # stage 1, K = 7: (a + b, a - b + 7 p) of two chunks; stage 2: pair (0, 2) = (2^257 sum, reduced to < 2 p) with K = 3,
+                # pair (1, 3) an ordinary butterfly
+                s1 = 2**256 + 7 * p
+                s2 = max(2**257 + 3 * p, s1 + grow)
+                good = good and icc_reduce_top_ok(p, 257)
+            else:
+                L = icc_load_top(p)
+                s1 = L + 2 * p                                                             # K = 2: (2 L, L + 2 p)
+                s2 = max(4 * L, 2 * L + 4 * p, s1 + grow)                                  # K = 4 on pair (0, 2)
+            worst = s2 + (stages - 2) * grow
+            good = good and s1 < 2**ICC_A_BITS and worst <= 2**ICC_A_BITS
+            print("icc:%-11s %-6s stream: %.2f p after the first round, %.2f p = %.4f x 2^263 after %d stages  %s"
+                  % (name, form, s2 / p, worst / p, worst / 2**ICC_A_BITS, stages, "ok" if worst <= 2**ICC_A_BITS else "TOO LARGE"))
+        # the finish step: any v < 2^263 -> [0, 2 p) -> canonical; the second part's product (symbol times wt) is below T as well
+        good = good and icc_reduce_top_ok(p) and T <= 2**ICC_A_BITS
+        # the mix: two symbols of 512 bits enter below 2^258, the outputs stay below 2^258 + max(T, 2 p)
+        good = good and (p + (((2**256 - 1) * (p - 1)) >> 270) + 1) + 2**256 <= 2**258 and 2**258 + grow <= 2**ICC_A_BITS
+        print("icc:%-11s bound chain (load step, %d stages, icc30_reduce_top on every v < 2^263, icc30_canonical): %s"
+              % (name, stages, "ok" if good else "BAD"))
+        ok = ok and good
     return ok
 
 
@@ -140,5 +232,6 @@ if __name__ == "__main__":
     ok = all([check("icc:" + n, p, 23, 17) for n, p in ICC_MODULI.items()]) and ok
     ok = check_value_ranges() and ok
     ok = check_sub_tables() and ok
-    # result bound of the ICC product: a b / 2^270 + p < p + 2^249 for a < 2^263, b < 2^256: limb 8 stays far below 2^30
+    # result bound of the ICC product: a b / 2^270 + p < p + 2^250 for a < 2^263, b < 2^257: limb 8 stays far below 2^30
+    ok = check_icc_chain() and ok
     sys.exit(0 if ok else 1)
