@@ -656,6 +656,55 @@ int porla_kzg_update_batch_device(const porla_update_req *reqs, size_t k, size_t
 int porla_ipa_update_batch_device(porla_fixed_base *generators_fb, const porla_update_req *reqs, size_t k, size_t n_total,
                                   void *hip_stream);
 
+/* ---- Client::update's preprocessing for K independent writes in ONE asynchronous call (Client.hpp:457-614: the block's MAC,
+ * compute_MAC_complement for every slot below the level the write lands on, Client::HAdd -> HRebuildX / HRebuildY :978-1038 on them,
+ * mix :921-976, and the differences "new complement - mixed complement" that go on the wire) ----
+ * The other side of porla_*_update_batch_device: d_mac_out and d_complements_out are what porla_update_req takes as d_mac and
+ * d_complements, and d_block is the SAME buffer.  AES stays on the host: the caller passes the 16-byte AES_encrypt outputs of
+ * compute_MAC_complement raw.  Request a is one write:
+ *   d_block            n_cols x 32 bytes little-endian raw chunks (any 256-bit values; reduced mod the group order)
+ *   d_prf              2^(level+2) - 1 PRF outputs of 16 raw bytes: [0] the block's own complement (compute_MAC_complement(0, block_id),
+ *                      :467); then for i = 0 .. level-1 level i's resident complements, X part j = 0 .. 2^i-1, then Y part (the values
+ *                      of :525-534); then the 2 * 2^level new ones of :586-588 in loop order.  A value is read as the reference reads
+ *                      it: KZG a big-endian 128-bit integer (compute_digest_complement), IPA r.d[0], r.d[1] as little-endian 64-bit
+ *                      words (:435-436)
+ *   d_mac_out          64 bytes big-endian affine (zeros = infinity)
+ *   d_complements_out  2 * 2^level points of 64 bytes, X part then Y part
+ *   write_step         the value Client::HAdd sees (after the ++ of :480); level: the level the write lands on; pad must be 0
+ * All four pointers are device memory, 16-byte aligned.  n_cols = the SRS size (KZG) or 128 (IPA); n_total = num_blocks.
+ * Per request, byte for byte the reference's sequence:
+ *   1. comp0 = prf[0] * h; MAC = Commit_alpha(block) + comp0.  KZG: compute_digest of the chunks (alpha f(tau) G1[0]) and h = h_MAC:
+ *      the bytes of porla_kzg_mac_batch_device on the big-endian form of the same chunks.  IPA: sum (chunk_i mod n) *
+ *      alpha_generators[i] over the first 128 points of alpha_generators_fb, h = the one point of h_fb.
+ *   2. cH[i].X[j], cH[i].Y[j] = prf * h for i < level.
+ *   3. Client::HAdd(comp0, level), wt = w^reverse_bits(write_step % n_total, height-1) as the MAC side's scalar: level 0: X[0] = comp0,
+ *      Y[0] = wt * comp0; otherwise X[1] = comp0, Y[1] = wt * comp0 and for i < level the halves of level i mixed into the incoming
+ *      half of level i + 1 (the arithmetic of porla_icc_mac_mix_device, v = w^(n_total / 2^i)), X and Y.  T = the level-`level` result.
+ *   4. out[j] = new_X[j] - T_X[j], out[2^level + j] = new_Y[j] - T_Y[j], j < 2^level.
+ * The pyramid of intermediate complements (4 * 2^level points per part and request) lives in the library's workspace.
+ * Contract: that of porla_*_update_batch_device -- asynchronous on hip_stream, no host wait, no internal side stream; the work waits
+ * for whatever was enqueued on hip_stream before the call and the outputs are complete when the stream is, so the server update batch
+ * can be enqueued right behind it on the same stream and buffers with no synchronisation.  The launch sequence depends on the
+ * highest level of the call, not on k: two fixed-base passes per call (the k block rows; every PRF scalar of the call).
+ * PORLA_ERR_ARG (with a message, before the device is touched): NULL reqs with k > 0; a NULL or misaligned block, prf or output
+ * pointer; n_total not a power of two or < 2; level < 0 or 2^level > n_total / 2; write_step % n_total == 0 (CRebuild's step); pad
+ * != 0; two requests naming the same output pointer; IPA: a NULL base, a BN254 base, alpha_generators_fb with fewer than 128 points,
+ * h_fb without exactly one point.  k = 0 returns 0; KZG without init_key + init_SRS: PORLA_ERR_STATE; no device: PORLA_ERR_NO_DEVICE.
+ * tools/bench_client_update_batch.py times it against the composition of the entry points a caller had before
+ * (profiles/r13_a_client_update_batch.jsonl, DESIGN s4). */
+#define PORLA_CLIENT_UPDATE_REQ_BYTES 48   /* sizeof(porla_client_update_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    const void *d_block;
+    const void *d_prf;
+    void       *d_mac_out;
+    void       *d_complements_out;
+    unsigned long long write_step;
+    int level; int pad;
+} porla_client_update_req;
+int porla_kzg_client_update_batch_device(const porla_client_update_req *reqs, size_t k, size_t n_total, void *hip_stream);
+int porla_ipa_client_update_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb,
+                                         const porla_client_update_req *reqs, size_t k, size_t n_total, void *hip_stream);
+
 /* ---- audit row combine (Server::audit, Server.hpp:790-828) + the scalar part of align_MAC on the result (:531-541) ----
  * B_j = sum_i coeff_i * row_i[j] (exact integer), then aligned_j = B_j mod p_icc, c_j = (aligned_j - B_j) mod q.
  * The challenged rows are addressed inside row stores resident in HBM:

@@ -1,0 +1,279 @@
+// Client::update's preprocessing for K independent writes in ONE asynchronous call (include/porla_gpu.h:
+// porla_kzg_client_update_batch_device / porla_ipa_client_update_batch_device): the block's MAC, the complements of every slot below
+// the level the write lands on, Client::HAdd -> HRebuildX / HRebuildY on them and the differences that go on the wire
+// (porla/Client/Client.hpp:457-614, 921-1038).  Its outputs are what porla_*_update_batch_device takes as d_mac and d_complements; the
+// pyramid of intermediate complements stays in the workspace.  Every step is on the caller's stream, and the launch sequence depends
+// on Lmax = the highest level of the call, never on K:
+//
+//   upload                   one copy of the host-built work list (descriptors with wt, the pyramid's level pointers) from pinned memory
+//   k_cu_expand              chunks -> the K big-endian coefficient rows of the block pass, PRF bytes -> the scalar rows of the h pass
+//   block pass               KZG: k_kzg_eval_rows_lazy and the one-point table of G1[0] (the digest row of
+//                            porla_kzg_digest_batch_device); IPA: alpha_generators_fb over the 128 coefficients of a row -> K points
+//   h pass                   every PRF scalar of the call against the one-point table of the hiding base (128-bit scalars: the upper
+//                            windows are zero digits) -> sum over requests of 2^(level+2) - 1 points
+//   k_cu_scatter             the resident complements into the pyramid
+//   k_cu_place               comp0 and wt * comp0 into level 0, MAC = block commitment + comp0
+//   for i < Lmax:            k_update_mix_points_* with two families (X, Y) of the requests with level > i
+//   k_cu_close               new complement - mixed complement, to affine
+//
+// Both passes leave affine bytes (k_fb_finish: the table's own conversion), which is what the mix bodies read.
+#include "batch_host.hpp"
+#include "client_update_batch.hip.h"
+#include "../../include/porla_gpu.h"
+
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+namespace porla {
+
+constexpr size_t CU_IPA_COLS = 128;            // NUM_CHUNKS: the row width of the IPA build
+
+struct ClientUpdateWs {
+    std::mutex mu;
+    int device = -1;
+    Buf list, rows, scalars, blk, hpts, pyramid;
+    PinnedList h_list;
+    UseFence fence;
+    bool lds_set = false;
+};
+static PerDevice<ClientUpdateWs> g_cu_ws;
+
+template <class C> struct CuCurve;
+template <> struct CuCurve<Bn254G1> { using Q = IccBn254Fr; static constexpr int id = 0; };
+template <> struct CuCurve<Secp256k1G> { using Q = IccSecp256k1Fn; static constexpr int id = 1; };
+
+template <class C>
+static void cu_lds_attributes() {
+    using M = typename C::Fp;
+    auto set = [](const void* f, size_t bytes) { (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+    set(reinterpret_cast<const void*>(&k_cu_place<C>), sizeof(MacOctLds<M>));
+    set(reinterpret_cast<const void*>(&k_update_mix_points_oct<C, 1, 0, CU_PARTS>), sizeof(MacOctLds<M>));
+    set(reinterpret_cast<const void*>(&k_update_mix_points_quad<C, 1, 0, CU_PARTS>), sizeof(MacQuadLds<M>));
+}
+
+struct CuPlan {
+    const CuDesc* d_desc;
+    uint8_t* const* d_ptrs;
+    uint32_t l1, k;
+    hipStream_t stream;
+};
+
+// the mixes of steps 0 .. lmax - 1 under the MAC side's table lease, the form by the step's butterfly count as mac_mix_core picks it
+template <class C>
+static int cu_launch_steps(const CuPlan& P, const std::vector<uint32_t>& active, uint32_t lmax, size_t n_total) {
+    using M = typename C::Fp;
+    const uint32_t* tws = nullptr;
+    int quad_log = 0, rc;
+    if ((rc = mac_mix_tables_acquire(CuCurve<C>::id, n_total, P.stream, &tws, &quad_log))) return rc;
+    for (uint32_t i = 0; i < lmax && !rc; i++) {
+        const uint32_t a = active[i], tw_step = (uint32_t)(n_total >> i);
+        ProfScope ps("client_update_mix", P.stream);
+        const size_t bf = ((size_t)CU_PARTS * a) << i, quad_max = (size_t)1 << quad_log;
+        if (quad_log > 0 && bf <= quad_max && bf <= MACO_MAX_BUTTERFLIES)
+            hipLaunchKernelGGL((k_update_mix_points_oct<C, 1, 0, CU_PARTS>), dim3((unsigned)((bf + MACO_BF - 1) / MACO_BF)), dim3(8 * MACO_BF),
+                               sizeof(MacOctLds<M>), P.stream, P.d_ptrs, P.l1, a, i, tws, tw_step);
+        else if (quad_log > 0 && bf <= quad_max)
+            hipLaunchKernelGGL((k_update_mix_points_quad<C, 1, 0, CU_PARTS>), dim3((unsigned)((bf + MACQ_BF - 1) / MACQ_BF)), dim3(4 * MACQ_BF),
+                               sizeof(MacQuadLds<M>), P.stream, P.d_ptrs, P.l1, a, i, tws, tw_step);
+        else
+            hipLaunchKernelGGL((k_update_mix_points_lane<C, 1, 0, CU_PARTS>), dim3((unsigned)((bf + 63) / 64)), dim3(64), 0, P.stream, P.d_ptrs,
+                               P.l1, a, i, tws, tw_step);
+        if (hipGetLastError() != hipSuccess) { set_last_error("porla: client update batch: a mix launch failed"); rc = PORLA_ERR_HIP; }
+    }
+    const int r1 = mac_mix_tables_release(P.stream);
+    return rc ? rc : r1;
+}
+
+// ws->mu held, ws->fence entered.  fb_alpha == nullptr: the KZG build (the resident key, SRS and hiding base).
+template <class C>
+static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* fb_h, const porla_client_update_req* reqs, size_t k,
+                      size_t ncols, size_t n_total, hipStream_t stream) {
+    using Q = typename CuCurve<C>::Q;
+    int rc;
+    // ---- the plan: requests by level, highest first (stable), so that the requests step i concerns are the first active[i]
+    std::vector<uint32_t> order(k);
+    for (size_t a = 0; a < k; a++) order[a] = (uint32_t)a;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return reqs[x].level > reqs[y].level; });
+    const uint32_t lmax = (uint32_t)reqs[order[0]].level, l1 = lmax + 1;
+    std::vector<uint32_t> active(lmax);
+    for (uint32_t i = 0; i < lmax; i++) {
+        uint32_t a = 0;
+        while (a < k && (uint32_t)reqs[order[a]].level > i) a++;
+        active[i] = a;
+    }
+    // ---- sizes: the h pass' rows, and the pyramid at 4 * 2^level points per part and request
+    size_t n_prf = 0, pyr_pts = 0;
+    for (size_t a = 0; a < k; a++) {
+        n_prf += ((size_t)4 << reqs[a].level) - 1;
+        pyr_pts += (size_t)CU_PARTS * ((size_t)4 << reqs[a].level);
+    }
+    size_t rows_b, scal_b, hpts_b, pyr_b, ptr_b, desc_b;
+    if (n_prf > 0xfffffff0u || !mul_ok(k * ncols, 32, &rows_b) || !mul_ok(n_prf, 32, &scal_b) || !mul_ok(n_prf, 64, &hpts_b) ||
+        !mul_ok(pyr_pts, 64, &pyr_b) || !mul_ok(k * CU_PARTS * l1, sizeof(void*), &ptr_b) || !mul_ok(k, sizeof(CuDesc), &desc_b)) {
+        set_last_error("porla: client update batch: the call's complements do not fit a workspace");
+        return PORLA_ERR_ARG;
+    }
+    const size_t list_b = desc_b + ptr_b;
+    if ((rc = ws->h_list.stage(list_b))) return rc;
+    if ((rc = ws->list.ensure(list_b))) return rc;
+    if ((rc = ws->rows.ensure(rows_b))) return rc;
+    if ((rc = ws->scalars.ensure(scal_b))) return rc;
+    if ((rc = ws->blk.ensure(k * 64))) return rc;
+    if ((rc = ws->hpts.ensure(hpts_b))) return rc;
+    if ((rc = ws->pyramid.ensure(pyr_b))) return rc;
+    // ---- the work list: descriptors | pyramid level pointers, one pinned buffer, one copy
+    {
+        CuDesc* hd = (CuDesc*)ws->h_list.h;
+        void** hp = (void**)((uint8_t*)ws->h_list.h + desc_b);
+        size_t prf0 = 0;
+        uint8_t* pyr = (uint8_t*)ws->pyramid.p;
+        for (size_t a = 0; a < k; a++) {
+            const porla_client_update_req& R = reqs[order[a]];
+            CuDesc& D = hd[a];
+            D.block = (const uint8_t*)R.d_block; D.prf = (const uint8_t*)R.d_prf;
+            D.mac_out = (uint8_t*)R.d_mac_out; D.comp_out = (uint8_t*)R.d_complements_out;
+            uint32_t wt_p[8], wt_q[8];
+            uint8_t be[32];
+            (void)icc_wt_residues(CuCurve<C>::id, n_total, R.write_step, wt_p, wt_q, be);
+            h_load_be(D.wt_sc, be);
+            fe_reduce_plain<Q>(D.wt_sc, 8);                    // the group sees wt mod its order (convert_ZZ_to_scalar / fr.SetBytes)
+            D.level = (uint32_t)R.level; D.prf0 = (uint32_t)prf0;
+            prf0 += ((size_t)4 << R.level) - 1;
+            const size_t part_b = (size_t)256 << R.level;      // 4 * 2^level points
+            for (uint32_t part = 0; part < CU_PARTS; part++, pyr += part_b)
+                for (uint32_t l = 0; l < l1; l++)
+                    hp[(a * CU_PARTS + part) * l1 + l] = l <= (uint32_t)R.level ? pyr + (size_t)128 * (((size_t)1 << l) - 1) : nullptr;
+        }
+    }
+    if (!ws->lds_set) { cu_lds_attributes<Bn254G1>(); cu_lds_attributes<Secp256k1G>(); ws->lds_set = true; }
+    if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
+    CuPlan P;
+    P.d_desc = (const CuDesc*)ws->list.p;
+    P.d_ptrs = (uint8_t* const*)((const uint8_t*)ws->list.p + desc_b);
+    P.l1 = l1; P.k = (uint32_t)k; P.stream = stream;
+    uint8_t* d_rows = (uint8_t*)ws->rows.p;
+    uint8_t* d_scal = (uint8_t*)ws->scalars.p;
+    uint8_t* d_blk = (uint8_t*)ws->blk.p;
+    uint8_t* d_hpts = (uint8_t*)ws->hpts.p;
+    // ---- 1. the rows of the two passes
+    {
+        ProfScope ps("client_update_expand", stream);
+        const size_t items = ncols + ((size_t)4 << lmax) - 1;
+        hipLaunchKernelGGL((k_cu_expand<CuCurve<C>::id == 1>), dim3((unsigned)((items + 255) / 256), (unsigned)k), dim3(256), 0, stream, P.d_desc,
+                           (uint32_t)ncols, d_rows, d_scal);
+        PORLA_HIP(hipGetLastError());
+    }
+    // ---- 2. the block pass and the h pass
+    if constexpr (CuCurve<C>::id == 0) {
+        if ((rc = porla_kzg_digest_batch_device(d_rows, k, d_blk, stream))) return rc;
+        if ((rc = porla_kzg_complement_batch_device(d_scal, n_prf, d_hpts, stream))) return rc;
+    } else {
+        {
+            std::lock_guard<std::mutex> lk(fb_alpha->mu);
+            if ((rc = fb_alpha->commit_device(d_rows, k, ncols, 32 * ncols, d_blk, stream))) return rc;
+        }
+        std::lock_guard<std::mutex> lk(fb_h->mu);
+        if ((rc = fb_h->commit_device(d_scal, n_prf, 1, 32, d_hpts, stream))) return rc;
+    }
+    // ---- 3. level 0 of the pyramid and the MAC
+    if (lmax) {
+        ProfScope ps("client_update_scatter", stream);
+        const size_t units = (((size_t)2 << lmax) - 2) * 4;
+        const unsigned gx = (unsigned)std::min<size_t>((units + 255) / 256, 256);
+        hipLaunchKernelGGL(k_cu_scatter, dim3(gx, (unsigned)k), dim3(256), 0, stream, P.d_desc, P.d_ptrs, l1, d_hpts);
+        PORLA_HIP(hipGetLastError());
+    }
+    {
+        ProfScope ps("client_update_place", stream);
+        hipLaunchKernelGGL((k_cu_place<C>), dim3((unsigned)((k + MACO_BF - 1) / MACO_BF)), dim3(8 * MACO_BF), sizeof(MacOctLds<typename C::Fp>),
+                           stream, P.d_desc, P.d_ptrs, l1, (uint32_t)k, d_blk, d_hpts);
+        PORLA_HIP(hipGetLastError());
+    }
+    // ---- 4. the rebuild steps
+    if (lmax && (rc = cu_launch_steps<C>(P, active, lmax, n_total))) return rc;
+    // ---- 5. the close
+    {
+        ProfScope ps("client_update_close", stream);
+        hipLaunchKernelGGL((k_cu_close<C>), dim3((unsigned)((((size_t)2 << lmax) + 63) / 64), (unsigned)k), dim3(64), 0, stream, P.d_desc,
+                           P.d_ptrs, l1, d_hpts);
+        PORLA_HIP(hipGetLastError());
+    }
+    return PORLA_OK;
+}
+
+// the checks both entry points make before the device is touched
+static int cu_check(const char* who, const porla_client_update_req* reqs, size_t k, size_t n_total) {
+    auto bad = [&](const std::string& what) { return bad_arg(who, what); };
+    if (k && !reqs) return bad("reqs is NULL");
+    int ln = 0;
+    while (((size_t)1 << ln) < n_total && ln < 62) ln++;
+    if (n_total < 2 || ((size_t)1 << ln) != n_total || n_total > ((size_t)1 << 30)) return bad("n_total must be a power of two, 2 .. 2^30");
+    if (k > 0xffffu) return bad("more than 65535 requests in one call");
+    std::unordered_set<const void*> seen;
+    for (size_t a = 0; a < k; a++) {
+        const porla_client_update_req& R = reqs[a];
+        const std::string at = "request " + std::to_string(a) + ": ";
+        if (!R.d_block || !R.d_prf || !R.d_mac_out || !R.d_complements_out) return bad(at + "a NULL block, prf or output pointer");
+        if ((((uintptr_t)R.d_block | (uintptr_t)R.d_prf | (uintptr_t)R.d_mac_out | (uintptr_t)R.d_complements_out) & 15u) != 0)
+            return bad(at + "a block, prf or output pointer that is not 16-byte aligned");
+        if (R.pad != 0) return bad(at + "pad must be 0");
+        if (R.level < 0 || R.level > 29 || ((size_t)1 << R.level) > n_total / 2) return bad(at + "level must be 0 .. log2(n_total) - 1");
+        if (R.write_step % n_total == 0) return bad(at + "write_step % n_total == 0 is CRebuild's step, not an H update");
+        if (!seen.insert(R.d_mac_out).second || !seen.insert(R.d_complements_out).second)
+            return bad(at + "an output pointer another request (or output) of this call names too");
+    }
+    return PORLA_OK;
+}
+
+}  // namespace porla
+
+using namespace porla;
+
+static_assert(sizeof(porla_client_update_req) == PORLA_CLIENT_UPDATE_REQ_BYTES, "porla_client_update_req size");
+static_assert(offsetof(porla_client_update_req, d_block) == 0 && offsetof(porla_client_update_req, d_prf) == 8 &&
+              offsetof(porla_client_update_req, d_mac_out) == 16 && offsetof(porla_client_update_req, d_complements_out) == 24 &&
+              offsetof(porla_client_update_req, write_step) == 32 && offsetof(porla_client_update_req, level) == 40 &&
+              offsetof(porla_client_update_req, pad) == 44,
+              "porla_client_update_req offsets (include/porla_gpu.h)");
+
+extern "C" int porla_kzg_client_update_batch_device(const porla_client_update_req* reqs, size_t k, size_t n_total, void* hip_stream) {
+    int rc = cu_check("porla_kzg_client_update_batch_device", reqs, k, n_total);
+    if (rc) return rc;
+    if (k == 0) return PORLA_OK;
+    if ((rc = ensure_device())) return rc;
+    // the key and the SRS, before any device work: an empty digest batch makes exactly that check
+    if ((rc = porla_kzg_digest_batch_device(nullptr, 0, nullptr, nullptr))) return rc;
+    size_t n = 0;
+    if ((rc = porla_kzg_row_coefficients(&n))) return rc;
+    if (n == 0) { set_last_error("porla: SRS not initialised (call init_SRS / init_SRS_from_data first)"); return PORLA_ERR_STATE; }
+    if (n > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
+    ClientUpdateWs* ws = nullptr;
+    if ((rc = g_cu_ws.get(&ws))) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    return FencedCall(ws, stream).run([&] { return cu_enqueue<Bn254G1>(ws, nullptr, nullptr, reqs, k, n, n_total, stream); });
+}
+
+extern "C" int porla_ipa_client_update_batch_device(porla_fixed_base* alpha_generators_fb, porla_fixed_base* h_fb,
+                                                    const porla_client_update_req* reqs, size_t k, size_t n_total, void* hip_stream) {
+    static const char* who = "porla_ipa_client_update_batch_device";
+    int rc = cu_check(who, reqs, k, n_total);
+    if (rc) return rc;
+    if (k == 0) return PORLA_OK;
+    if (!alpha_generators_fb || !h_fb) return bad_arg(who, "a NULL base");
+    if ((rc = ensure_device())) return rc;
+    // (a handle exists only where a device does: it is read after ensure_device, and still before any device work)
+    if (alpha_generators_fb->curve != 1 || alpha_generators_fb->secp.n_points < CU_IPA_COLS)
+        return bad_arg(who, "alpha_generators_fb must be a secp256k1 fixed base over at least the 128 generators");
+    if (h_fb->curve != 1 || h_fb->secp.n_points != 1) return bad_arg(who, "h_fb must be a secp256k1 fixed base over exactly one point");
+    ClientUpdateWs* ws = nullptr;
+    if ((rc = g_cu_ws.get(&ws))) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    return FencedCall(ws, stream).run([&] {
+        return cu_enqueue<Secp256k1G>(ws, &alpha_generators_fb->secp, &h_fb->secp, reqs, k, CU_IPA_COLS, n_total, stream);
+    });
+}

@@ -112,50 +112,53 @@ k_update_mix_data(uint8_t* const* __restrict__ ptrs, uint32_t l1, uint32_t activ
     icc30_mix_elem<Q>(a0, a0 + per * 64, e, len, ncols, tw30, tw_step, out);
 }
 
-// ---- step i, the four point families (MAC X, MAC Y, align X, align Y) of the first `active` requests: butterfly g of the step belongs
-// to item g >> i = (request, family) and is row g & (2^i - 1) of it.  FORM 8 / 4 / 1: lanes per butterfly, the forms of mac_mix_core.
-template <class C>
+// ---- step i, the point families of the first `active` requests: butterfly g of the step belongs to item g >> i = (request, family)
+// and is row g & (2^i - 1) of it.  FORM 8 / 4 / 1: lanes per butterfly, the forms of mac_mix_core.  A request's point families are
+// 2^LOGF consecutive ones from FIRST on, of STRIDE families per request in the pointer table: the server's four (MAC X, MAC Y,
+// align X, align Y) of its six by default; the client update batch (client_update_batch.hip.h) mixes its two complement parts.
+template <class C, uint32_t LOGF, uint32_t FIRST, uint32_t STRIDE>
 __device__ __forceinline__ void upd_point_item(uint8_t* const* __restrict__ ptrs, uint32_t l1, uint32_t i, uint32_t g, const uint8_t*& a0,
                                                uint8_t*& out, uint32_t& row) {
     const uint32_t item = g >> i;
     row = g & ((1u << i) - 1u);
-    a0 = upd_level(ptrs, l1, item >> 2, UPD_MAC_X + (item & 3u), i);
-    out = upd_level(ptrs, l1, item >> 2, UPD_MAC_X + (item & 3u), i + 1) + ((size_t)128 << i);
+    uint8_t* const* lv = ptrs + ((size_t)(item >> LOGF) * STRIDE + FIRST + (item & ((1u << LOGF) - 1u))) * l1 + i;
+    a0 = lv[0];
+    out = lv[1] + ((size_t)128 << i);
 }
-template <class C>
+template <class C, uint32_t LOGF = 2, uint32_t FIRST = UPD_MAC_X, uint32_t STRIDE = UPD_FAMILIES>
 __global__ void __launch_bounds__(8 * MACO_BF) MACO_ATTR
 k_update_mix_points_oct(uint8_t* const* __restrict__ ptrs, uint32_t l1, uint32_t active, uint32_t i, const uint32_t* __restrict__ tws,
                         uint32_t tw_step) {
     using M = typename C::Fp;
     MACO_LDS(L);
     uint32_t g = blockIdx.x * MACO_BF + (threadIdx.x >> 3);
-    const bool valid = g < ((4u * active) << i);
+    const bool valid = g < ((active << LOGF) << i);
     if (!valid) g = 0;
     const uint8_t* a0; uint8_t* out; uint32_t row;
-    upd_point_item<C>(ptrs, l1, i, g, a0, out, row);
+    upd_point_item<C, LOGF, FIRST, STRIDE>(ptrs, l1, i, g, a0, out, row);
     maco_mix_one<C>(L, a0, a0 + ((size_t)64 << i), row, 1u << i, valid, tws, tw_step, out);
 }
-template <class C>
+template <class C, uint32_t LOGF = 2, uint32_t FIRST = UPD_MAC_X, uint32_t STRIDE = UPD_FAMILIES>
 __global__ void __launch_bounds__(4 * MACQ_BF) MACQ_GUEST_ATTR
 k_update_mix_points_quad(uint8_t* const* __restrict__ ptrs, uint32_t l1, uint32_t active, uint32_t i, const uint32_t* __restrict__ tws,
                          uint32_t tw_step) {
     using M = typename C::Fp;
     MACQ_LDS(L);
     uint32_t g = blockIdx.x * MACQ_BF + (threadIdx.x >> 2);
-    const bool valid = g < ((4u * active) << i);
+    const bool valid = g < ((active << LOGF) << i);
     if (!valid) g = 0;
     const uint8_t* a0; uint8_t* out; uint32_t row;
-    upd_point_item<C>(ptrs, l1, i, g, a0, out, row);
+    upd_point_item<C, LOGF, FIRST, STRIDE>(ptrs, l1, i, g, a0, out, row);
     macq_mix_one<C>(L, a0, a0 + ((size_t)64 << i), row, 1u << i, valid, tws, tw_step, out);
 }
-template <class C>
+template <class C, uint32_t LOGF = 2, uint32_t FIRST = UPD_MAC_X, uint32_t STRIDE = UPD_FAMILIES>
 __global__ void __launch_bounds__(64)
 k_update_mix_points_lane(uint8_t* const* __restrict__ ptrs, uint32_t l1, uint32_t active, uint32_t i, const uint32_t* __restrict__ tws,
                          uint32_t tw_step) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= ((4u * active) << i)) return;
+    if (g >= ((active << LOGF) << i)) return;
     const uint8_t* a0; uint8_t* out; uint32_t row;
-    upd_point_item<C>(ptrs, l1, i, g, a0, out, row);
+    upd_point_item<C, LOGF, FIRST, STRIDE>(ptrs, l1, i, g, a0, out, row);
     mac_mix_one<C>(a0, a0 + ((size_t)64 << i), row, 1u << i, tws, tw_step, out);
 }
 

@@ -51,6 +51,17 @@ PORLA_UPDATE_REQ_BYTES = 88
 assert ctypes.sizeof(UpdateReq) == PORLA_UPDATE_REQ_BYTES
 
 
+class ClientUpdateReq(ctypes.Structure):
+    """porla_client_update_req, include/porla_gpu.h: one write of porla_kzg_client_update_batch_device /
+    porla_ipa_client_update_batch_device (PORLA_CLIENT_UPDATE_REQ_BYTES = 48)."""
+    _fields_ = [("d_block", ctypes.c_void_p), ("d_prf", ctypes.c_void_p), ("d_mac_out", ctypes.c_void_p),
+                ("d_complements_out", ctypes.c_void_p), ("write_step", ctypes.c_ulonglong), ("level", ctypes.c_int), ("pad", ctypes.c_int)]
+
+
+PORLA_CLIENT_UPDATE_REQ_BYTES = 48
+assert ctypes.sizeof(ClientUpdateReq) == PORLA_CLIENT_UPDATE_REQ_BYTES
+
+
 def load():
     """Load the engine.  When torch is importable it is imported FIRST so that the HIP runtime the process
     ends up with is the one torch ships (both have soname libamdhip64.so.7; two runtimes in one process
@@ -159,6 +170,10 @@ def _declare(L):
     L.porla_ipa_audit_batch_device.restype = ctypes.c_int
     L.porla_kzg_update_batch_device.argtypes = [ctypes.POINTER(UpdateReq), sz, sz, vp]; L.porla_kzg_update_batch_device.restype = ctypes.c_int
     L.porla_ipa_update_batch_device.argtypes = [vp, ctypes.POINTER(UpdateReq), sz, sz, vp]; L.porla_ipa_update_batch_device.restype = ctypes.c_int
+    L.porla_kzg_client_update_batch_device.argtypes = [ctypes.POINTER(ClientUpdateReq), sz, sz, vp]
+    L.porla_kzg_client_update_batch_device.restype = ctypes.c_int
+    L.porla_ipa_client_update_batch_device.argtypes = [vp, vp, ctypes.POINTER(ClientUpdateReq), sz, sz, vp]
+    L.porla_ipa_client_update_batch_device.restype = ctypes.c_int
     L.porla_ipa_prove_batch_device.argtypes = [vp, vp, vp, sz, vp, vp]; L.porla_ipa_prove_batch_device.restype = ctypes.c_int
     L.porla_ipa_verify_batch_device.argtypes = [vp, ctypes.POINTER(IpaVerifyReq), sz, vp, vp, vp]
     L.porla_ipa_verify_batch_device.restype = ctypes.c_int

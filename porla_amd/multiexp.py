@@ -303,6 +303,28 @@ def jac_sum(curve, jacobians, count):
     return out.raw
 
 
+# ---- Client::update's preprocessing for K writes in one asynchronous call (include/porla_gpu.h: porla_*_client_update_batch_device) ----
+def client_update_requests(reqs):
+    """a ctypes array of porla_client_update_req from per-write tuples (d_block, d_prf, d_mac_out, d_complements_out, write_step,
+    level): device addresses as integers"""
+    from .loader import ClientUpdateReq
+    arr = (ClientUpdateReq * max(len(reqs), 1))()
+    for i, r in enumerate(reqs):
+        if len(r) != 6:
+            raise ValueError("client_update_batch_device: request %d has %d fields, want 6" % (i, len(r)))
+        arr[i] = ClientUpdateReq(r[0] or None, r[1] or None, r[2] or None, r[3] or None, r[4], r[5], 0)
+    return arr
+
+
+def kzg_client_update_batch_device(reqs, n_total, stream=0):
+    """Client::update's preprocessing (the block's MAC, the complements below the write's level through HAdd / HRebuildX / HRebuildY,
+    the differences that go on the wire) of len(reqs) independent writes in ONE asynchronous call on `stream`, KZG build: d_mac_out
+    and d_complements_out of every request are what icc.kzg_update_batch_device takes as d_mac and d_complements.  `reqs`: tuples as
+    client_update_requests takes them."""
+    arr = client_update_requests(reqs)
+    _check(lib.porla_kzg_client_update_batch_device(arr, len(reqs), n_total, ctypes.c_void_p(stream)))
+
+
 # ---- batched fixed-base commitments (include/porla_gpu.h) ------------------------------------------
 CURVES = {"bn254": 0, "secp256k1": 1}
 
@@ -356,6 +378,14 @@ class FixedBase:
         from .icc import update_requests
         arr = update_requests(reqs)
         _check(lib.porla_ipa_update_batch_device(self.h, arr, len(reqs), n_total, ctypes.c_void_p(stream)))
+
+    def ipa_client_update_batch_device(self, h_fb, reqs, n_total, stream=0):
+        """Client::update's preprocessing of len(reqs) independent writes in ONE asynchronous call on `stream`, IPA build
+        (porla_ipa_client_update_batch_device); self = a secp256k1 fixed base whose first 128 points are the alpha generators, h_fb = a
+        FixedBase over the one hiding point.  `reqs`: tuples as client_update_requests takes them."""
+        arr = client_update_requests(reqs)
+        _check(lib.porla_ipa_client_update_batch_device(self.h, h_fb.h if h_fb is not None else None, arr, len(reqs), n_total,
+                                                        ctypes.c_void_p(stream)))
 
     def ipa_prove_batch_device(self, d_a, d_b, k, d_proofs, stream=0):
         """k proofs of Server::inner_product_prove(a, b) in ONE asynchronous call (porla_ipa_prove_batch_device): d_a, d_b = k x 128 x
