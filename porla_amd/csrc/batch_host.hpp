@@ -23,6 +23,11 @@ struct PerDevice {
         *out = w;
         return PORLA_OK;
     }
+    // every workspace made so far: a walk over all devices works on the copy, outside the registry's lock
+    std::vector<Ws*> snapshot() {
+        std::lock_guard<std::mutex> lk(mu);
+        return all;
+    }
 };
 
 static inline bool mul_ok(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
@@ -62,14 +67,20 @@ struct FencedCall {
 
 // one commitment pass over n_rows contiguous rows of n_coeffs coefficients, sums left projective in the table's partials, and
 // `then(sums, S)` (row r at sums[r S]) enqueued under the table's lock before its fence is recorded again: the partials hold only the
-// LAST pass's sums, and another caller's pass may follow as soon as the lock is let go
+// LAST pass's sums, and another caller's pass may follow as soon as the lock is let go.  The _locked form is for a caller that holds
+// fb.mu already (the resident SRS table behind its guard, kzg_state.hpp).
+template <class C, class Then>
+static int commit_then_locked(FixedBase<C>& fb, const uint8_t* d_rows, size_t n_rows, size_t n_coeffs, hipStream_t stream, Then then) {
+    int rc;
+    if ((rc = fb.commit_device(d_rows, n_rows, n_coeffs, 32 * n_coeffs, nullptr, stream))) return rc;
+    // the table's fence was recorded behind the commit; `then` reads the partials after it, so the fence moves behind `then`
+    if ((rc = then((const XYZZ<typename C::Fp>*)fb.partial, fb.last_S))) return rc;
+    return fb.fence.leave(stream);
+}
 template <class C, class Then>
 static int commit_then(FixedBase<C>& fb, const uint8_t* d_rows, size_t n_rows, size_t n_coeffs, hipStream_t stream, Then then) {
     std::lock_guard<std::mutex> lk(fb.mu);
-    int rc;
-    if ((rc = fb.commit_device(d_rows, n_rows, n_coeffs, 32 * n_coeffs, nullptr, stream))) return rc;
-    if ((rc = then((const XYZZ<typename C::Fp>*)fb.partial, fb.last_S))) return rc;
-    return fb.fence.leave(stream);
+    return commit_then_locked(fb, d_rows, n_rows, n_coeffs, stream, then);
 }
 
 }  // namespace porla

@@ -17,7 +17,7 @@
 //   k_cu_close               new complement - mixed complement, to affine
 //
 // Both passes leave affine bytes (k_fb_finish: the table's own conversion), which is what the mix bodies read.
-#include "batch_host.hpp"
+#include "kzg_state.hpp"
 #include "client_update_batch.hip.h"
 #include "../../include/porla_gpu.h"
 
@@ -248,9 +248,8 @@ extern "C" int porla_kzg_client_update_batch_device(const porla_client_update_re
     if ((rc = ensure_device())) return rc;
     // the key and the SRS, before any device work: an empty digest batch makes exactly that check
     if ((rc = porla_kzg_digest_batch_device(nullptr, 0, nullptr, nullptr))) return rc;
-    size_t n = 0;
-    if ((rc = porla_kzg_row_coefficients(&n))) return rc;
-    if (n == 0) { set_last_error("porla: SRS not initialised (call init_SRS / init_SRS_from_data first)"); return PORLA_ERR_STATE; }
+    const size_t n = kzg_n_samples();
+    if (n == 0) return kzg_no_srs();
     if (n > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
     ClientUpdateWs* ws = nullptr;
     if ((rc = g_cu_ws.get(&ws))) return rc;

@@ -345,15 +345,5 @@ int audit_combine_batch_launch(const KzgAuditDesc* d_desc, const uint32_t* d_blk
                                hipStream_t stream);
 size_t audit_combine_partial_bytes(uint32_t n_blocks, uint32_t n_cols);
 constexpr uint32_t AUDIT_BATCH_SLICES = 8;   // row slices per block of the batched combine (audit.hip: AUD_SLICES)
-// kzg_abi.hip: commit n_rows contiguous rows of n_samples coefficients against the resident SRS table, leave the row sums in the
-// table's partials, and run `then(sums, S)` (row r at sums[r * S]) under the table's lock before its fence is recorded again
-int kzg_commit_rows_raw(const uint8_t* d_rows, size_t n_rows, hipStream_t stream,
-                        int (*then)(const XYZZ<Bn254Fp>* sums, uint32_t S, void* ctx), void* ctx);
-// kzg_abi.hip, for the batched verifier (kzg_verify_batch.hip): G1[0] as 64 bytes big-endian affine, PORLA_ERR_STATE without an SRS
-// and its G2 points; verify_proof's predicate on a record's commitment | proof_h | point | claim (192 bytes), without its message;
-// and the folded check e(P, G2[0]) * e(-Q, G2[1]) == 1 over 64-byte big-endian affine P and Q (coordinates < p)
-int kzg_verify_base(uint8_t g_be[64]);
-bool kzg_opening_holds(const uint8_t rec[192]);
-bool kzg_folded_opening_holds(const uint8_t p_be[64], const uint8_t q_be[64]);
 
 }  // namespace porla

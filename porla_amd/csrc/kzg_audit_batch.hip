@@ -13,7 +13,7 @@
 //   fb_commit / fb_fold   ONE commitment pass over the 3K rows against the resident SRS table, projective sums kept
 //   k_kzg_audit_join      per audit: align_value + MSM(align) (align_MAC, Server.hpp:903), the four points of the record to affine
 //                         with one inversion, the 320-byte record
-#include "engine.hpp"
+#include "kzg_state.hpp"
 #include "icc.hip.h"
 #include "kzg_batch.hip.h"
 #include "../../include/porla_gpu.h"
@@ -141,15 +141,6 @@ struct KzgAuditBatchWs {
 };
 static PerDevice<KzgAuditBatchWs> g_kab_ws;
 
-struct JoinArgs { const XYZZ<Bn254Fp>* msm; uint32_t k; uint8_t* out; hipStream_t stream; };
-static int launch_join(const XYZZ<Bn254Fp>* sums, uint32_t S, void* ctx) {
-    const JoinArgs* j = (const JoinArgs*)ctx;
-    ProfScope ps("kzg_audit_join", j->stream);
-    hipLaunchKernelGGL(k_kzg_audit_join, dim3((j->k + 63) / 64), dim3(64), 0, j->stream, sums, S, j->msm, j->k, j->out);
-    PORLA_HIP(hipGetLastError());
-    return PORLA_OK;
-}
-
 // ws->mu held, ws->fence entered
 static int audit_batch_enqueue(KzgAuditBatchWs* ws, const porla_kzg_audit_req* reqs, size_t k, size_t n, uint8_t* d_out, uint8_t* d_b_out,
                                hipStream_t stream) {
@@ -196,8 +187,12 @@ static int audit_batch_enqueue(KzgAuditBatchWs* ws, const porla_kzg_audit_req* r
     if ((rc = msm_batch_sums_device<Bn254G1>((const uint8_t*)ws->msm_sc.p, (const uint8_t*)ws->msm_pt.p, P.offsets.data(), 2 * k, msm_sums, stream)))
         return rc;
     // ---- 4. the 3K commitments, then 5. the join into the records
-    JoinArgs j = {msm_sums, (uint32_t)k, d_out, stream};
-    return kzg_commit_rows_raw(rows3, 3 * k, stream, launch_join, &j);
+    return kzg_commit_rows_raw(rows3, 3 * k, stream, [&](const XYZZ<Bn254Fp>* sums, uint32_t S) {
+        ProfScope ps("kzg_audit_join", stream);
+        hipLaunchKernelGGL(k_kzg_audit_join, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, stream, sums, S, msm_sums, (uint32_t)k, d_out);
+        PORLA_HIP(hipGetLastError());
+        return PORLA_OK;
+    });
 }
 
 }  // namespace porla
@@ -226,9 +221,8 @@ extern "C" int porla_kzg_audit_batch_device(const porla_kzg_audit_req* reqs, siz
     if (!mul_ok(k, 3 * 32 * 65536, &pt_b) || !mul_ok((size_t)pairs, 96, &pt_b)) return bad_arg(who, "the batch's byte size overflows");
     if (k == 0) return PORLA_OK;
     if ((rc = ensure_device())) return rc;
-    size_t n = 0;
-    if ((rc = porla_kzg_row_coefficients(&n))) return rc;
-    if (n == 0) { set_last_error("porla: SRS not initialised (call init_SRS / init_SRS_from_data first)"); return PORLA_ERR_STATE; }
+    const size_t n = kzg_n_samples();
+    if (n == 0) return kzg_no_srs();
     if (n > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
     KzgAuditBatchWs* ws = nullptr;
     if ((rc = g_kab_ws.get(&ws))) return rc;

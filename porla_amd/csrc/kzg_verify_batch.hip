@@ -14,7 +14,7 @@
 //   batch_*              the batched MSM over the 2K + 2 entries (msm_batch_impl.hip.h), projective sums kept
 //   k_kzg_verify_join    a lane per reply: complement sum + 3-pair sum = O ? -> FULL; one more lane: P and Q to affine with one inversion
 //   copy back            P | Q | K flag bytes, then ONE host pairing; only when it fails, verify_proof's predicate per reply
-#include "engine.hpp"
+#include "kzg_state.hpp"
 #include "icc.hip.h"
 #include "kzg_batch.hip.h"
 #include "../../include/porla_gpu.h"

@@ -10,7 +10,7 @@
 //   k_update_place           MAC X, MAC Y = wt * MAC, align X = infinity, align Y = Commit(c)
 //   for i < Lmax:            k_update_mix_data (both parts) and k_update_mix_points (the four point families) of the requests with level > i
 //   k_update_close           incoming half over resident half at the request's level, then the complements onto MAC X / MAC Y
-#include "batch_host.hpp"
+#include "kzg_state.hpp"
 #include "update_batch.hip.h"
 #include "../../include/porla_gpu.h"
 
@@ -68,7 +68,6 @@ static int launch_place(const UpdPlan& P, const XYZZ<typename C::Fp>* sums, uint
     PORLA_HIP(hipGetLastError());
     return PORLA_OK;
 }
-static int place_after_srs(const XYZZ<Bn254Fp>* sums, uint32_t S, void* ctx) { return launch_place<Bn254G1>(*(const UpdPlan*)ctx, sums, S); }
 
 // the mixes of steps 0 .. lmax - 1 under the table leases (the MAC side's lock first, as mac_fft.hip's matrix form takes them)
 template <class C>
@@ -159,13 +158,10 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
         PORLA_HIP(hipGetLastError());
     }
     // ---- 2. the K commitments, then the four point slots
-    if constexpr (UpdCurve<C>::id == 0) {
-        if ((rc = kzg_commit_rows_raw((const uint8_t*)ws->scalars.p, k, stream, place_after_srs, &P))) return rc;
-    } else {
-        rc = commit_then(*fb, (const uint8_t*)ws->scalars.p, k, ncols, stream,
-                         [&](const XYZZ<typename C::Fp>* sums, uint32_t S) { return launch_place<C>(P, sums, S); });
-        if (rc) return rc;
-    }
+    auto place = [&](const XYZZ<typename C::Fp>* sums, uint32_t S) { return launch_place<C>(P, sums, S); };
+    if constexpr (UpdCurve<C>::id == 0) rc = kzg_commit_rows_raw((const uint8_t*)ws->scalars.p, k, stream, place);
+    else rc = commit_then(*fb, (const uint8_t*)ws->scalars.p, k, ncols, stream, place);
+    if (rc) return rc;
     // ---- 3. the rebuild steps
     if (lmax && (rc = launch_steps<C>(P, active, lmax, n_total))) return rc;
     // ---- 4. the close
@@ -223,9 +219,8 @@ extern "C" int porla_kzg_update_batch_device(const porla_update_req* reqs, size_
     if (rc) return rc;
     if (k == 0) return PORLA_OK;
     if ((rc = ensure_device())) return rc;
-    size_t n = 0;
-    if ((rc = porla_kzg_row_coefficients(&n))) return rc;
-    if (n == 0) { set_last_error("porla: SRS not initialised (call init_SRS / init_SRS_from_data first)"); return PORLA_ERR_STATE; }
+    const size_t n = kzg_n_samples();
+    if (n == 0) return kzg_no_srs();
     if (n > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
     UpdateBatchWs* ws = nullptr;
     if ((rc = g_upd_ws.get(&ws))) return rc;

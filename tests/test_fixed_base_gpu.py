@@ -285,6 +285,119 @@ def test_digest_batch_row_lengths(mx, n_coeffs):
     mx.init_SRS(128)
 
 
+def _client_batches(mx, rows, scal, n_rows):
+    """the digest and the MAC batch of n_rows rows on the current stream, synchronised: (digests, macs)"""
+    import torch
+    s = torch.cuda.current_stream().cuda_stream
+    d_rows = torch.frombuffer(bytearray(rows), dtype=torch.uint8).cuda()
+    d_sc = torch.frombuffer(bytearray(scal), dtype=torch.uint8).cuda()
+    d_dig = torch.empty(64 * n_rows, dtype=torch.uint8, device="cuda")
+    d_mac = torch.empty(64 * n_rows, dtype=torch.uint8, device="cuda")
+    mx.kzg_digest_batch_device(d_rows.data_ptr(), n_rows, d_dig.data_ptr(), s)
+    mx.kzg_mac_batch_device(d_rows.data_ptr(), d_sc.data_ptr(), n_rows, d_mac.data_ptr(), s)
+    torch.cuda.synchronize()
+    return bytes(d_dig.cpu().numpy()), bytes(d_mac.cpu().numpy())
+
+
+@pytest.mark.parametrize("n_coeffs", [7, 1024, 1025])
+def test_mac_batch_row_lengths(mx, n_coeffs):
+    """the MAC batch at row lengths other than 128: the second scalar rides along in both evaluation kernels (the dot-product form up
+    to 1024 coefficients, the Horner form beyond), 19 rows leave a ragged last wave whose idle lanes redo the last row; a
+    coefficient >= r and an all-ones one in row 0, a scalar >= r and a zero scalar; every row against the host symbols"""
+    n_rows = 19
+    rows = bytearray(hashlib.shake_256(b"maclen%d" % n_coeffs).digest(32 * n_coeffs * n_rows))
+    rows[0:32] = b"\xff" * 32
+    rows[32 * (n_coeffs - 1):32 * n_coeffs] = (R + 1).to_bytes(32, "big")
+    rows = bytes(rows)
+    scal = bytearray(hashlib.shake_256(b"macsc%d" % n_coeffs).digest(32 * n_rows))
+    scal[32 * 3:32 * 4] = bytes(32)
+    scal[32 * 5:32 * 6] = (R + 9).to_bytes(32, "big")
+    scal = bytes(scal)
+    mx.init_key(TAU, ALPHA)
+    mx.init_SRS(n_coeffs)
+    try:
+        dig, mac = _client_batches(mx, rows, scal, n_rows)
+        for r in range(n_rows):
+            want = mx.compute_digest(rows[32 * n_coeffs * r:32 * n_coeffs * (r + 1)])
+            assert dig[64 * r:64 * r + 64] == want, (n_coeffs, r)
+            assert mac[64 * r:64 * r + 64] == mx.bn254_add(want, mx.compute_digest_complement(scal[32 * r:32 * r + 32])), (n_coeffs, r)
+    finally:
+        mx.init_key(TAU, ALPHA)
+        mx.init_SRS(128)
+
+
+def test_client_batches_past_one_trip_of_the_stride_loop(mx):
+    """65 536 + 40 rows of 9 coefficients: the dot-product kernel's 2 048 blocks take 32 rows a trip, so blocks 0 and 1 make a second
+    trip and the second of them has a ragged group of 8 rows; rows 0, 65 535, 65 536, the last one and 32 drawn with a fixed seed
+    against the host symbols, and on every row the MAC is the digest batch's point plus the complement batch's"""
+    import random
+    import torch
+    n_coeffs, n_rows = 9, 65536 + 40
+    rows = hashlib.shake_256(b"stride-rows").digest(32 * n_coeffs * n_rows)
+    scal = hashlib.shake_256(b"stride-scalars").digest(32 * n_rows)
+    mx.init_key(TAU, ALPHA)
+    mx.init_SRS(n_coeffs)
+    try:
+        dig, mac = _client_batches(mx, rows, scal, n_rows)
+        d_sc = torch.frombuffer(bytearray(scal), dtype=torch.uint8).cuda()
+        d_comp = torch.empty(64 * n_rows, dtype=torch.uint8, device="cuda")
+        mx.kzg_complement_batch_device(d_sc.data_ptr(), n_rows, d_comp.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        comp = bytes(d_comp.cpu().numpy())
+        for r in [0, 65535, 65536, n_rows - 1] + random.Random(20240).sample(range(n_rows), 32):
+            want = mx.compute_digest(rows[32 * n_coeffs * r:32 * n_coeffs * (r + 1)])
+            assert dig[64 * r:64 * r + 64] == want, r
+            assert mac[64 * r:64 * r + 64] == mx.bn254_add(want, mx.compute_digest_complement(scal[32 * r:32 * r + 32])), r
+        bad = [r for r in range(n_rows) if mac[64 * r:64 * r + 64] != mx.bn254_add(dig[64 * r:64 * r + 64], comp[64 * r:64 * r + 64])]
+        assert not bad, bad[:8]
+    finally:
+        mx.init_key(TAU, ALPHA)
+        mx.init_SRS(128)
+
+
+def test_client_batches_on_two_streams_share_the_evaluation_scratch(mx):
+    """the three client tables share one evaluation scratch, ordered by the tables' fences: a 40-row digest batch held in flight on
+    stream A, a 300-row MAC batch on stream B with nothing awaited, a 40-row complement batch on A again -- no host
+    synchronisation in between -- give the bytes of single, synchronised calls; then once more with the streams' roles swapped"""
+    import torch
+    mx.init_key(TAU, ALPHA)
+    mx.init_SRS(128)
+    dev = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).cuda()    # noqa: E731
+    d_rows300, d_sc300 = dev(rows_bytes(300, 128, b"two-mac")), dev(rows_bytes(300, 1, b"two-mac-sc"))
+    d_rows40, d_sc40 = dev(rows_bytes(40, 128, b"two-dig")), dev(rows_bytes(40, 1, b"two-comp"))
+    outs = [torch.empty(64 * n, dtype=torch.uint8, device="cuda") for n in (40, 300, 40)]
+
+    def issue(sa, sb):
+        mx.kzg_digest_batch_device(d_rows40.data_ptr(), 40, outs[0].data_ptr(), sa.cuda_stream)
+        mx.kzg_mac_batch_device(d_rows300.data_ptr(), d_sc300.data_ptr(), 300, outs[1].data_ptr(), sb.cuda_stream)
+        mx.kzg_complement_batch_device(d_sc40.data_ptr(), 40, outs[2].data_ptr(), sa.cuda_stream)
+
+    # the expected bytes (and the warm scratch: the 300-row MAC batch is the largest user): every call alone and awaited
+    cur = torch.cuda.current_stream()
+    mx.kzg_mac_batch_device(d_rows300.data_ptr(), d_sc300.data_ptr(), 300, outs[1].data_ptr(), cur.cuda_stream)
+    torch.cuda.synchronize()
+    want = []
+    for i, call in enumerate((lambda: mx.kzg_digest_batch_device(d_rows40.data_ptr(), 40, outs[0].data_ptr(), cur.cuda_stream),
+                              lambda: mx.kzg_mac_batch_device(d_rows300.data_ptr(), d_sc300.data_ptr(), 300, outs[1].data_ptr(), cur.cuda_stream),
+                              lambda: mx.kzg_complement_batch_device(d_sc40.data_ptr(), 40, outs[2].data_ptr(), cur.cuda_stream))):
+        call()
+        torch.cuda.synchronize()
+        want.append(bytes(outs[i].cpu().numpy()))
+    assert want[0][:64] == mx.compute_digest(bytes(d_rows40[:4096].cpu().numpy()))
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    ballast = torch.empty(1 << 26, dtype=torch.float32, device="cuda")
+    for sa, sb in ((s1, s2), (s2, s1)):
+        for o in outs:
+            o.zero_()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(sa):
+            for _ in range(4):
+                ballast.normal_()                   # a few milliseconds ahead of the digest batch on its stream
+        issue(sa, sb)
+        torch.cuda.synchronize()
+        assert [bytes(o.cpu().numpy()) for o in outs] == want
+
+
 def test_eight_threads_call_the_plugin_concurrently(mx, srs128):
     """the server calls compute_digest_from_srs / add_point / mult_point / neg_point from 8 pool threads at once
     (porla/Server/Server.hpp:1054-1078, 1530-1535, 1600-1608); ctypes releases the GIL, so these really overlap"""

@@ -27,7 +27,7 @@ for name in ("fetch", "write"):
     for f in files:
         for row in csv.DictReader(open(f)):
             k = row.get("Kernel_Name", "?")
-            if k.startswith("(anonymous namespace)::"):      # kernels of an unnamed namespace (kzg_abi.hip)
+            if k.startswith("(anonymous namespace)::"):      # kernels of an unnamed namespace (kzg_client_batch.hip)
                 k = k[len("(anonymous namespace)::"):]
             k = k.split("(")[0]
             agg[(k, row.get("Counter_Name"))][0] += float(row.get("Counter_Value", 0))
