@@ -616,6 +616,7 @@ int porla_icc_mac_hrebuild_host(uint8_t *const *levels, int level, size_t n_tota
  *   d_mac          the block's MAC, 64 bytes big-endian affine (zeros = infinity)
  *   d_complements  2 * 2^level points of 64 bytes (2^level for the X part, then 2^level for Y), or NULL = none
  *   write_step     the value HAdd sees (after the ++ of Server.hpp:431); write_step % n_total == 0 is CRebuild's step and refused
+ *                  (the client's side of that step: porla_*_client_rebuild_batch_device)
  *   level          the level HAdd lands on (0 = level 0 was empty); pad must be 0
  *   data_x .. align_y  HOST arrays of level + 1 DEVICE pointers: family[i] = level i's 2 * 2^i rows as porla_icc_hrebuild_host lays them
  *                  out (the first 2^i resident, the second 2^i incoming; a data row = n_cols 64-byte little-endian symbols < LCM, a
@@ -687,7 +688,8 @@ int porla_ipa_update_batch_device(porla_fixed_base *generators_fb, const porla_u
  * can be enqueued right behind it on the same stream and buffers with no synchronisation.  The launch sequence depends on the
  * highest level of the call, not on k: two fixed-base passes per call (the k block rows; every PRF scalar of the call).
  * PORLA_ERR_ARG (with a message, before the device is touched): NULL reqs with k > 0; a NULL or misaligned block, prf or output
- * pointer; n_total not a power of two or < 2; level < 0 or 2^level > n_total / 2; write_step % n_total == 0 (CRebuild's step); pad
+ * pointer; n_total not a power of two or < 2; level < 0 or 2^level > n_total / 2; write_step % n_total == 0 (CRebuild's step:
+ * porla_*_client_rebuild_batch_device); pad
  * != 0; two requests naming the same output pointer; IPA: a NULL base, a BN254 base, alpha_generators_fb with fewer than 128 points,
  * h_fb without exactly one point.  k = 0 returns 0; KZG without init_key + init_SRS: PORLA_ERR_STATE; no device: PORLA_ERR_NO_DEVICE.
  * tools/bench_client_update_batch.py times it against the composition of the entry points a caller had before
@@ -704,6 +706,49 @@ typedef struct {
 int porla_kzg_client_update_batch_device(const porla_client_update_req *reqs, size_t k, size_t n_total, void *hip_stream);
 int porla_ipa_client_update_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb,
                                          const porla_client_update_req *reqs, size_t k, size_t n_total, void *hip_stream);
+
+/* ---- the client's rebuild write, Client::CRebuild's step, for K independent writes in ONE asynchronous call (Client.hpp:483-502: all
+ * n_total complements recomputed, the whole MAC-side network over them :1040-1453, X part and Y part, and the 2 * n_total differences
+ * of the wire loop :584-614) ----
+ * The write porla_*_client_update_batch_device refuses (write_step % n_total == 0), behind the same contract.  On the client every
+ * point of this step is a known scalar times the ONE hiding point h, and the network is linear over Z_q (its multipliers are the
+ * integers v^j mod p_icc, which the group reduces mod its order), so the library runs the butterflies on scalars mod q and spends one
+ * fixed-base pass on the results: out = (new - T) * h.  Request a is one write:
+ *   d_block            n_cols x 32 bytes little-endian raw chunks, as porla_client_update_req
+ *   d_prf              3 * n_total + 1 PRF outputs of 16 raw bytes in the order the reference draws them: [0] the block's own complement
+ *                      (:467); [1 .. n_total] complements_U[0 .. n_total-1] (:494-497); then the 2 * n_total new ones of :586-588 in
+ *                      loop order, X then Y.  A value is read as porla_client_update_req.d_prf documents (KZG big-endian, IPA r.d[0],
+ *                      r.d[1] little-endian words)
+ *   d_mac_out          64 bytes big-endian affine (zeros = infinity)
+ *   d_complements_out  2 * n_total points of 64 bytes, X part then Y part
+ *   write_step         the value Client::CRebuild sees.  The protocol passes a multiple of n_total (wt = 1); any value is accepted
+ * All four pointers are device memory, 16-byte aligned.  n_cols = the SRS size (KZG) or 128 (IPA); n_total = num_blocks.
+ * Per request, byte for byte the reference's sequence:
+ *   1. comp0 = prf[0] * h; MAC = Commit_alpha(block) + comp0: step 1 of the client update batch, the same block pass.
+ *   2. X_i = complements_U[i] = prf[1 + i] * h, Y_i = wt * X_i, wt = w^reverse_bits(write_step % n_total, height-1) as the MAC side's
+ *      scalar; then the stages s = 1 .. height-1 of :1083-1450: the result of porla_icc_mac_encode_xy_device on the complements.
+ *   3. out[j] = new_X[j] - X_j, out[n_total + j] = new_Y[j] - Y_j, j < n_total.
+ * Contract: that of porla_*_client_update_batch_device -- asynchronous on hip_stream, no host wait, no internal side stream; the
+ * outputs are complete when the stream is.  The launch sequence depends on n_total, not on k: the block pass over the k rows, the
+ * network (the stages up to T = 1024 symbols in one launch on LDS tiles, one launch per later stage), ONE fixed-base pass over the
+ * k * (2 * n_total + 1) scalars.  The twiddles are the MAC side's table, used under its lock and fence.
+ * PORLA_ERR_ARG (with a message, before the device is touched): NULL reqs with k > 0; a NULL or misaligned block, prf or output
+ * pointer; n_total not a power of two or < 2; two requests naming the same output pointer; IPA: a NULL base, a BN254 base,
+ * alpha_generators_fb with fewer than 128 points, h_fb without exactly one point.  k = 0 returns 0; KZG without init_key + init_SRS:
+ * PORLA_ERR_STATE; no device: PORLA_ERR_NO_DEVICE.
+ * NOT MEASURED on an MI355X yet: tools/bench_client_rebuild.py times it against the composition of the entry points a caller had
+ * before (two complement passes, porla_icc_mac_encode_xy_device, host subtractions; profiles/r14_a_client_rebuild.jsonl, DESIGN s4). */
+#define PORLA_CLIENT_REBUILD_REQ_BYTES 40   /* sizeof(porla_client_rebuild_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    const void *d_block;
+    const void *d_prf;
+    void       *d_mac_out;
+    void       *d_complements_out;
+    unsigned long long write_step;
+} porla_client_rebuild_req;
+int porla_kzg_client_rebuild_batch_device(const porla_client_rebuild_req *reqs, size_t k, size_t n_total, void *hip_stream);
+int porla_ipa_client_rebuild_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb,
+                                          const porla_client_rebuild_req *reqs, size_t k, size_t n_total, void *hip_stream);
 
 /* ---- audit row combine (Server::audit, Server.hpp:790-828) + the scalar part of align_MAC on the result (:531-541) ----
  * B_j = sum_i coeff_i * row_i[j] (exact integer), then aligned_j = B_j mod p_icc, c_j = (aligned_j - B_j) mod q.

@@ -31,8 +31,6 @@
 
 namespace porla {
 
-constexpr size_t CU_IPA_COLS = 128;            // NUM_CHUNKS: the row width of the IPA build
-
 struct ClientUpdateWs {
     std::mutex mu;
     int device = -1;
@@ -169,14 +167,10 @@ static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* 
         PORLA_HIP(hipGetLastError());
     }
     // ---- 2. the block pass and the h pass
+    if ((rc = client_block_pass<C>(fb_alpha, d_rows, k, ncols, d_blk, stream))) return rc;
     if constexpr (CuCurve<C>::id == 0) {
-        if ((rc = porla_kzg_digest_batch_device(d_rows, k, d_blk, stream))) return rc;
         if ((rc = porla_kzg_complement_batch_device(d_scal, n_prf, d_hpts, stream))) return rc;
     } else {
-        {
-            std::lock_guard<std::mutex> lk(fb_alpha->mu);
-            if ((rc = fb_alpha->commit_device(d_rows, k, ncols, 32 * ncols, d_blk, stream))) return rc;
-        }
         std::lock_guard<std::mutex> lk(fb_h->mu);
         if ((rc = fb_h->commit_device(d_scal, n_prf, 1, 32, d_hpts, stream))) return rc;
     }

@@ -7,6 +7,7 @@
 // porla_icc_mac_hrebuild_host are (level i: 2^i resident points, then 2^i incoming ones), level i at byte 128 (2^i - 1).
 #pragma once
 #include "update_batch.hip.h"
+#include "client_block_pass.hip.h"
 
 namespace porla {
 
@@ -43,11 +44,7 @@ k_cu_expand(const CuDesc* __restrict__ desc, uint32_t ncols, uint8_t* __restrict
     const uint32_t nprf = (4u << D.level) - 1u;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t < ncols) {
-        const uint4* s4 = reinterpret_cast<const uint4*>(D.block + 32 * (size_t)t);
-        const uint4 lo = s4[0], hi = s4[1];
-        uint4* d4 = reinterpret_cast<uint4*>(rows + 32 * ((size_t)q * ncols + t));
-        d4[0] = make_uint4(__builtin_bswap32(hi.w), __builtin_bswap32(hi.z), __builtin_bswap32(hi.y), __builtin_bswap32(hi.x));
-        d4[1] = make_uint4(__builtin_bswap32(lo.w), __builtin_bswap32(lo.z), __builtin_bswap32(lo.y), __builtin_bswap32(lo.x));
+        cu_chunk_to_coeff(D.block, t, rows + 32 * ((size_t)q * ncols + t));
     } else if (t - ncols < nprf) {
         const uint32_t p = t - ncols;
         const uint4 v = reinterpret_cast<const uint4*>(D.prf)[p];

@@ -62,6 +62,18 @@ PORLA_CLIENT_UPDATE_REQ_BYTES = 48
 assert ctypes.sizeof(ClientUpdateReq) == PORLA_CLIENT_UPDATE_REQ_BYTES
 
 
+
+class ClientRebuildReq(ctypes.Structure):
+    """porla_client_rebuild_req, include/porla_gpu.h: one write of porla_kzg_client_rebuild_batch_device /
+    porla_ipa_client_rebuild_batch_device (PORLA_CLIENT_REBUILD_REQ_BYTES = 40)."""
+    _fields_ = [("d_block", ctypes.c_void_p), ("d_prf", ctypes.c_void_p), ("d_mac_out", ctypes.c_void_p),
+                ("d_complements_out", ctypes.c_void_p), ("write_step", ctypes.c_ulonglong)]
+
+
+PORLA_CLIENT_REBUILD_REQ_BYTES = 40
+assert ctypes.sizeof(ClientRebuildReq) == PORLA_CLIENT_REBUILD_REQ_BYTES
+
+
 def load():
     """Load the engine.  When torch is importable it is imported FIRST so that the HIP runtime the process
     ends up with is the one torch ships (both have soname libamdhip64.so.7; two runtimes in one process
@@ -174,6 +186,10 @@ def _declare(L):
     L.porla_kzg_client_update_batch_device.restype = ctypes.c_int
     L.porla_ipa_client_update_batch_device.argtypes = [vp, vp, ctypes.POINTER(ClientUpdateReq), sz, sz, vp]
     L.porla_ipa_client_update_batch_device.restype = ctypes.c_int
+    L.porla_kzg_client_rebuild_batch_device.argtypes = [ctypes.POINTER(ClientRebuildReq), sz, sz, vp]
+    L.porla_kzg_client_rebuild_batch_device.restype = ctypes.c_int
+    L.porla_ipa_client_rebuild_batch_device.argtypes = [vp, vp, ctypes.POINTER(ClientRebuildReq), sz, sz, vp]
+    L.porla_ipa_client_rebuild_batch_device.restype = ctypes.c_int
     L.porla_ipa_prove_batch_device.argtypes = [vp, vp, vp, sz, vp, vp]; L.porla_ipa_prove_batch_device.restype = ctypes.c_int
     L.porla_ipa_verify_batch_device.argtypes = [vp, ctypes.POINTER(IpaVerifyReq), sz, vp, vp, vp]
     L.porla_ipa_verify_batch_device.restype = ctypes.c_int

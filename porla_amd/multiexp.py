@@ -325,6 +325,31 @@ def kzg_client_update_batch_device(reqs, n_total, stream=0):
     _check(lib.porla_kzg_client_update_batch_device(arr, len(reqs), n_total, ctypes.c_void_p(stream)))
 
 
+# ---- the client's rebuild write (Client::CRebuild's step) for K writes in one call (include/porla_gpu.h: porla_*_client_rebuild_batch_device) ----
+CLIENT_REBUILD_TILE = 1024      # client_rebuild_batch.hip.h:CR_TILE -- the network's stages up to this many symbols run on one LDS tile
+
+
+def client_rebuild_requests(reqs):
+    """a ctypes array of porla_client_rebuild_req from per-write tuples (d_block, d_prf, d_mac_out, d_complements_out, write_step):
+    device addresses as integers"""
+    from .loader import ClientRebuildReq
+    arr = (ClientRebuildReq * max(len(reqs), 1))()
+    for i, r in enumerate(reqs):
+        if len(r) != 5:
+            raise ValueError("client_rebuild_batch_device: request %d has %d fields, want 5" % (i, len(r)))
+        arr[i] = ClientRebuildReq(r[0] or None, r[1] or None, r[2] or None, r[3] or None, r[4])
+    return arr
+
+
+def kzg_client_rebuild_batch_device(reqs, n_total, stream=0):
+    """The client's side of the write on which the reference calls Client::CRebuild -- the block's MAC, all n_total complements through
+    the whole MAC-side network (X and Y part), the 2 * n_total differences that go on the wire -- of len(reqs) independent writes in
+    ONE asynchronous call on `stream`, KZG build.  d_prf holds 3 * n_total + 1 PRF outputs per request.  `reqs`: tuples as
+    client_rebuild_requests takes them."""
+    arr = client_rebuild_requests(reqs)
+    _check(lib.porla_kzg_client_rebuild_batch_device(arr, len(reqs), n_total, ctypes.c_void_p(stream)))
+
+
 # ---- batched fixed-base commitments (include/porla_gpu.h) ------------------------------------------
 CURVES = {"bn254": 0, "secp256k1": 1}
 
@@ -386,6 +411,14 @@ class FixedBase:
         arr = client_update_requests(reqs)
         _check(lib.porla_ipa_client_update_batch_device(self.h, h_fb.h if h_fb is not None else None, arr, len(reqs), n_total,
                                                         ctypes.c_void_p(stream)))
+
+    def ipa_client_rebuild_batch_device(self, h_fb, reqs, n_total, stream=0):
+        """The client's rebuild write (Client::CRebuild's step) of len(reqs) independent writes in ONE asynchronous call on `stream`, IPA
+        build (porla_ipa_client_rebuild_batch_device); self and h_fb as for ipa_client_update_batch_device.  `reqs`: tuples as
+        client_rebuild_requests takes them."""
+        arr = client_rebuild_requests(reqs)
+        _check(lib.porla_ipa_client_rebuild_batch_device(self.h, h_fb.h if h_fb is not None else None, arr, len(reqs), n_total,
+                                                         ctypes.c_void_p(stream)))
 
     def ipa_prove_batch_device(self, d_a, d_b, k, d_proofs, stream=0):
         """k proofs of Server::inner_product_prove(a, b) in ONE asynchronous call (porla_ipa_prove_batch_device): d_a, d_b = k x 128 x
