@@ -616,7 +616,7 @@ int porla_icc_mac_hrebuild_host(uint8_t *const *levels, int level, size_t n_tota
  *   d_mac          the block's MAC, 64 bytes big-endian affine (zeros = infinity)
  *   d_complements  2 * 2^level points of 64 bytes (2^level for the X part, then 2^level for Y), or NULL = none
  *   write_step     the value HAdd sees (after the ++ of Server.hpp:431); write_step % n_total == 0 is CRebuild's step and refused
- *                  (the client's side of that step: porla_*_client_rebuild_batch_device)
+ *                  (that step: porla_server_rebuild_batch_device; the client's side of it: porla_*_client_rebuild_batch_device)
  *   level          the level HAdd lands on (0 = level 0 was empty); pad must be 0
  *   data_x .. align_y  HOST arrays of level + 1 DEVICE pointers: family[i] = level i's 2 * 2^i rows as porla_icc_hrebuild_host lays them
  *                  out (the first 2^i resident, the second 2^i incoming; a data row = n_cols 64-byte little-endian symbols < LCM, a
@@ -728,6 +728,8 @@ int porla_ipa_client_update_batch_device(porla_fixed_base *alpha_generators_fb, 
  *   2. X_i = complements_U[i] = prf[1 + i] * h, Y_i = wt * X_i, wt = w^reverse_bits(write_step % n_total, height-1) as the MAC side's
  *      scalar; then the stages s = 1 .. height-1 of :1083-1450: the result of porla_icc_mac_encode_xy_device on the complements.
  *   3. out[j] = new_X[j] - X_j, out[n_total + j] = new_Y[j] - Y_j, j < n_total.
+ * The server's side of this write: porla_server_rebuild_batch_device takes d_mac_out and d_complements_out as its d_mac and
+ * d_complements, on the same stream with no synchronisation in between.
  * Contract: that of porla_*_client_update_batch_device -- asynchronous on hip_stream, no host wait, no internal side stream; the
  * outputs are complete when the stream is.  The launch sequence depends on n_total, not on k: the block pass over the k rows, the
  * network (the stages up to T = 1024 symbols in one launch on LDS tiles, one launch per later stage), ONE fixed-base pass over the
@@ -749,6 +751,63 @@ typedef struct {
 int porla_kzg_client_rebuild_batch_device(const porla_client_rebuild_req *reqs, size_t k, size_t n_total, void *hip_stream);
 int porla_ipa_client_rebuild_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb,
                                           const porla_client_rebuild_req *reqs, size_t k, size_t n_total, void *hip_stream);
+
+/* ---- the server's rebuild write, the step of Server::update that calls CRebuild instead of HAdd, for K independent files in ONE
+ * asynchronous call (Server.hpp:413-469 with CRebuild_Cached :1487-1833) ----
+ * The write porla_*_update_batch_device refuses (write_step % n_total == 0) and the other side of
+ * porla_*_client_rebuild_batch_device: d_mac and d_complements are that call's d_mac_out and d_complements_out, d_block the SAME
+ * buffer.  This form of the rebuild commits nothing, so it needs no SRS, key or fixed base: the curve is an argument (0 = BN254 / KZG,
+ * 1 = secp256k1 / IPA) and one symbol serves both builds.  Request a is one write to one file:
+ *   d_block        n_cols x 32 bytes little-endian raw chunks: the incoming block
+ *   d_mac          its MAC, 64 bytes big-endian affine (zeros = infinity)
+ *   d_complements  2 * n_total points of 64 bytes, X part then Y part, or NULL = none
+ *   d_u_blocks     the file's raw store U: n_total x n_cols x 32 bytes;  d_u_macs: MAC_commitments_U, n_total x 64 bytes
+ *   d_data_x .. d_align_y  the TOP level (log2 n_total) of the six families in the layout porla_update_req's families have there:
+ *                  2 * n_total rows, the resident half first, then the incoming half (a data row = n_cols 64-byte little-endian symbols
+ *                  < LCM, a point row = one 64-byte affine point).  A pointer the update batch was given as family[log2 n_total] is
+ *                  passed here unchanged
+ *   write_step     the value CRebuild sees (after the ++ of Server.hpp:431).  The protocol passes a multiple of n_total (wt = 1); any
+ *                  value is accepted;  index: the block id of the message, 1 .. n_total (Server.hpp:407)
+ * Per request, byte for byte the reference's sequence:
+ *   1. U[index-1] = block, MAC_U[index-1] = mac (:413-427); the rebuild reads the stores with this write in them.
+ *   2. the resident half of data X = the X part of the network over the n_total rows of U, of data Y = the Y part,
+ *      wt = w^reverse_bits(write_step % n_total, height-1): the bytes porla_icc_encode_xy_device writes to d_x_out and d_y_x_out.
+ *   3. the resident halves of MAC X / MAC Y = the bytes of porla_icc_mac_encode_xy_device on MAC_U.
+ *   4. the resident halves of align X / align Y = infinity, 64 zero bytes per point (:1527-1535; the stage loops never touch them).
+ *   5. mac_x[j] += comp[j], mac_y[j] += comp[n_total + j], j < n_total (:449-469 with updated_level = height-1): general additions that
+ *      leave affine bytes, infinity on either side and equal or opposite points included.
+ * The incoming halves and every lower level stay untouched; clear_H_data, clear_H_MAC and the `empty` flags are the caller's
+ * bookkeeping, as with the update batch.  The CRebuild_No_Cached form (:1835-2255: rows mod p_icc, an alignment commitment per row)
+ * stays with porla_kzg_crebuild_stage_device.
+ * Contract: that of porla_*_update_batch_device -- asynchronous on hip_stream, no host wait, no internal side stream; the work waits
+ * for whatever was enqueued on hip_stream before the call and the outputs are complete when the stream is, so the call can sit right
+ * behind porla_*_client_rebuild_batch_device on the same stream and buffers and right in front of a batched audit.  The launch sequence
+ * depends on n_total, not on k: the store, ceil(log2 n_total / 9) passes of the data network, the MAC load, log2 n_total MAC stages, the
+ * Y scaling and the close.  The twiddle tables are the single-file encodes', used under their workspace locks and fences;
+ * PORLA_MAC_QUAD_MAX moves the MAC stages between their eight- / four-lane and one-lane forms as it does there (the bytes are the same).
+ * PORLA_ERR_ARG (with a message, before the device is touched): NULL reqs with k > 0; any NULL pointer other than d_complements; any
+ * pointer not 16-byte aligned; n_total not a power of two, < 2 or > 2^16 (larger files: the single-file calls
+ * porla_icc_encode_xy_device and porla_icc_mac_encode_xy_device); n_cols == 0 or > 65535; curve not 0 or 1; index outside 1 .. n_total;
+ * two requests (or two fields of one) sharing a store or top-level pointer; more than 65535 requests; a byte size that overflows.
+ * k = 0 returns 0; valid arguments without a device: PORLA_ERR_NO_DEVICE.
+ * tools/bench_server_rebuild.py times it against the composition of the entry points a caller had before, every output byte compared
+ * (profiles/r15_a_server_rebuild.jsonl, DESIGN s4: 64 files of 2^10 blocks in 11 ms, 19x the single-file encodes in sequence; 8 files of
+ * 2^15 in 43 ms, 1.4x; the host point additions a caller needed for the complements not counted). */
+#define PORLA_SERVER_REBUILD_REQ_BYTES 104   /* sizeof(porla_server_rebuild_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    const void *d_block;
+    const void *d_mac;
+    const void *d_complements;
+    void *d_u_blocks;
+    void *d_u_macs;
+    void *d_data_x, *d_data_y;
+    void *d_mac_x, *d_mac_y;
+    void *d_align_x, *d_align_y;
+    unsigned long long write_step;
+    unsigned long long index;
+} porla_server_rebuild_req;
+int porla_server_rebuild_batch_device(const porla_server_rebuild_req *reqs, size_t k, size_t n_total, size_t n_cols, int curve,
+                                      void *hip_stream);
 
 /* ---- audit row combine (Server::audit, Server.hpp:790-828) + the scalar part of align_MAC on the result (:531-541) ----
  * B_j = sum_i coeff_i * row_i[j] (exact integer), then aligned_j = B_j mod p_icc, c_j = (aligned_j - B_j) mod q.

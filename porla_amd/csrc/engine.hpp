@@ -318,6 +318,8 @@ int icc_wt_scalar_be(size_t n_total, unsigned long long write_step, uint8_t out[
 int icc_wt_residues(int curve, size_t n_total, unsigned long long write_step, uint32_t wt_p[8], uint32_t wt_q[8], uint8_t plain_be[32]);
 int icc_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** tw30);
 int icc_mix_tables_release(hipStream_t stream);
+// ... and with the encode's plane tables beside it (server_rebuild_batch.hip); let go with icc_mix_tables_release
+int icc_encode_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** twp, const uint32_t** twq);
 int mac_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** tws, int* quad_max_log);
 int mac_mix_tables_release(hipStream_t stream);
 // icc.hip: the ICC butterfly network as an n x n matrix of 32-byte big-endian coefficients mod the group order

@@ -50,6 +50,19 @@ static int ensure_twiddles(IccWs* ws, int curve, size_t n, hipStream_t stream) {
     return PORLA_OK;
 }
 
+// the plane tables of icc30_split.hip.h (40-byte slots) for (n, curve), made from the twiddle table, which the caller has ensured
+template <class Q>
+static int ensure_plane_twiddles(IccWs* ws, int curve, size_t n, hipStream_t stream) {
+    if (ws->tw30s_n == n && ws->tw30s_curve == curve) return PORLA_OK;
+    int rc;
+    if ((rc = ws->tw30p.ensure(n * ICC30_PSLOT_WORDS * 4)) || (rc = ws->tw30q.ensure(n * ICC30_PSLOT_WORDS * 4))) return rc;
+    hipLaunchKernelGGL((k_icc_twiddles30_planes<Q>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       (const IccElem<Q>*)ws->tw.p, (uint32_t)n, (uint32_t*)ws->tw30p.p, (uint32_t*)ws->tw30q.p);
+    ws->tw30s_n = (uint32_t)n;
+    ws->tw30s_curve = curve;
+    return PORLA_OK;
+}
+
 // the fence entered on `stream`, the twiddle table and its reduced-radix form (80-byte slots) resident for (n_total, curve)
 template <class Q>
 static int icc_mix_tables(IccWs* ws, int curve, size_t n_total, hipStream_t stream) {
@@ -148,13 +161,7 @@ static int icc_encode_core(IccWs* ws, int curve, const uint8_t* d_rows, size_t n
     // a time, two stages per LDS round trip); the first pass reads the raw chunks, the last one writes the outputs: the two
     // residue planes (9 words per symbol each) only travel between passes.
     if ((rc = ws->work.ensure(total * ICC30_PACK_WORDS * 4))) return rc;
-    if (ws->tw30s_n != n || ws->tw30s_curve != curve) {
-        if ((rc = ws->tw30p.ensure(n * ICC30_PSLOT_WORDS * 4)) || (rc = ws->tw30q.ensure(n * ICC30_PSLOT_WORDS * 4))) return rc;
-        hipLaunchKernelGGL((k_icc_twiddles30_planes<Q>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                           (const IccElem<Q>*)ws->tw.p, (uint32_t)n, (uint32_t*)ws->tw30p.p, (uint32_t*)ws->tw30q.p);
-        ws->tw30s_n = (uint32_t)n;
-        ws->tw30s_curve = curve;
-    }
+    if ((rc = ensure_plane_twiddles<Q>(ws, curve, n, stream))) return rc;
     // at most ICC_TILE_LOG - 1 stages per pass (a tile keeps two columns of a row side by side): 2^9 rows are one pass, 2^10 .. 2^18
     // two, beyond that three
     constexpr int max_ns = ICC_TILE_LOG - 1;
@@ -228,6 +235,20 @@ int icc_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const 
     rc = curve == 0 ? icc_mix_tables<IccBn254Fr>(ws, 0, n_total, stream) : icc_mix_tables<IccSecp256k1Fn>(ws, 1, n_total, stream);
     if (rc) { ws->mu.unlock(); return rc; }
     *tw30 = (const uint32_t*)ws->tw30.p;
+    return PORLA_OK;
+}
+// For server_rebuild_batch.hip: icc_mix_tables_acquire plus the plane tables the encode's kernels read (icc30_split.hip.h), under the
+// same lock and fence; icc_mix_tables_release lets go.
+int icc_encode_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** twp, const uint32_t** twq) {
+    const uint32_t* tw30 = nullptr;
+    int rc = icc_mix_tables_acquire(curve, n_total, stream, &tw30);
+    if (rc) return rc;
+    IccWs* ws = nullptr;
+    rc = g_icc_ws.get(&ws);
+    if (!rc) rc = curve == 0 ? ensure_plane_twiddles<IccBn254Fr>(ws, 0, n_total, stream) : ensure_plane_twiddles<IccSecp256k1Fn>(ws, 1, n_total, stream);
+    if (rc) { (void)icc_mix_tables_release(stream); return rc; }
+    *twp = (const uint32_t*)ws->tw30p.p;
+    *twq = (const uint32_t*)ws->tw30q.p;
     return PORLA_OK;
 }
 int icc_mix_tables_release(hipStream_t stream) {

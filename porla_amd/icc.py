@@ -4,7 +4,7 @@ C ABI (include/porla_gpu.h: porla_icc_encode_*).  Rows are in the reference's ow
 little-endian chunks in (utils.h:353-364), 64-byte little-endian values mod LCM out (utils.h:473-517)."""
 import ctypes
 
-from .loader import UpdateReq, lib
+from .loader import ServerRebuildReq, UpdateReq, lib
 
 CURVE = {"bn254": 0, "secp256k1": 1}
 NUM_CHUNKS = 128  # config.hpp:22
@@ -195,3 +195,27 @@ def kzg_update_batch_device(reqs, n_total, stream=0):
     takes them."""
     arr = update_requests(reqs)
     _check(lib.porla_kzg_update_batch_device(arr, len(reqs), n_total, ctypes.c_void_p(stream)))
+
+
+# ---- the server's rebuild write for K files in one asynchronous call (include/porla_gpu.h: porla_server_rebuild_batch_device) ----
+SERVER_REBUILD_FIELDS = ("d_block", "d_mac", "d_complements", "d_u_blocks", "d_u_macs", "d_data_x", "d_data_y", "d_mac_x", "d_mac_y",
+                         "d_align_x", "d_align_y", "write_step", "index")
+
+
+def server_rebuild_requests(reqs):
+    """a ctypes array of porla_server_rebuild_req from per-write tuples in the order of SERVER_REBUILD_FIELDS: eleven device addresses
+    as integers (0 = NULL; the top-level buffers are what the update batch takes as family[log2 n_total]), write_step and index"""
+    arr = (ServerRebuildReq * max(len(reqs), 1))()
+    for i, r in enumerate(reqs):
+        if len(r) != 13:
+            raise ValueError("server_rebuild_batch_device: request %d has %d fields, want 13" % (i, len(r)))
+        arr[i] = ServerRebuildReq(*[(x or None) for x in r[:11]], r[11], r[12])
+    return arr
+
+
+def server_rebuild_batch_device(reqs, n_total, n_cols, curve, stream=0):
+    """the write on which Server::update calls CRebuild (the store, both networks over U and MAC_U into the resident halves of the top
+    level, the alignments to infinity, the complement adds) for len(reqs) independent files in ONE asynchronous call on `stream`.
+    `reqs`: tuples as server_rebuild_requests takes them; curve: "bn254" or "secp256k1"."""
+    arr = server_rebuild_requests(reqs)
+    _check(lib.porla_server_rebuild_batch_device(arr, len(reqs), n_total, n_cols, CURVE[curve], ctypes.c_void_p(stream)))

@@ -74,6 +74,20 @@ PORLA_CLIENT_REBUILD_REQ_BYTES = 40
 assert ctypes.sizeof(ClientRebuildReq) == PORLA_CLIENT_REBUILD_REQ_BYTES
 
 
+class ServerRebuildReq(ctypes.Structure):
+    """porla_server_rebuild_req, include/porla_gpu.h: one write of porla_server_rebuild_batch_device
+    (PORLA_SERVER_REBUILD_REQ_BYTES = 104)."""
+    _fields_ = [("d_block", ctypes.c_void_p), ("d_mac", ctypes.c_void_p), ("d_complements", ctypes.c_void_p),
+                ("d_u_blocks", ctypes.c_void_p), ("d_u_macs", ctypes.c_void_p),
+                ("d_data_x", ctypes.c_void_p), ("d_data_y", ctypes.c_void_p), ("d_mac_x", ctypes.c_void_p), ("d_mac_y", ctypes.c_void_p),
+                ("d_align_x", ctypes.c_void_p), ("d_align_y", ctypes.c_void_p),
+                ("write_step", ctypes.c_ulonglong), ("index", ctypes.c_ulonglong)]
+
+
+PORLA_SERVER_REBUILD_REQ_BYTES = 104
+assert ctypes.sizeof(ServerRebuildReq) == PORLA_SERVER_REBUILD_REQ_BYTES
+
+
 def load():
     """Load the engine.  When torch is importable it is imported FIRST so that the HIP runtime the process
     ends up with is the one torch ships (both have soname libamdhip64.so.7; two runtimes in one process
@@ -190,6 +204,8 @@ def _declare(L):
     L.porla_kzg_client_rebuild_batch_device.restype = ctypes.c_int
     L.porla_ipa_client_rebuild_batch_device.argtypes = [vp, vp, ctypes.POINTER(ClientRebuildReq), sz, sz, vp]
     L.porla_ipa_client_rebuild_batch_device.restype = ctypes.c_int
+    L.porla_server_rebuild_batch_device.argtypes = [ctypes.POINTER(ServerRebuildReq), sz, sz, sz, ctypes.c_int, vp]
+    L.porla_server_rebuild_batch_device.restype = ctypes.c_int
     L.porla_ipa_prove_batch_device.argtypes = [vp, vp, vp, sz, vp, vp]; L.porla_ipa_prove_batch_device.restype = ctypes.c_int
     L.porla_ipa_verify_batch_device.argtypes = [vp, ctypes.POINTER(IpaVerifyReq), sz, vp, vp, vp]
     L.porla_ipa_verify_batch_device.restype = ctypes.c_int
