@@ -778,7 +778,7 @@ int porla_ipa_client_rebuild_batch_device(porla_fixed_base *alpha_generators_fb,
  *      leave affine bytes, infinity on either side and equal or opposite points included.
  * The incoming halves and every lower level stay untouched; clear_H_data, clear_H_MAC and the `empty` flags are the caller's
  * bookkeeping, as with the update batch.  The CRebuild_No_Cached form (:1835-2255: rows mod p_icc, an alignment commitment per row)
- * stays with porla_kzg_crebuild_stage_device.
+ * is porla_kzg_server_rebuild_aligned_batch_device / porla_ipa_server_rebuild_aligned_batch_device below.
  * Contract: that of porla_*_update_batch_device -- asynchronous on hip_stream, no host wait, no internal side stream; the work waits
  * for whatever was enqueued on hip_stream before the call and the outputs are complete when the stream is, so the call can sit right
  * behind porla_*_client_rebuild_batch_device on the same stream and buffers and right in front of a batched audit.  The launch sequence
@@ -808,6 +808,46 @@ typedef struct {
 } porla_server_rebuild_req;
 int porla_server_rebuild_batch_device(const porla_server_rebuild_req *reqs, size_t k, size_t n_total, size_t n_cols, int curve,
                                       void *hip_stream);
+
+/* ---- the same write in the CRebuild_No_Cached form (Server.hpp:1835-2255), the form the reference runs while height - 1 >
+ * TOP_CACHING_LEVEL, that is for every file above 2^10 blocks (:1479-1485), the protocol's 2^15 among them ----
+ * The last stage of each part ends in align_MAC (:531-541, :1977-1980, :2061-2064 and the Y twins): the top-level row is stored mod
+ * p_icc and its alignment is Commit(c), c = (A mod p_icc - A) mod q.  These calls commit, so the curve comes with the entry point, as
+ * with the update batch: the KZG call commits against the resident SRS (n_cols = porla_kzg_row_coefficients), the IPA call against the
+ * first 128 points of generators_fb (n_cols = 128).  The request is porla_server_rebuild_req and every field means what it means
+ * above, except the layout of d_data_x / d_data_y: the top level in the 256-BIT ROW FORMAT -- 2 * n_total rows of n_cols 32-byte
+ * little-endian symbols below p_icc, the resident half first: the store the audits take as d_rows32, half the bytes per row of the
+ * cached form for the audit's row combine to read.  Whether a file uses this form or the cached one is the caller's decision (the
+ * reference: height - 1 > 10); both accept any power of two from 2 to 2^16.
+ * Per request, byte for byte what Server::update with CRebuild_No_Cached leaves:
+ *   1. U[index-1] = block, MAC_U[index-1] = mac (:413-427).
+ *   2. the resident half of data X = A mod p_icc of the X part's network over U, of data Y = the same of the Y part,
+ *      wt = w^reverse_bits(write_step % n_total, height-1): the bytes porla_icc_encode_xy_device writes to d_aligned_out / d_y_aligned_out.
+ *   3. the resident halves of MAC X / MAC Y = the bytes of porla_icc_mac_encode_xy_device on MAC_U.
+ *   4. the resident halves of align X / align Y, row by row: row j = the commitment of that part's row j of alignment scalars (the
+ *      `scalars` outputs of the same encode), 64 bytes big-endian affine; B starts at infinity (:1882-1890), so the commitment is the
+ *      whole value; a row of zero scalars gives 64 zero bytes.
+ *   5. mac_x[j] += comp[j], mac_y[j] += comp[n_total + j] (:449-469).
+ * The incoming halves and every lower level stay untouched.
+ * Contract: that of porla_server_rebuild_batch_device -- asynchronous on hip_stream, no host wait, no internal side stream (the
+ * single-file porla_kzg_crebuild_stage_device overlaps the MAC network and the commitments on a second stream; here they run one
+ * behind the other), so the client's rebuild call -> this call -> a batched audit -> a batched verify runs in HBM on one stream.  The
+ * rows of alignment scalars (2 * n_total per request) go through a workspace of at most 2^18 rows: the requests are taken in groups that
+ * fit (a group holds at least one request), and per group the last pass of the data network, ONE commitment pass over the group's rows
+ * and the close run one after the other.  So the launch sequence depends on n_total and on the number of groups, not on k within a
+ * group: the store, the passes of the data network but the last, the MAC load, log2 n_total MAC stages and the Y scaling over all k
+ * requests; then per group the last data pass, the commitment pass and the close.  PORLA_REBUILD_ROWS_MAX (rows, read once per process)
+ * lowers the workspace's bound.
+ * PORLA_ERR_ARG (with a message, before the device is touched): every refusal of porla_server_rebuild_batch_device that concerns reqs,
+ * k and n_total; generators_fb NULL, a BN254 base or one with fewer than 128 points.  No SRS loaded (KZG): PORLA_ERR_STATE.  k = 0
+ * returns 0; valid arguments without a device: PORLA_ERR_NO_DEVICE.
+ * tools/bench_server_rebuild_aligned.py times the calls against what a caller had, every output byte compared
+ * (profiles/r16_a_server_rebuild_aligned.jsonl, DESIGN s4: 64 files of 2^10 blocks in 27 ms, 8.0x porla_kzg_crebuild_stage_device run per
+ * file; 8 files of 2^15 in 103 ms, 1.18x; one file 0.91x / 0.96x -- slower: the stage call's side stream hides the MAC network beside
+ * the commitments; the host point additions a caller needed for the complements not counted). */
+int porla_kzg_server_rebuild_aligned_batch_device(const porla_server_rebuild_req *reqs, size_t k, size_t n_total, void *hip_stream);
+int porla_ipa_server_rebuild_aligned_batch_device(porla_fixed_base *generators_fb, const porla_server_rebuild_req *reqs, size_t k,
+                                                  size_t n_total, void *hip_stream);
 
 /* ---- audit row combine (Server::audit, Server.hpp:790-828) + the scalar part of align_MAC on the result (:531-541) ----
  * B_j = sum_i coeff_i * row_i[j] (exact integer), then aligned_j = B_j mod p_icc, c_j = (aligned_j - B_j) mod q.

@@ -14,10 +14,8 @@
 //   stage 1 .. log2 n_total  one launch each over the whole work array, under the MAC side's table lease
 //   k_sr_mac_scale           work_y = wt * work, grid.y = request
 //   k_sr_close               + complements, to affine, into MAC X / MAC Y; align X / align Y = infinity
-#include "batch_host.hpp"
+#include "server_rebuild_host.hpp"
 #include "server_rebuild_batch.hip.h"
-#include "icc_host.hpp"
-#include "../../include/porla_gpu.h"
 
 #include <algorithm>
 #include <cstddef>
@@ -28,15 +26,8 @@
 
 namespace porla {
 
-struct ServerRebuildWs {
-    std::mutex mu;
-    int device = -1;
-    Buf list, planes, work, work_y;
-    PinnedList h_list;
-    UseFence fence;
-    bool lds_set = false;
-};
 static PerDevice<ServerRebuildWs> g_sr_ws;
+int sr_workspace(ServerRebuildWs** out) { return g_sr_ws.get(out); }
 
 // dynamic LDS above 64 KiB: a kernel must be told once per device (as mac_fft.hip does for the kernels these are forms of)
 static void sr_lds_attributes(ServerRebuildWs* ws) {
@@ -55,23 +46,20 @@ template <class C> struct SrCurve;
 template <> struct SrCurve<Bn254G1> { using Q = IccBn254Fr; static constexpr int id = 0; };
 template <> struct SrCurve<Secp256k1G> { using Q = IccSecp256k1Fn; static constexpr int id = 1; };
 
-// the data network of the K stores: icc_encode_core's passes (icc.hip), every pass one launch with grid.y = request
+// the data network of the K stores: icc_encode_core's passes (icc.hip), every pass one launch with grid.y = request; with_last =
+// false leaves the last pass to the caller (the aligned form's own kernel)
 template <class Q>
 static int sr_launch_data(int curve, const SrDesc* d_desc, uint32_t* d_planes, size_t plane_words, size_t k, size_t n, size_t ncols,
-                          hipStream_t stream) {
+                          bool with_last, hipStream_t stream) {
+    SrPass plan[SR_MAX_PASSES];
+    const int passes = sr_pass_plan(ilog2u(n), ncols, ICC_TILE_LOG, plan);
+    if (!with_last && passes == 1) return PORLA_OK;
     const uint32_t *twp = nullptr, *twq = nullptr;
     int rc;
     if ((rc = icc_encode_tables_acquire(curve, n, stream, &twp, &twq))) return rc;
-    const int logn = ilog2u(n);
-    constexpr int max_ns = ICC_TILE_LOG - 1;
-    const int passes = (logn + max_ns - 1) / max_ns;
-    int s = 1;
-    for (int pz = 0; pz < passes; pz++) {
-        const int ns = (logn - (s - 1) + (passes - pz) - 1) / (passes - pz);
-        int cc_log = ICC_TILE_LOG - ns;                                    // 2^ns rows x 2^cc_log columns = ICC_TILE_ELEMS symbols
-        while (cc_log > 0 && ((size_t)1 << (cc_log - 1)) >= ncols) cc_log--;   // no wider than the row
-        const size_t col_tiles = (ncols + ((size_t)1 << cc_log) - 1) >> cc_log;
-        const dim3 grid((unsigned)(col_tiles * (n >> ns)), (unsigned)k);
+    for (int pz = 0; pz < passes - (with_last ? 0 : 1); pz++) {
+        const int s = plan[pz].s, ns = plan[pz].ns, cc_log = plan[pz].cc_log;
+        const dim3 grid((unsigned)(plan[pz].col_tiles * (n >> ns)), (unsigned)k);
         const bool first = pz == 0, last = pz == passes - 1;
         ProfScope ps("server_rebuild_data", stream);
 #define PORLA_SR_LAUNCH(F, L)                                                                                                    \
@@ -82,7 +70,6 @@ static int sr_launch_data(int curve, const SrDesc* d_desc, uint32_t* d_planes, s
         else if (last) PORLA_SR_LAUNCH(false, true);
         else PORLA_SR_LAUNCH(false, false);
 #undef PORLA_SR_LAUNCH
-        s += ns;
     }
     if (hipGetLastError() != hipSuccess) { set_last_error("porla: server rebuild batch: a data launch failed"); rc = PORLA_ERR_HIP; }
     const int r1 = icc_mix_tables_release(stream);
@@ -91,9 +78,10 @@ static int sr_launch_data(int curve, const SrDesc* d_desc, uint32_t* d_planes, s
 
 // the MAC network of the K stores on one work array, the Y part and the close.  The forms: every stage with per-butterfly scalars --
 // eight lanes per butterfly while the whole call has at most MACO_MAX_BUTTERFLIES of them, four above that up to 4 * 2^quad_log points
-// (2^16 by default: where mac_encode_core leaves its four-lane forms), one lane beyond or with PORLA_MAC_QUAD_MAX = 0.
+// (2^16 by default: where mac_encode_core leaves its four-lane forms), one lane beyond or with PORLA_MAC_QUAD_MAX = 0.  close = false
+// leaves the close to the caller (the aligned form's own kernel, behind its commitments).
 template <class C>
-static int sr_launch_mac(ServerRebuildWs* ws, const SrDesc* d_desc, size_t k, size_t n, hipStream_t stream) {
+static int sr_launch_mac(ServerRebuildWs* ws, const SrDesc* d_desc, size_t k, size_t n, bool close, hipStream_t stream) {
     using M = typename C::Fp;
     const uint32_t* tws = nullptr;
     int quad_log = 0, rc;
@@ -130,7 +118,7 @@ static int sr_launch_mac(ServerRebuildWs* ws, const SrDesc* d_desc, size_t k, si
             hipLaunchKernelGGL((k_sr_mac_scale_lane<C>), dim3((unsigned)((n + 63) / 64), (unsigned)k), dim3(64), 0, stream, d_desc, (uint32_t)n,
                                work, work_y);
     }
-    {
+    if (close) {
         ProfScope ps("server_rebuild_close", stream);
         const unsigned gx = (unsigned)std::min<size_t>((2 * n + 255) / 256, 512);
         hipLaunchKernelGGL((k_sr_close<C>), dim3(gx, (unsigned)k), dim3(256), 0, stream, d_desc, (uint32_t)n, work, work_y);
@@ -140,9 +128,11 @@ static int sr_launch_mac(ServerRebuildWs* ws, const SrDesc* d_desc, size_t k, si
     return rc ? rc : r1;
 }
 
-// ws->mu held, ws->fence entered
+// ws->mu held, ws->fence entered.  cached: the whole sequence of this call; otherwise its front for the aligned form
+// (server_rebuild_host.hpp: sr_enqueue_front) -- without the last data pass and the close -- and F says where that form goes on
 template <class C>
-static int sr_enqueue(ServerRebuildWs* ws, const porla_server_rebuild_req* reqs, size_t k, size_t n, size_t ncols, hipStream_t stream) {
+static int sr_enqueue(ServerRebuildWs* ws, const porla_server_rebuild_req* reqs, size_t k, size_t n, size_t ncols, bool cached, hipStream_t stream,
+                      SrFront* F) {
     using Q = typename SrCurve<C>::Q;
     using M = typename C::Fp;
     int rc;
@@ -181,12 +171,18 @@ static int sr_enqueue(ServerRebuildWs* ws, const porla_server_rebuild_req* reqs,
         hipLaunchKernelGGL(k_sr_store, dim3(gx, (unsigned)k), dim3(256), 0, stream, d_desc, (uint32_t)ncols);
         PORLA_HIP(hipGetLastError());
     }
-    if ((rc = sr_launch_data<Q>(SrCurve<C>::id, d_desc, (uint32_t*)ws->planes.p, plane_words, k, n, ncols, stream))) return rc;
-    return sr_launch_mac<C>(ws, d_desc, k, n, stream);
+    if (F) *F = SrFront{d_desc, (uint32_t*)ws->planes.p, plane_words, ws->work.p, ws->work_y.p};
+    if ((rc = sr_launch_data<Q>(SrCurve<C>::id, d_desc, (uint32_t*)ws->planes.p, plane_words, k, n, ncols, cached, stream))) return rc;
+    return sr_launch_mac<C>(ws, d_desc, k, n, cached, stream);
+}
+
+int sr_enqueue_front(ServerRebuildWs* ws, int curve, const porla_server_rebuild_req* reqs, size_t k, size_t n, size_t ncols, hipStream_t stream,
+                     SrFront* F) {
+    return curve == 0 ? sr_enqueue<Bn254G1>(ws, reqs, k, n, ncols, false, stream, F) : sr_enqueue<Secp256k1G>(ws, reqs, k, n, ncols, false, stream, F);
 }
 
 // the checks made before the device is touched
-static int sr_check(const char* who, const porla_server_rebuild_req* reqs, size_t k, size_t n_total, size_t n_cols, int curve) {
+int sr_check(const char* who, const porla_server_rebuild_req* reqs, size_t k, size_t n_total, size_t n_cols, int curve) {
     auto bad = [&](const std::string& what) { return bad_arg(who, what); };
     if (k && !reqs) return bad("reqs is NULL");
     int ln = 0;
@@ -244,6 +240,7 @@ extern "C" int porla_server_rebuild_batch_device(const porla_server_rebuild_req*
     if ((rc = g_sr_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     return FencedCall(ws, stream).run([&] {
-        return curve == 0 ? sr_enqueue<Bn254G1>(ws, reqs, k, n_total, n_cols, stream) : sr_enqueue<Secp256k1G>(ws, reqs, k, n_total, n_cols, stream);
+        return curve == 0 ? sr_enqueue<Bn254G1>(ws, reqs, k, n_total, n_cols, true, stream, nullptr)
+                          : sr_enqueue<Secp256k1G>(ws, reqs, k, n_total, n_cols, true, stream, nullptr);
     });
 }

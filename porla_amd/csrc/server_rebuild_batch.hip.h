@@ -30,7 +30,8 @@ struct SrDesc {
 static_assert(sizeof(SrDesc) == 192, "SrDesc: 88 bytes of pointers, 96 of wt, the row");
 
 // ---- the store: U[index - 1] = block, MAC_U[index - 1] = mac (Server.hpp:413-427), 16 bytes per lane and turn
-__global__ void __launch_bounds__(256)
+// (static: no template, and two translation units include this file)
+static __global__ void __launch_bounds__(256)
 k_sr_store(const SrDesc* __restrict__ desc, uint32_t ncols) {
     const SrDesc& D = desc[blockIdx.y];
     const size_t bu = (size_t)ncols * 2;                                   // 16-byte units of a block; the MAC is four more

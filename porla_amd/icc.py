@@ -219,3 +219,12 @@ def server_rebuild_batch_device(reqs, n_total, n_cols, curve, stream=0):
     `reqs`: tuples as server_rebuild_requests takes them; curve: "bn254" or "secp256k1"."""
     arr = server_rebuild_requests(reqs)
     _check(lib.porla_server_rebuild_batch_device(arr, len(reqs), n_total, n_cols, CURVE[curve], ctypes.c_void_p(stream)))
+
+
+def kzg_server_rebuild_aligned_batch_device(reqs, n_total, stream=0):
+    """the same write in the CRebuild_No_Cached form, KZG build (porla_kzg_server_rebuild_aligned_batch_device): the top-level data rows
+    mod p_icc in the 256-bit row format (2 * n_total rows of porla_kzg_row_coefficients 32-byte symbols, what the audits take as
+    d_rows32) and, per row, the commitment of its alignment scalars against the resident SRS.  `reqs`: tuples as
+    server_rebuild_requests takes them.  The IPA twin is FixedBase.ipa_server_rebuild_aligned_batch_device."""
+    arr = server_rebuild_requests(reqs)
+    _check(lib.porla_kzg_server_rebuild_aligned_batch_device(arr, len(reqs), n_total, ctypes.c_void_p(stream)))

@@ -206,6 +206,10 @@ def _declare(L):
     L.porla_ipa_client_rebuild_batch_device.restype = ctypes.c_int
     L.porla_server_rebuild_batch_device.argtypes = [ctypes.POINTER(ServerRebuildReq), sz, sz, sz, ctypes.c_int, vp]
     L.porla_server_rebuild_batch_device.restype = ctypes.c_int
+    L.porla_kzg_server_rebuild_aligned_batch_device.argtypes = [ctypes.POINTER(ServerRebuildReq), sz, sz, vp]
+    L.porla_kzg_server_rebuild_aligned_batch_device.restype = ctypes.c_int
+    L.porla_ipa_server_rebuild_aligned_batch_device.argtypes = [vp, ctypes.POINTER(ServerRebuildReq), sz, sz, vp]
+    L.porla_ipa_server_rebuild_aligned_batch_device.restype = ctypes.c_int
     L.porla_ipa_prove_batch_device.argtypes = [vp, vp, vp, sz, vp, vp]; L.porla_ipa_prove_batch_device.restype = ctypes.c_int
     L.porla_ipa_verify_batch_device.argtypes = [vp, ctypes.POINTER(IpaVerifyReq), sz, vp, vp, vp]
     L.porla_ipa_verify_batch_device.restype = ctypes.c_int

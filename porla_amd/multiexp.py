@@ -404,6 +404,14 @@ class FixedBase:
         arr = update_requests(reqs)
         _check(lib.porla_ipa_update_batch_device(self.h, arr, len(reqs), n_total, ctypes.c_void_p(stream)))
 
+    def ipa_server_rebuild_aligned_batch_device(self, reqs, n_total, stream=0):
+        """The server's rebuild write in the CRebuild_No_Cached form of len(reqs) independent files in ONE asynchronous call on `stream`,
+        IPA build (porla_ipa_server_rebuild_aligned_batch_device: 128 columns, rows mod p_icc, an alignment commitment per row); self as
+        for ipa_update_batch_device.  `reqs`: tuples as icc.server_rebuild_requests takes them."""
+        from .icc import server_rebuild_requests
+        arr = server_rebuild_requests(reqs)
+        _check(lib.porla_ipa_server_rebuild_aligned_batch_device(self.h, arr, len(reqs), n_total, ctypes.c_void_p(stream)))
+
     def ipa_client_update_batch_device(self, h_fb, reqs, n_total, stream=0):
         """Client::update's preprocessing of len(reqs) independent writes in ONE asynchronous call on `stream`, IPA build
         (porla_ipa_client_update_batch_device); self = a secp256k1 fixed base whose first 128 points are the alpha generators, h_fb = a
