@@ -1,8 +1,10 @@
 // Host pieces every batched entry point is written against (the batched MSM, the KZG / IPA audit, prove and verify batches, the
-// update batch) and the older per-device workspaces share: the workspace registry, the argument refusals, the block -> owner lists
-// of a work list, the fenced call, and a commitment pass with its follow-up kernel under the table's lock.
+// update batch) and the older per-device workspaces share: the workspace registry, the argument refusals, the dynamic-LDS attribute
+// set once per device, the block -> owner lists of a work list, the fenced call, and a commitment pass with its follow-up kernel
+// under the table's lock.
 #pragma once
 #include "engine.hpp"
+#include <initializer_list>
 
 namespace porla {
 
@@ -37,6 +39,30 @@ static inline int bad_arg(const char* who, const std::string& what) {
     set_last_error(std::string(who) + ": " + what);
     return PORLA_ERR_ARG;
 }
+
+// "n_total must be a power of two, 2 .. 2^max_log": the refusal every batched call over levels of n_total rows makes first
+static inline int check_n_total(const char* who, size_t n_total, int max_log) {
+    if (n_total >= 2 && (n_total & (n_total - 1)) == 0 && n_total <= ((size_t)1 << max_log)) return PORLA_OK;
+    return bad_arg(who, "n_total must be a power of two, 2 .. 2^" + std::to_string(max_log));
+}
+
+// Dynamic LDS above 64 KiB: a kernel must be told once per device before its first launch.  One static LdsOnce per group of
+// kernels that are launched together; set() does its work the first time it is called on a device.
+struct LdsKernel { const void* f; size_t bytes; };
+template <class F>
+static inline LdsKernel lds_kernel(F* kernel, size_t bytes) { return LdsKernel{reinterpret_cast<const void*>(kernel), bytes}; }
+struct LdsOnce {
+    std::mutex mu;
+    std::vector<int> done;
+    void set(std::initializer_list<LdsKernel> kernels) {
+        int dev = 0;
+        const bool known = hipGetDevice(&dev) == hipSuccess;               // (unknown: set them anyway, remember nothing)
+        std::lock_guard<std::mutex> lk(mu);
+        for (int d : done) if (known && d == dev) return;
+        for (const LdsKernel& k : kernels) (void)hipFuncSetAttribute(k.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes);
+        if (known) done.push_back(dev);
+    }
+};
 
 // block -> owner list of a work list: blocks_of(a) times a, for a = 0 .. k - 1; returns the list's end
 template <class BlocksOf>

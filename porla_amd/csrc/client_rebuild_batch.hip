@@ -33,10 +33,6 @@ struct ClientRebuildWs {
 };
 static PerDevice<ClientRebuildWs> g_cr_ws;
 
-template <class C> struct CrCurve;
-template <> struct CrCurve<Bn254G1> { using Q = IccBn254Fr; static constexpr int id = 0; };
-template <> struct CrCurve<Secp256k1G> { using Q = IccSecp256k1Fn; static constexpr int id = 1; };
-
 // the network on the K work arrays under the MAC side's table lease
 template <class Q>
 static int cr_launch_network(int curve, uint32_t* d_work, size_t k, size_t n_total, hipStream_t stream) {
@@ -63,8 +59,8 @@ static int cr_launch_network(int curve, uint32_t* d_work, size_t k, size_t n_tot
 template <class C>
 static int cr_enqueue(ClientRebuildWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* fb_h, const porla_client_rebuild_req* reqs, size_t k,
                       size_t ncols, size_t n_total, hipStream_t stream) {
-    using Q = typename CrCurve<C>::Q;
-    constexpr bool LE_PRF = CrCurve<C>::id == 1;
+    using Q = typename IccCurve<C>::Q;
+    constexpr bool LE_PRF = IccCurve<C>::id == 1;
     int rc;
     const uint32_t n = (uint32_t)n_total;
     size_t n_rows, rows_b, work_b, scal_b, hpts_b, blk_b, desc_b;
@@ -90,7 +86,7 @@ static int cr_enqueue(ClientRebuildWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>*
             D.mac_out = (uint8_t*)R.d_mac_out; D.comp_out = (uint8_t*)R.d_complements_out;
             uint32_t wt_p[8], wt_q[8];
             uint8_t be[32];
-            (void)icc_wt_residues(CrCurve<C>::id, n_total, R.write_step, wt_p, wt_q, be);
+            (void)icc_wt_residues(IccCurve<C>::id, n_total, R.write_step, wt_p, wt_q, be);
             h_load_be(D.wt_sc, be);
             fe_reduce_plain<Q>(D.wt_sc, 8);                    // the group sees wt mod its order (convert_ZZ_to_scalar / fr.SetBytes)
         }
@@ -113,7 +109,7 @@ static int cr_enqueue(ClientRebuildWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>*
     // ---- 2. the block pass
     if ((rc = client_block_pass<C>(fb_alpha, d_rows, k, ncols, d_blk, stream))) return rc;
     // ---- 3. the network in Z_q and the rows of the h pass
-    if ((rc = cr_launch_network<Q>(CrCurve<C>::id, d_work, k, n_total, stream))) return rc;
+    if ((rc = cr_launch_network<Q>(IccCurve<C>::id, d_work, k, n_total, stream))) return rc;
     {
         ProfScope ps("client_rebuild_close", stream);
         hipLaunchKernelGGL((k_cr_close<Q, LE_PRF>), dim3((unsigned)((2 * n_total + 255) / 256), (unsigned)k), dim3(256), 0, stream, d_desc, n,
@@ -121,7 +117,7 @@ static int cr_enqueue(ClientRebuildWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>*
         PORLA_HIP(hipGetLastError());
     }
     // ---- 4. the h pass
-    if constexpr (CrCurve<C>::id == 0) {
+    if constexpr (IccCurve<C>::id == 0) {
         if ((rc = porla_kzg_complement_batch_device(d_scal, n_rows, d_hpts, stream))) return rc;
     } else {
         std::lock_guard<std::mutex> lk(fb_h->mu);
@@ -142,9 +138,7 @@ static int cr_enqueue(ClientRebuildWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>*
 static int cr_check(const char* who, const porla_client_rebuild_req* reqs, size_t k, size_t n_total) {
     auto bad = [&](const std::string& what) { return bad_arg(who, what); };
     if (k && !reqs) return bad("reqs is NULL");
-    int ln = 0;
-    while (((size_t)1 << ln) < n_total && ln < 62) ln++;
-    if (n_total < 2 || ((size_t)1 << ln) != n_total || n_total > ((size_t)1 << 30)) return bad("n_total must be a power of two, 2 .. 2^30");
+    if (int rc = check_n_total(who, n_total, 30)) return rc;
     if (k > 0xffffu) return bad("more than 65535 requests in one call");
     std::unordered_set<const void*> seen;
     for (size_t a = 0; a < k; a++) {

@@ -19,6 +19,7 @@
 // Both passes leave affine bytes (k_fb_finish: the table's own conversion), which is what the mix bodies read.
 #include "kzg_state.hpp"
 #include "client_update_batch.hip.h"
+#include "icc_host.hpp"
 #include "../../include/porla_gpu.h"
 
 #include <algorithm>
@@ -37,21 +38,16 @@ struct ClientUpdateWs {
     Buf list, rows, scalars, blk, hpts, pyramid;
     PinnedList h_list;
     UseFence fence;
-    bool lds_set = false;
 };
 static PerDevice<ClientUpdateWs> g_cu_ws;
 
-template <class C> struct CuCurve;
-template <> struct CuCurve<Bn254G1> { using Q = IccBn254Fr; static constexpr int id = 0; };
-template <> struct CuCurve<Secp256k1G> { using Q = IccSecp256k1Fn; static constexpr int id = 1; };
-
+// dynamic LDS above 64 KiB: told once per device (batch_host.hpp:LdsOnce)
 template <class C>
 static void cu_lds_attributes() {
     using M = typename C::Fp;
-    auto set = [](const void* f, size_t bytes) { (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
-    set(reinterpret_cast<const void*>(&k_cu_place<C>), sizeof(MacOctLds<M>));
-    set(reinterpret_cast<const void*>(&k_update_mix_points_oct<C, 1, 0, CU_PARTS>), sizeof(MacOctLds<M>));
-    set(reinterpret_cast<const void*>(&k_update_mix_points_quad<C, 1, 0, CU_PARTS>), sizeof(MacQuadLds<M>));
+    static LdsOnce once;
+    once.set({lds_kernel(&k_cu_place<C>, sizeof(MacOctLds<M>)), lds_kernel(&k_update_mix_points_oct<C, 1, 0, CU_PARTS>, sizeof(MacOctLds<M>)),
+              lds_kernel(&k_update_mix_points_quad<C, 1, 0, CU_PARTS>, sizeof(MacQuadLds<M>))});
 }
 
 struct CuPlan {
@@ -67,7 +63,7 @@ static int cu_launch_steps(const CuPlan& P, const std::vector<uint32_t>& active,
     using M = typename C::Fp;
     const uint32_t* tws = nullptr;
     int quad_log = 0, rc;
-    if ((rc = mac_mix_tables_acquire(CuCurve<C>::id, n_total, P.stream, &tws, &quad_log))) return rc;
+    if ((rc = mac_mix_tables_acquire(IccCurve<C>::id, n_total, P.stream, &tws, &quad_log))) return rc;
     for (uint32_t i = 0; i < lmax && !rc; i++) {
         const uint32_t a = active[i], tw_step = (uint32_t)(n_total >> i);
         ProfScope ps("client_update_mix", P.stream);
@@ -91,7 +87,7 @@ static int cu_launch_steps(const CuPlan& P, const std::vector<uint32_t>& active,
 template <class C>
 static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* fb_h, const porla_client_update_req* reqs, size_t k,
                       size_t ncols, size_t n_total, hipStream_t stream) {
-    using Q = typename CuCurve<C>::Q;
+    using Q = typename IccCurve<C>::Q;
     int rc;
     // ---- the plan: requests by level, highest first (stable), so that the requests step i concerns are the first active[i]
     std::vector<uint32_t> order(k);
@@ -137,7 +133,7 @@ static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* 
             D.mac_out = (uint8_t*)R.d_mac_out; D.comp_out = (uint8_t*)R.d_complements_out;
             uint32_t wt_p[8], wt_q[8];
             uint8_t be[32];
-            (void)icc_wt_residues(CuCurve<C>::id, n_total, R.write_step, wt_p, wt_q, be);
+            (void)icc_wt_residues(IccCurve<C>::id, n_total, R.write_step, wt_p, wt_q, be);
             h_load_be(D.wt_sc, be);
             fe_reduce_plain<Q>(D.wt_sc, 8);                    // the group sees wt mod its order (convert_ZZ_to_scalar / fr.SetBytes)
             D.level = (uint32_t)R.level; D.prf0 = (uint32_t)prf0;
@@ -148,7 +144,7 @@ static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* 
                     hp[(a * CU_PARTS + part) * l1 + l] = l <= (uint32_t)R.level ? pyr + (size_t)128 * (((size_t)1 << l) - 1) : nullptr;
         }
     }
-    if (!ws->lds_set) { cu_lds_attributes<Bn254G1>(); cu_lds_attributes<Secp256k1G>(); ws->lds_set = true; }
+    cu_lds_attributes<C>();
     if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
     CuPlan P;
     P.d_desc = (const CuDesc*)ws->list.p;
@@ -162,13 +158,13 @@ static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* 
     {
         ProfScope ps("client_update_expand", stream);
         const size_t items = ncols + ((size_t)4 << lmax) - 1;
-        hipLaunchKernelGGL((k_cu_expand<CuCurve<C>::id == 1>), dim3((unsigned)((items + 255) / 256), (unsigned)k), dim3(256), 0, stream, P.d_desc,
+        hipLaunchKernelGGL((k_cu_expand<IccCurve<C>::id == 1>), dim3((unsigned)((items + 255) / 256), (unsigned)k), dim3(256), 0, stream, P.d_desc,
                            (uint32_t)ncols, d_rows, d_scal);
         PORLA_HIP(hipGetLastError());
     }
     // ---- 2. the block pass and the h pass
     if ((rc = client_block_pass<C>(fb_alpha, d_rows, k, ncols, d_blk, stream))) return rc;
-    if constexpr (CuCurve<C>::id == 0) {
+    if constexpr (IccCurve<C>::id == 0) {
         if ((rc = porla_kzg_complement_batch_device(d_scal, n_prf, d_hpts, stream))) return rc;
     } else {
         std::lock_guard<std::mutex> lk(fb_h->mu);
@@ -204,9 +200,7 @@ static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* 
 static int cu_check(const char* who, const porla_client_update_req* reqs, size_t k, size_t n_total) {
     auto bad = [&](const std::string& what) { return bad_arg(who, what); };
     if (k && !reqs) return bad("reqs is NULL");
-    int ln = 0;
-    while (((size_t)1 << ln) < n_total && ln < 62) ln++;
-    if (n_total < 2 || ((size_t)1 << ln) != n_total || n_total > ((size_t)1 << 30)) return bad("n_total must be a power of two, 2 .. 2^30");
+    if (int rc = check_n_total(who, n_total, 30)) return rc;
     if (k > 0xffffu) return bad("more than 65535 requests in one call");
     std::unordered_set<const void*> seen;
     for (size_t a = 0; a < k; a++) {

@@ -322,6 +322,12 @@ int icc_mix_tables_release(hipStream_t stream);
 int icc_encode_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** twp, const uint32_t** twq);
 int mac_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** tws, int* quad_max_log);
 int mac_mix_tables_release(hipStream_t stream);
+// ... and, under that lease, the stages 1 .. log2 n_total of the MAC network over a work array of `points` projective points
+// (points / n_total tables end to end; quad: the four- and eight-lane forms; tws: as acquire returned it), each stage one launch
+// inside a ProfScope `scope`.  work: XYZZ<Fp> of the curve `curve` names (0: Bn254Fp, 1: Secp256k1Fp) -- the caller's to get right,
+// a mismatch is not detected
+void mac_stages_leased(int curve, void* work, size_t points, size_t n_total, bool quad, const uint32_t* tws, const char* scope,
+                       hipStream_t stream);
 // icc.hip: the ICC butterfly network as an n x n matrix of 32-byte big-endian coefficients mod the group order
 int icc_network_matrix_device(int curve, size_t n, unsigned long long write_step, int part, uint8_t* d_rows_out,
                               hipStream_t stream);

@@ -157,22 +157,16 @@ static int icc_encode_core(IccWs* ws, int curve, const uint8_t* d_rows, size_t n
         if (!out_y->al && (out_y->x || out_y->sc) && (rc = ws->park_y.ensure(total * 32))) return rc;
     }
     const IccOut oy = out_y ? *out_y : IccOut{nullptr, nullptr, nullptr, nullptr, 0};
-    // ceil(logn / 8) passes of (almost) equal stage counts, each through LDS tiles of ICC_TILE_ELEMS = 1 024 symbols (icc30_split.hip.h: one plane at
+    // the passes (icc_host.hpp:icc_pass_plan), each through LDS tiles of ICC_TILE_ELEMS = 1 024 symbols (icc30_split.hip.h: one plane at
     // a time, two stages per LDS round trip); the first pass reads the raw chunks, the last one writes the outputs: the two
     // residue planes (9 words per symbol each) only travel between passes.
     if ((rc = ws->work.ensure(total * ICC30_PACK_WORDS * 4))) return rc;
     if ((rc = ensure_plane_twiddles<Q>(ws, curve, n, stream))) return rc;
-    // at most ICC_TILE_LOG - 1 stages per pass (a tile keeps two columns of a row side by side): 2^9 rows are one pass, 2^10 .. 2^18
-    // two, beyond that three
-    constexpr int max_ns = ICC_TILE_LOG - 1;
-    const int passes = (logn + max_ns - 1) / max_ns;
-    int s = 1;
+    IccPass plan[ICC_MAX_PASSES];
+    const int passes = icc_pass_plan(logn, ncols, plan);
     for (int pz = 0; pz < passes; pz++) {
-        const int ns = (logn - (s - 1) + (passes - pz) - 1) / (passes - pz);
-        int cc_log = ICC_TILE_LOG - ns;                                    // 2^ns rows x 2^cc_log columns = ICC_TILE_ELEMS symbols
-        while (cc_log > 0 && ((size_t)1 << (cc_log - 1)) >= ncols) cc_log--;   // no wider than the row
-        const size_t col_tiles = (ncols + ((size_t)1 << cc_log) - 1) >> cc_log;
-        const dim3 grid((unsigned)(col_tiles * (n >> ns)));
+        const int s = plan[pz].s, ns = plan[pz].ns, cc_log = plan[pz].cc_log;
+        const dim3 grid((unsigned)(plan[pz].col_tiles * (n >> ns)));
         const bool first = pz == 0, last = pz == passes - 1;
         ProfScope ps("icc_fused", stream, true);
 #define PORLA_ICC_LAUNCH(F, L)                                                                                              \
@@ -193,7 +187,6 @@ static int icc_encode_core(IccWs* ws, int curve, const uint8_t* d_rows, size_t n
         else if (last) PORLA_ICC_LAUNCH(false, true);
         else PORLA_ICC_LAUNCH(false, false);
 #undef PORLA_ICC_LAUNCH
-        s += ns;
     }
     PORLA_HIP(hipGetLastError());
     return PORLA_OK;

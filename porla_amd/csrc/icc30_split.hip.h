@@ -103,6 +103,31 @@ struct IccTile {           // what a block knows about its tile (the same for bo
     int s0, ns;
     int raw;               // first pass without an init scaling: the chunks enter the network as they are (see icc30_fetch)
 };
+// the tile of the calling block in a pass that runs stages s0 .. s0 + ns - 1 on tiles of 2^ns rows x 2^cc_log columns (grid.x =
+// column tiles x row tiles).  blocks b, b + 8, ... share an XCD (observed round-robin dispatch; speed only): XCD x takes tiles
+// [x G / 8, (x + 1) G / 8)
+__device__ __forceinline__ IccTile icc30_block_tile(uint32_t n, uint32_t ncols, int s0, int ns, int cc_log, bool raw) {
+    IccTile T;
+    T.n = n; T.ncols = ncols; T.s0 = s0; T.ns = ns; T.cc_log = (uint32_t)cc_log;
+    T.elems = (1u << ns) << cc_log;
+    T.raw = raw;
+    T.lo_bits = (uint32_t)(s0 - 1);
+    const uint32_t col_tiles = (ncols + (1u << cc_log) - 1) >> cc_log;
+    uint32_t tile = blockIdx.x;
+    if ((gridDim.x & 7u) == 0) tile = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const uint32_t ct = tile % col_tiles;
+    tile /= col_tiles;
+    T.lo = tile & ((1u << T.lo_bits) - 1u);
+    const uint32_t hi = tile >> T.lo_bits;
+    T.row_base = (hi << (T.lo_bits + ns)) + T.lo;
+    T.c0 = ct << cc_log;
+    return T;
+}
+// tile slot e = (row of the tile, column of the tile) -> the symbol's index in the n x ncols array
+__device__ __forceinline__ size_t icc30_symbol_index(const IccTile& T, uint32_t e) {
+    const uint32_t mid = e >> T.cc_log, col = e & ((1u << T.cc_log) - 1u);
+    return (size_t)(T.row_base + (mid << T.lo_bits)) * T.ncols + T.c0 + col;
+}
 
 // a tile symbol from where the pass finds it.  FIRST: the raw 32-byte chunk x.  The stream is made of PLAIN residues and nothing
 // in the network needs them reduced -- a product with a twiddle brings any operand below 2^263 under p + 2^250, sums and
@@ -116,8 +141,7 @@ struct IccTile {           // what a block knows about its tile (the same for bo
 template <class M, bool FIRST>
 __device__ __forceinline__ F30<M> icc30_fetch(const IccTile& T, uint32_t e, const uint8_t* __restrict__ raw, const F30<M>& K,
                                               const uint32_t* __restrict__ work) {
-    const uint32_t mid = e >> T.cc_log, col = e & ((1u << T.cc_log) - 1u);
-    const size_t gi = (size_t)(T.row_base + (mid << T.lo_bits)) * T.ncols + T.c0 + col;
+    const size_t gi = icc30_symbol_index(T, e);
     if (FIRST) {
         const Fe<IccFp> x = ld_fe<IccFp>(reinterpret_cast<const uint32_t*>(raw + 32 * gi));
         const F30<M> u = f30_unpack<M>(x.v);
@@ -255,22 +279,7 @@ k_icc_split30(uint32_t* __restrict__ work_p, uint32_t* __restrict__ work_q, cons
     static_assert(LAST || !XY, "the second part's outputs are derived in the last pass");
     __shared__ uint2 lds2[ICC_TILE_ELEMS * ICC30_PSLOT_WORDS / 2];
     uint32_t* lds = reinterpret_cast<uint32_t*>(lds2);
-    IccTile T;
-    T.n = n; T.ncols = ncols; T.s0 = s0; T.ns = ns; T.cc_log = (uint32_t)cc_log;
-    T.elems = (1u << ns) << cc_log;
-    T.raw = FIRST && !use_wt;
-    T.lo_bits = (uint32_t)(s0 - 1);
-    const uint32_t Cc = 1u << cc_log;
-    const uint32_t col_tiles = (ncols + Cc - 1) >> cc_log;
-    // blocks b, b + 8, ... share an XCD (observed round-robin dispatch; speed only): XCD x takes tiles [x G / 8, (x + 1) G / 8)
-    uint32_t tile = blockIdx.x;
-    if ((gridDim.x & 7u) == 0) tile = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const uint32_t ct = tile % col_tiles;
-    tile /= col_tiles;
-    T.lo = tile & ((1u << T.lo_bits) - 1u);
-    const uint32_t hi = tile >> T.lo_bits;
-    T.row_base = (hi << (T.lo_bits + ns)) + T.lo;
-    T.c0 = ct << cc_log;
+    const IccTile T = icc30_block_tile(n, ncols, s0, ns, cc_log, FIRST && !use_wt);
 
     // planes the requested outputs need: the values mod p_icc (al) only the p_icc plane, the values mod q (qres: the MAC side's
     // network matrix) only the q plane; the alignment scalars and the values mod LCM both
@@ -290,8 +299,7 @@ k_icc_split30(uint32_t* __restrict__ work_p, uint32_t* __restrict__ work_q, cons
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             if (slot[i] != 0xffffffffu) {
-                const uint32_t mid = slot[i] >> cc_log, col = slot[i] & (Cc - 1);
-                const size_t gi = (size_t)(T.row_base + (mid << T.lo_bits)) * ncols + T.c0 + col;
+                const size_t gi = icc30_symbol_index(T, slot[i]);
                 if (LAST) {
                     // A mod p_icc leaves the registers here: to `aligned` when the caller wants it, and -- for the q plane's finish
                     // step, by the same lane -- to the symbol's own place in the p_icc work plane, which this block has finished reading
@@ -327,8 +335,7 @@ k_icc_split30(uint32_t* __restrict__ work_p, uint32_t* __restrict__ work_q, cons
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             if (slot[i] != 0xffffffffu) {
-                const uint32_t mid = slot[i] >> cc_log, col = slot[i] & (Cc - 1);
-                const size_t gi = (size_t)(T.row_base + (mid << T.lo_bits)) * ncols + T.c0 + col;
+                const size_t gi = icc30_symbol_index(T, slot[i]);
                 if (LAST) {
                     if (x_q) {
                         Fe<IccFp> P = fe_zero<IccFp>();

@@ -1,4 +1,4 @@
-// Host helpers shared by the ICC data encode (icc.hip) and the MAC-side encode (mac_fft.hip).
+// Host helpers shared by the ICC data encode (icc.hip), the MAC-side encode (mac_fft.hip) and the batched calls built on them.
 #pragma once
 #include "host_curve.hpp"
 #include "icc.hip.h"
@@ -32,6 +32,31 @@ inline Fe<IccFp> icc_wt(size_t n, unsigned long long write_step) {
     uint64_t ex = rev_bits(write_step % n, height - 1);
     uint32_t e[8] = {(uint32_t)ex, (uint32_t)(ex >> 32), 0, 0, 0, 0, 0, 0};
     return h_fe_pow<IccFp>(icc_root(n), e);
+}
+
+// a group as the ICC code sees it: Q = the CRT partner of p_icc (the group's order), id = the `curve` argument of the C ABI
+template <class C> struct IccCurve;
+template <> struct IccCurve<Bn254G1> { using Q = IccBn254Fr; static constexpr int id = 0; };
+template <> struct IccCurve<Secp256k1G> { using Q = IccSecp256k1Fn; static constexpr int id = 1; };
+
+// The passes of the data network over n = 2^logn rows of ncols symbols: ceil(logn / (ICC_TILE_LOG - 1)) passes of (almost) equal
+// stage counts -- a tile keeps two columns of a row side by side, so 2^9 rows are one pass, 2^10 .. 2^18 two, beyond that three.
+// Pass z runs stages s .. s + ns - 1 on tiles of 2^ns rows x 2^cc_log columns = ICC_TILE_ELEMS symbols, no wider than the row; its
+// grid is col_tiles * (n >> ns) blocks.
+struct IccPass { int s, ns, cc_log; size_t col_tiles; };
+constexpr int ICC_MAX_PASSES = 8;
+inline int icc_pass_plan(int logn, size_t ncols, IccPass out[ICC_MAX_PASSES]) {
+    constexpr int max_ns = ICC_TILE_LOG - 1;
+    const int passes = (logn + max_ns - 1) / max_ns;
+    int s = 1;
+    for (int pz = 0; pz < passes; pz++) {
+        const int ns = (logn - (s - 1) + (passes - pz) - 1) / (passes - pz);
+        int cc_log = ICC_TILE_LOG - ns;
+        while (cc_log > 0 && ((size_t)1 << (cc_log - 1)) >= ncols) cc_log--;
+        out[pz] = IccPass{s, ns, cc_log, (ncols + ((size_t)1 << cc_log) - 1) >> cc_log};
+        s += ns;
+    }
+    return passes;
 }
 
 }  // namespace porla

@@ -89,47 +89,17 @@ static int ensure_mac_codes(MacWs* ws, int curve, size_t n, hipStream_t stream) 
     return PORLA_OK;
 }
 
-// dynamic LDS of the quad-lane stage / load kernels (mac_fft.hip.h:MACQ_LDS); above 64 KiB a kernel must be told once per device
+// dynamic LDS of the four- and eight-lane kernels (mac_fft.hip.h:MACQ_LDS / MACO_LDS) is above 64 KiB: told once per device
+// (batch_host.hpp:LdsOnce), before the first launch of any of them from this file
+template <class C> constexpr size_t macq_lds_bytes() { return sizeof(MacQuadLds<typename C::Fp>); }
+template <class C> constexpr size_t maco_lds_bytes() { return sizeof(MacOctLds<typename C::Fp>); }
 template <class C>
-static size_t macq_lds_bytes() {
-    using M = typename C::Fp;
-    static std::mutex mu;
-    static std::vector<int> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return sizeof(MacQuadLds<M>);
-    std::lock_guard<std::mutex> lk(mu);
-    bool seen = false;
-    for (int d : done) seen = seen || d == dev;
-    if (!seen) {
-        const int bytes = (int)sizeof(MacQuadLds<M>);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mac_stage30_quad<C, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mac_stage30_quad<C, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mac_load30_quad<C, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mac_load30_quad<C, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mac_mix_quad<C>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        done.push_back(dev);
-    }
-    return sizeof(MacQuadLds<M>);
-}
-
-template <class C>
-static size_t maco_lds_bytes() {
-    using M = typename C::Fp;
-    static std::mutex mu;
-    static std::vector<int> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return sizeof(MacOctLds<M>);
-    std::lock_guard<std::mutex> lk(mu);
-    bool seen = false;
-    for (int d : done) seen = seen || d == dev;
-    if (!seen) {
-        const int bytes = (int)sizeof(MacOctLds<M>);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mac_stage30_oct<C>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mac_mix_oct<C>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mac_stage30_oct_uniform<C>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        done.push_back(dev);
-    }
-    return sizeof(MacOctLds<M>);
+static void mac_lds_attributes() {
+    static LdsOnce once;
+    constexpr size_t quad = macq_lds_bytes<C>(), oct = maco_lds_bytes<C>();
+    once.set({lds_kernel(&k_mac_stage30_quad<C, false, uint32_t>, quad), lds_kernel(&k_mac_stage30_quad<C, true>, quad),
+              lds_kernel(&k_mac_load30_quad<C, false>, quad), lds_kernel(&k_mac_load30_quad<C, true>, quad), lds_kernel(&k_mac_mix_quad<C>, quad),
+              lds_kernel(&k_mac_stage30_oct<C>, oct), lds_kernel(&k_mac_stage30_oct_uniform<C>, oct), lds_kernel(&k_mac_mix_oct<C>, oct)});
 }
 
 template <class C, class Q>
@@ -137,6 +107,7 @@ static int mac_mix_core(MacWs* ws, int curve, const uint8_t* d_a0, const uint8_t
                         hipStream_t stream, const uint8_t* d_b0 = nullptr, const uint8_t* d_b1 = nullptr, uint8_t* d_out_b = nullptr) {
     int rc;
     if ((rc = ensure_mac_twiddles<Q>(ws, curve, n_total, stream))) return rc;
+    mac_lds_attributes<C>();
     ProfScope ps("mac_mix", stream);
     const unsigned sets = d_b0 ? 2u : 1u;               // the second array pair (MAC alignments beside the MAC commitments)
     const size_t quad_max = (size_t)1 << macq_max_log(14);
@@ -166,6 +137,49 @@ static int mac_mix_core(MacWs* ws, int curve, const uint8_t* d_a0, const uint8_t
                        (const uint32_t*)ws->tws.p, (uint32_t)(n_total / len), d_out, d_b0, d_b1, d_out_b);
     PORLA_HIP(hipGetLastError());
     return PORLA_OK;
+}
+
+// The stages s = 1 .. log2 n of the network on a work array of `points` points: points / n tables of n rows end to end (one for the
+// single-file encode; the rebuild batch's K requests), stage s one launch over all points / 2 butterflies (mac_fft.hip.h:
+// mac_stage_index).  quad: the four- and eight-lane forms (the caller's size rule) -- stage 1 as its two additions, then eight
+// lanes per butterfly while the launch has at most MACO_MAX_BUTTERFLIES of them, four above; otherwise one lane.  codes: the
+// twiddles' digit codes for the wave-uniform forms (points == n only), or nullptr: per-butterfly scalars at every stage.  A caller
+// that passes codes passes the table ensure_mac_codes made for THIS n: the uniform forms start at n = 128 and read entries up to
+// n / 32 (below n = 32 that function makes nothing, and the workspace may still hold a larger call's table: never read here).
+template <class C>
+static void mac_stages(XYZZ<typename C::Fp>* work, size_t points, size_t n, bool quad, const uint32_t* tws, const uint16_t* codes,
+                       const char* scope, hipStream_t stream) {
+    const int logn = ilog2u(n);
+    const size_t total = points / 2;
+    const uint32_t n32 = (uint32_t)n, total32 = (uint32_t)total;
+    mac_lds_attributes<C>();
+    for (int s = 1; s <= logn; s++) {
+        ProfScope ps(scope, stream);
+        const bool shared16 = codes && (n >> s) >= 16 && n >= 128;        // >= 16 butterflies per twiddle (and whole blocks of 64)
+        if (quad && s == 1)      // every twiddle of stage 1 is w^0 = 1: two additions per butterfly, no ladder
+            hipLaunchKernelGGL((k_mac_stage1_quad<C>), dim3((unsigned)((total + 63) / 64)), dim3(256), 0, stream, work, (uint32_t)points);
+        else if (quad && shared16 && total <= MACO_MAX_BUTTERFLIES)
+            // ... and at most 2^13 butterflies: eight lanes each, the two half-scalar ladders in different waves
+            hipLaunchKernelGGL((k_mac_stage30_oct_uniform<C>), dim3((unsigned)(total / MACO_BF)), dim3(8 * MACO_BF), maco_lds_bytes<C>(), stream,
+                               work, tws, n32, s, codes);
+        else if (quad && shared16)
+            // a wave's 16 quads share their scalar -- the sparse ladder
+            hipLaunchKernelGGL((k_mac_stage30_quad<C, true>), dim3((unsigned)((total + MACQ_BF - 1) / MACQ_BF)), dim3(4 * MACQ_BF),
+                               macq_lds_bytes<C>(), stream, work, tws, n32, s, codes);
+        else if (quad && total <= MACO_MAX_BUTTERFLIES)
+            // per-butterfly scalars and at most 2^13 butterflies: eight lanes each (the two half-scalar ladders side by side)
+            hipLaunchKernelGGL((k_mac_stage30_oct<C>), dim3((unsigned)((total + MACO_BF - 1) / MACO_BF)), dim3(8 * MACO_BF), maco_lds_bytes<C>(),
+                               stream, work, tws, n32, total32, s);
+        else if (quad)
+            hipLaunchKernelGGL((k_mac_stage30_quad<C, false, uint32_t>), dim3((unsigned)((total + MACQ_BF - 1) / MACQ_BF)), dim3(4 * MACQ_BF),
+                               macq_lds_bytes<C>(), stream, work, tws, n32, s, codes, total32);
+        else if (codes && s > 1 && (n >> s) >= 64 && (total & 255) == 0)
+            // one lane per butterfly, >= 64 butterflies per twiddle: a wave shares its scalar -- the sparse ladder
+            hipLaunchKernelGGL((k_mac_stage30<C, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, work, tws, n32, s, codes);
+        else
+            hipLaunchKernelGGL((k_mac_stage30<C, false, uint32_t>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, work, tws, n32, s, codes,
+                               total32);
+    }
 }
 
 // d_out_y != nullptr (with part == 0): BOTH parts from one butterfly network.  The network is linear over Z_q and the Y part is
@@ -219,6 +233,7 @@ static int mac_encode_core(MacWs* ws, int curve, const uint8_t* d_in, size_t n, 
         use_wt = part == 1;
     }
     const bool quad_path = macq_max_log(16) > 0 && n <= ((size_t)1 << macq_max_log(16));
+    mac_lds_attributes<C>();
     {
         ProfScope ps("mac_load", stream);
         if (use_wt && macq_max_log(14) > 0 && n <= ((size_t)1 << macq_max_log(14)))
@@ -231,34 +246,7 @@ static int mac_encode_core(MacWs* ws, int curve, const uint8_t* d_in, size_t n, 
             hipLaunchKernelGGL((k_mac_load30<C, false>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, d_in, (uint32_t)n,
                                (XYZZ<M>*)ws->work.p, wt);
     }
-    for (int s = 1; s <= logn; s++) {
-        ProfScope ps("mac_stage", stream);
-        if (quad_path && s == 1)      // every twiddle of stage 1 is w^0 = 1: two additions per butterfly, no ladder
-            hipLaunchKernelGGL((k_mac_stage1_quad<C>), dim3((unsigned)((n / 2 + 63) / 64)), dim3(256), 0, stream, (XYZZ<M>*)ws->work.p,
-                               (uint32_t)n);
-        else if (quad_path && (n >> s) >= 16 && n >= 128 && n / 2 <= MACO_MAX_BUTTERFLIES)
-            // ... and at most 2^13 butterflies: eight lanes each, the two half-scalar ladders in different waves
-            hipLaunchKernelGGL((k_mac_stage30_oct_uniform<C>), dim3((unsigned)(n / 2 / MACO_BF)), dim3(8 * MACO_BF), maco_lds_bytes<C>(), stream,
-                               (XYZZ<M>*)ws->work.p, (const uint32_t*)ws->tws.p, (uint32_t)n, s, codes);
-        else if (quad_path && (n >> s) >= 16 && n >= 128)
-            // >= 16 butterflies per twiddle (and whole blocks of 64): a wave's 16 quads share their scalar -- the sparse ladder
-            hipLaunchKernelGGL((k_mac_stage30_quad<C, true>), dim3((unsigned)((n / 2 + MACQ_BF - 1) / MACQ_BF)), dim3(4 * MACQ_BF), macq_lds_bytes<C>(), stream,
-                               (XYZZ<M>*)ws->work.p, (const uint32_t*)ws->tws.p, (uint32_t)n, s, codes);
-        else if (quad_path && n / 2 <= MACO_MAX_BUTTERFLIES)
-            // per-butterfly scalars and at most 2^13 butterflies: eight lanes each (the two half-scalar ladders side by side)
-            hipLaunchKernelGGL((k_mac_stage30_oct<C>), dim3((unsigned)((n / 2 + MACO_BF - 1) / MACO_BF)), dim3(8 * MACO_BF), maco_lds_bytes<C>(), stream,
-                               (XYZZ<M>*)ws->work.p, (const uint32_t*)ws->tws.p, (uint32_t)n, s);
-        else if (quad_path)
-            hipLaunchKernelGGL((k_mac_stage30_quad<C, false>), dim3((unsigned)((n / 2 + MACQ_BF - 1) / MACQ_BF)), dim3(4 * MACQ_BF), macq_lds_bytes<C>(), stream,
-                               (XYZZ<M>*)ws->work.p, (const uint32_t*)ws->tws.p, (uint32_t)n, s, codes);
-        else if (s > 1 && (n >> s) >= 64 && ((n / 2) & 255) == 0)
-            // one lane per butterfly, >= 64 butterflies per twiddle: a wave shares its scalar -- the sparse ladder
-            hipLaunchKernelGGL((k_mac_stage30<C, true>), dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, stream, (XYZZ<M>*)ws->work.p,
-                               (const uint32_t*)ws->tws.p, (uint32_t)n, s, codes);
-        else
-            hipLaunchKernelGGL((k_mac_stage30<C, false>), dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, stream, (XYZZ<M>*)ws->work.p,
-                               (const uint32_t*)ws->tws.p, (uint32_t)n, s, codes);
-    }
+    mac_stages<C>((XYZZ<M>*)ws->work.p, n, n, quad_path, (const uint32_t*)ws->tws.p, codes, "mac_stage", stream);
     {
         ProfScope ps("mac_finish", stream);
         hipLaunchKernelGGL((k_mac_finish<C>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, (const XYZZ<M>*)ws->work.p,
@@ -296,6 +284,14 @@ int mac_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const 
     *tws = (const uint32_t*)ws->tws.p;
     *quad_max_log = macq_max_log(14);
     return PORLA_OK;
+}
+// For server_rebuild_batch.hip, between acquire and release: mac_stages on the caller's work array of points / n_total tables, with
+// per-butterfly scalars from the table `tws` that acquire returned.  work: XYZZ<Fp> points of THAT curve (the type does not cross
+// the translation units; a mismatch is not detected)
+void mac_stages_leased(int curve, void* work, size_t points, size_t n_total, bool quad, const uint32_t* tws, const char* scope,
+                       hipStream_t stream) {
+    if (curve == 0) mac_stages<Bn254G1>((XYZZ<Bn254Fp>*)work, points, n_total, quad, tws, nullptr, scope, stream);
+    else mac_stages<Secp256k1G>((XYZZ<Secp256k1Fp>*)work, points, n_total, quad, tws, nullptr, scope, stream);
 }
 int mac_mix_tables_release(hipStream_t stream) {
     MacWs* ws = nullptr;

@@ -48,6 +48,40 @@ __device__ __forceinline__ uint32_t mac_wnaf5_step(uint32_t (&k)[5], bool flip) 
 }
 
 
+// entry e of the twiddle table as the ladders take a scalar: eight little-endian words, two 16-byte loads
+__device__ __forceinline__ void mac_load_twiddle(uint32_t (&sc)[8], const uint32_t* __restrict__ tws, size_t e) {
+    const uint4* w4 = reinterpret_cast<const uint4*>(tws + e * 8);
+    const uint4 a = w4[0], b = w4[1];
+    sc[0] = a.x; sc[1] = a.y; sc[2] = a.z; sc[3] = a.w; sc[4] = b.x; sc[5] = b.y; sc[6] = b.z; sc[7] = b.w;
+}
+// The butterfly count of a stage launch.  The per-butterfly forms take it as their LAST kernel argument: n / 2 for one table, K n / 2
+// for the rebuild batch's K tables end to end.  The wave-uniform forms run on one table only (their twiddle sharing needs it): their
+// count is n / 2 and they take NO such argument (an empty pack), which leaves them the argument block and the prologue they were
+// tuned and measured with -- with a fourth scalar in the block the four-lane uniform stage of secp256k1 ran 3 % slower.
+__device__ __forceinline__ uint32_t mac_stage_total(uint32_t n) { return n / 2; }
+__device__ __forceinline__ uint32_t mac_stage_total(uint32_t, uint32_t total) { return total; }
+// Butterfly t of stage s of the network over tables of n rows: the pair (k, k + m2), m2 = 2^(s-1), and the exponent e of its twiddle
+// w^e, e = j * (n >> (s-1)) with j = k mod m2.  The work array may hold several tables of n rows end to end (the rebuild batch:
+// request r at r * n): t alone finds the pair because n is a multiple of every stage's block 2^s, and e is an entry of the table
+// of n, never of the work array's length.  SHARE = 1: k = (t >> (s-1)) 2^s + j, j = t mod m2.  SHARE = 16 / 64 (the wave-uniform
+// forms; n >> s >= SHARE): the SHARE butterflies t = (rest, i) of a wave have ONE j -- taken from the bits they share, and told to
+// the compiler as wave-uniform -- and differ in the stage's block (rest >> (s-1)) SHARE + i they belong to.
+template <uint32_t SHARE>
+__device__ __forceinline__ void mac_stage_index(uint32_t t, uint32_t n, int s, uint32_t& k, uint32_t& m2, uint32_t& e) {
+    m2 = 1u << (s - 1);
+    uint32_t j;
+    if constexpr (SHARE > 1) {
+        const uint32_t rest = t / SHARE;
+        j = rest & (m2 - 1);
+        k = ((((rest >> (s - 1)) * SHARE) | (t & (SHARE - 1u))) << s) + j;
+        j = (uint32_t)__builtin_amdgcn_readfirstlane((int)j);
+    } else {
+        j = t & (m2 - 1);
+        k = ((t >> (s - 1)) << s) + j;
+    }
+    e = j * (n >> (s - 1));
+}
+
 // plain little-endian limbs of (w^e mod p_icc) mod q for e in [0, n)   (cf. k_icc_twiddles in icc.hip.h)
 // The recoding of a TWIDDLE does not depend on the butterfly: the stages whose waves share a twiddle (>= 16 butterflies per twiddle
 // on four / eight lanes, >= 64 on one) read their 129 digit codes from a table made once per (N, curve) beside the twiddles
@@ -62,9 +96,7 @@ __global__ void k_mac_wnaf_codes(const uint32_t* __restrict__ tws, uint32_t entr
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= entries) return;
     uint32_t sc[8];
-    const uint4* w4 = reinterpret_cast<const uint4*>(tws + ((size_t)t << MACQ_CODES_EXP_SHIFT) * 8);
-    const uint4 a = w4[0], b = w4[1];
-    sc[0] = a.x; sc[1] = a.y; sc[2] = a.z; sc[3] = a.w; sc[4] = b.x; sc[5] = b.y; sc[6] = b.z; sc[7] = b.w;
+    mac_load_twiddle(sc, tws, (size_t)t << MACQ_CODES_EXP_SHIFT);
     uint32_t m0[4], m1[4];
     bool ng0, ng1;
     glv_split<G>(sc, m0, ng0, m1, ng1);
@@ -280,48 +312,43 @@ k_mac_load30(const uint8_t* __restrict__ in, uint32_t n, XYZZ<typename C::Fp>* _
     store_xyzz<M>(work + i, p);
 }
 
-// out[i] = wt * in[i] on the work array's own form (the Y part from the X part, see mac_fft.hip:mac_encode_core): one lane per MAC
+// out[i] = wt * in[i] on the work array's own form (the Y part from the X part, see mac_fft.hip:mac_encode_core): one lane per MAC.
+// The body, shared with the rebuild batch's kernel (server_rebuild_batch.hip.h: wt from the request's descriptor); wt is the same
+// on all 64 lanes -- a block is one wave
 template <class C>
-__global__ void __launch_bounds__(64)
-k_mac_scale30(const XYZZ<typename C::Fp>* __restrict__ in, uint32_t n, XYZZ<typename C::Fp>* __restrict__ out, MacScalar wt) {
+__device__ __forceinline__ void mac_scale_lane(const XYZZ<typename C::Fp>* __restrict__ in, uint32_t n, XYZZ<typename C::Fp>* __restrict__ out,
+                                               const uint32_t (&wt)[8]) {
     using M = typename C::Fp;
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     XYZZ<M> p = load_xyzz<M>(in + i);
+    XYZZ<M> r;
+    __shared__ __align__(8) uint16_t wdig[MACQ_CODES_STRIDE];              // (64 lanes = one wave per block; one scalar for every MAC)
+    mac30_scalar_mul_uniform<C>(&r, &p, wt, wdig);
+    store_xyzz<M>(out + i, r);
+}
+template <class C>
+__global__ void __launch_bounds__(64)
+k_mac_scale30(const XYZZ<typename C::Fp>* __restrict__ in, uint32_t n, XYZZ<typename C::Fp>* __restrict__ out, MacScalar wt) {
     uint32_t k[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) k[j] = wt.v[j];
-    XYZZ<M> r;
-    __shared__ __align__(8) uint16_t wdig[MACQ_CODES_STRIDE];              // (64 lanes = one wave per block; one scalar for every MAC)
-    mac30_scalar_mul_uniform<C>(&r, &p, k, wdig);
-    store_xyzz<M>(out + i, r);
+    mac_scale_lane<C>(in, n, out, k);
 }
 
 // UNIFORM (launched when n / 2^s >= 64 and n / 2 is a multiple of 256): the 64 lanes of a wave take butterflies of ONE twiddle index j
 // (they differ in the block of the stage they belong to): mac30_scalar_mul_uniform
-template <class C, bool UNIFORM>
+template <class C, bool UNIFORM, class... Total>
 __global__ void __launch_bounds__(256)      // (launched with 256 lanes: 21.1 against 22.2 ms at N = 2^17 with 64)
 k_mac_stage30(XYZZ<typename C::Fp>* __restrict__ work, const uint32_t* __restrict__ tws, uint32_t n, int s,
-              const uint16_t* __restrict__ codes) {
+              const uint16_t* __restrict__ codes, Total... total) {
+    static_assert(sizeof...(Total) == (UNIFORM ? 0 : 1), "the butterfly count: the per-butterfly form's last argument (mac_stage_total)");
     using M = typename C::Fp;
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n / 2) return;
-    const uint32_t m2 = 1u << (s - 1);
-    uint32_t j, k;
-    if constexpr (UNIFORM) {
-        const uint32_t rest = t >> 6;
-        j = rest & (m2 - 1);
-        k = ((((rest >> (s - 1)) << 6) | (t & 63u)) << s) + j;
-        j = (uint32_t)__builtin_amdgcn_readfirstlane((int)j);              // (the same on all 64 lanes: tell the compiler)
-    } else {
-        j = t & (m2 - 1);
-        k = ((t >> (s - 1)) << s) + j;
-    }
-    const uint32_t e = j * (n >> (s - 1));
-    uint32_t sc[8];
-    const uint4* q = reinterpret_cast<const uint4*>(tws + (size_t)e * 8);
-    uint4 a = q[0], b = q[1];
-    sc[0] = a.x; sc[1] = a.y; sc[2] = a.z; sc[3] = a.w; sc[4] = b.x; sc[5] = b.y; sc[6] = b.z; sc[7] = b.w;
+    if (t >= mac_stage_total(n, total...)) return;
+    uint32_t k, m2, e, sc[8];
+    mac_stage_index<UNIFORM ? 64u : 1u>(t, n, s, k, m2, e);
+    mac_load_twiddle(sc, tws, e);
     XYZZ<M> hi = load_xyzz<M>(work + k + m2);
     XYZZ<M> tm;
     if (s == 1) tm = hi;                            // stage 1: every twiddle is w^0 = 1 (uniform over the launch): no ladder
@@ -495,10 +522,11 @@ __device__ __forceinline__ void macq_butterfly_out(const XYZZ<M>* um, XYZZ<M>* s
 
 // UNIFORM (launched when n / 2^s >= 16): the 16 quads of a wave take butterflies of ONE twiddle index j (they differ in the block
 // of the stage they belong to), so the whole wave multiplies by one scalar: macq_ladder_uniform
-template <class C, bool UNIFORM>
+template <class C, bool UNIFORM, class... Total>
 __global__ void __launch_bounds__(4 * MACQ_BF) MACQ_GUEST_ATTR
 k_mac_stage30_quad(XYZZ<typename C::Fp>* __restrict__ work, const uint32_t* __restrict__ tws, uint32_t n, int s,
-                   const uint16_t* __restrict__ codes) {
+                   const uint16_t* __restrict__ codes, Total... total) {
+    static_assert(sizeof...(Total) == (UNIFORM ? 0 : 1), "the butterfly count: the per-butterfly form's last argument (mac_stage_total)");
     using M = typename C::Fp;
     MACQ_LDS(L);
     // a stage is one wave per SIMD walking ~200 dependent group operations: when another kernel shares the chip (the
@@ -507,27 +535,11 @@ k_mac_stage30_quad(XYZZ<typename C::Fp>* __restrict__ work, const uint32_t* __re
     __builtin_amdgcn_s_setprio(3);
     const uint32_t q = threadIdx.x >> 2, r = threadIdx.x & 3u, lane = threadIdx.x & 63u;
     uint32_t t = blockIdx.x * MACQ_BF + q;
-    const bool valid = t < n / 2;
+    const bool valid = t < mac_stage_total(n, total...);
     if (!valid) t = 0;                                                     // padding quads compute butterfly 0 and store nothing
-    const uint32_t m2 = 1u << (s - 1);
-    uint32_t j, k;
-    if constexpr (UNIFORM) {
-        // butterfly t = (rest, i16): j from the bits the wave shares, the stage's block number from the rest and the quad's place
-        const uint32_t rest = t >> 4;
-        j = rest & (m2 - 1);
-        k = ((((rest >> (s - 1)) << 4) | (t & 15u)) << s) + j;
-        j = (uint32_t)__builtin_amdgcn_readfirstlane((int)j);              // (the same on all 64 lanes: tell the compiler)
-    } else {
-        j = t & (m2 - 1);
-        k = ((t >> (s - 1)) << s) + j;
-    }
-    const uint32_t e = j * (n >> (s - 1));
-    uint32_t sc[8];
-    {
-        const uint4* w4 = reinterpret_cast<const uint4*>(tws + (size_t)e * 8);
-        const uint4 a = w4[0], b = w4[1];
-        sc[0] = a.x; sc[1] = a.y; sc[2] = a.z; sc[3] = a.w; sc[4] = b.x; sc[5] = b.y; sc[6] = b.z; sc[7] = b.w;
-    }
+    uint32_t k, m2, e, sc[8];
+    mac_stage_index<UNIFORM ? 16u : 1u>(t, n, s, k, m2, e);
+    mac_load_twiddle(sc, tws, e);
     macq_copy_coord<M>(&L.qd[q].tbl[0], work + k + m2, r);
     macq_copy_coord<M>(&L.um[q], work + k, r);
     macq_sync();
@@ -659,24 +671,17 @@ __device__ __forceinline__ void maco_butterfly(MacOctLds<typename C::Fp>& L, uin
 
 template <class C>
 __global__ void __launch_bounds__(8 * MACO_BF) MACO_ATTR
-k_mac_stage30_oct(XYZZ<typename C::Fp>* __restrict__ work, const uint32_t* __restrict__ tws, uint32_t n, int s) {
+k_mac_stage30_oct(XYZZ<typename C::Fp>* __restrict__ work, const uint32_t* __restrict__ tws, uint32_t n, uint32_t total, int s) {
     using M = typename C::Fp;
     MACO_LDS(L);
     __builtin_amdgcn_s_setprio(3);                                         // (as k_mac_stage30_quad: a latency-bound wave must win the issue arbitration)
     const uint32_t o = threadIdx.x >> 3, half = (threadIdx.x >> 2) & 1u, r = threadIdx.x & 3u, lane = threadIdx.x & 63u;
     uint32_t t = blockIdx.x * MACO_BF + o;
-    const bool valid = t < n / 2;
-    if (!valid) t = 0;
-    const uint32_t m2 = 1u << (s - 1);
-    const uint32_t j = t & (m2 - 1);
-    const uint32_t k = ((t >> (s - 1)) << s) + j;
-    const uint32_t e = j * (n >> (s - 1));
-    uint32_t sc[8];
-    {
-        const uint4* w4 = reinterpret_cast<const uint4*>(tws + (size_t)e * 8);
-        const uint4 a = w4[0], b = w4[1];
-        sc[0] = a.x; sc[1] = a.y; sc[2] = a.z; sc[3] = a.w; sc[4] = b.x; sc[5] = b.y; sc[6] = b.z; sc[7] = b.w;
-    }
+    const bool valid = t < total;
+    if (!valid) t = 0;                                                     // padding octets compute butterfly 0 and store nothing
+    uint32_t k, m2, e, sc[8];
+    mac_stage_index<1u>(t, n, s, k, m2, e);
+    mac_load_twiddle(sc, tws, e);
     if (half) macq_copy_coord<M>(&L.um[o], work + k, r);
     else macq_copy_coord<M>(&L.qd[o].tbl[0], work + k + m2, r);
     macq_sync();
@@ -700,12 +705,8 @@ k_mac_stage30_oct_uniform(XYZZ<typename C::Fp>* __restrict__ work, const uint32_
     const uint32_t o = (wave >> 1) * 16u + (lane >> 2);                   // octet of the block: 16 per wave pair
     const uint32_t qi = 2u * o + half;
     // n / 2 is a multiple of 32 and 16 octets share a twiddle (the launch condition): no padding octets
-    const uint32_t t = blockIdx.x * MACO_BF + o;
-    const uint32_t m2 = 1u << (s - 1);
-    const uint32_t rest = t >> 4;
-    const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)(rest & (m2 - 1)));
-    const uint32_t k = ((((rest >> (s - 1)) << 4) | (t & 15u)) << s) + j;
-    const uint32_t e = j * (n >> (s - 1));
+    uint32_t k, m2, e;
+    mac_stage_index<16u>(blockIdx.x * MACO_BF + o, n, s, k, m2, e);
     (void)tws;
     typename MacQuadLds<M>::Quad& Q = L.qd[o];
     if (half) macq_copy_coord<M>(&L.um[o], work + k, r);
@@ -780,11 +781,7 @@ __device__ __forceinline__ void maco_mix_one(MacOctLds<typename C::Fp>& L, const
     using M = typename C::Fp;
     const uint32_t o = threadIdx.x >> 3, half = (threadIdx.x >> 2) & 1u, r = threadIdx.x & 3u, lane = threadIdx.x & 63u;
     uint32_t sc[8];
-    {
-        const uint4* w4 = reinterpret_cast<const uint4*>(tws + (size_t)i * tw_step * 8);
-        const uint4 a = w4[0], b = w4[1];
-        sc[0] = a.x; sc[1] = a.y; sc[2] = a.z; sc[3] = a.w; sc[4] = b.x; sc[5] = b.y; sc[6] = b.z; sc[7] = b.w;
-    }
+    mac_load_twiddle(sc, tws, (size_t)i * tw_step);
     if (r == 0u) store_xyzz<M>(half ? &L.um[o] : &L.qd[o].tbl[0], load_affine_be_lazy<M>((half ? a0 : a1) + (size_t)i * 64));
     macq_sync();
     // the sums land in the table's entries 1 and 2 (the table is done with by then: each quad writes its own entry last)
@@ -830,26 +827,33 @@ k_mac_stage1_quad(XYZZ<typename C::Fp>* __restrict__ work, uint32_t n) {
 
 // init scaling of the Y part (k_mac_load30 with use_wt) with four lanes per MAC: work[i] = wt * MAC[i]
 // FROM_WORK: `in` is a work array (n points in the lazy memory form) instead of 64-byte big-endian affine MACs
-template <class C, bool FROM_WORK = false>
-__global__ void __launch_bounds__(4 * MACQ_BF) MACQ_GUEST_ATTR
-k_mac_load30_quad(const uint8_t* __restrict__ in, uint32_t n, XYZZ<typename C::Fp>* __restrict__ work, MacScalar wt) {
+// The body, shared with the rebuild batch's kernel (server_rebuild_batch.hip.h: wt from the request's descriptor); sc is the same
+// for every MAC of the launch's block
+template <class C, bool FROM_WORK>
+__device__ __forceinline__ void macq_scale_quad(const uint8_t* __restrict__ in, uint32_t n, XYZZ<typename C::Fp>* __restrict__ work,
+                                                const uint32_t (&sc)[8]) {
     using M = typename C::Fp;
     MACQ_LDS(L);
     __builtin_amdgcn_s_setprio(3);                                         // (beside the commitments of a CRebuild, as the stage kernel)
     const uint32_t q = threadIdx.x >> 2, r = threadIdx.x & 3u, lane = threadIdx.x & 63u;
     uint32_t i = blockIdx.x * MACQ_BF + q;
     const bool valid = i < n;
-    if (!valid) i = 0;
-    uint32_t sc[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) sc[j] = wt.v[j];
+    if (!valid) i = 0;                                                     // padding quads compute point 0 and store nothing
     if (FROM_WORK) macq_copy_coord<M>(&L.qd[q].tbl[0], reinterpret_cast<const XYZZ<M>*>(in) + i, r);
     else if (r == 0u) store_xyzz<M>(&L.qd[q].tbl[0], load_affine_be_lazy<M>(in + (size_t)i * 64));
     macq_sync();
     F30<M> c;
     bool inf;
-    macq_ladder_uniform<C>(L, q, r, lane, threadIdx.x >> 6, sc, c, inf);   // one scalar (a kernel argument) for every MAC: the sparse ladder
+    macq_ladder_uniform<C>(L, q, r, lane, threadIdx.x >> 6, sc, c, inf);   // one scalar for every MAC: the sparse ladder
     if (valid) macq_store_point<M>(work + i, c, inf, r);
+}
+template <class C, bool FROM_WORK = false>
+__global__ void __launch_bounds__(4 * MACQ_BF) MACQ_GUEST_ATTR
+k_mac_load30_quad(const uint8_t* __restrict__ in, uint32_t n, XYZZ<typename C::Fp>* __restrict__ work, MacScalar wt) {
+    uint32_t sc[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) sc[j] = wt.v[j];
+    macq_scale_quad<C, FROM_WORK>(in, n, work, sc);
 }
 
 
@@ -863,11 +867,7 @@ __device__ __forceinline__ void macq_mix_one(MacQuadLds<typename C::Fp>& L, cons
     using M = typename C::Fp;
     const uint32_t q = threadIdx.x >> 2, r = threadIdx.x & 3u, lane = threadIdx.x & 63u;
     uint32_t sc[8];
-    {
-        const uint4* w4 = reinterpret_cast<const uint4*>(tws + (size_t)i * tw_step * 8);
-        const uint4 a = w4[0], b = w4[1];
-        sc[0] = a.x; sc[1] = a.y; sc[2] = a.z; sc[3] = a.w; sc[4] = b.x; sc[5] = b.y; sc[6] = b.z; sc[7] = b.w;
-    }
+    mac_load_twiddle(sc, tws, (size_t)i * tw_step);
     if (r < 2u) store_xyzz<M>(r ? &L.um[q] : &L.qd[q].tbl[0], load_affine_be_lazy<M>((r ? a0 : a1) + (size_t)i * 64));   // lanes 0 and 1 side by side
     macq_sync();
     F30<M> c;
@@ -920,9 +920,7 @@ __device__ __forceinline__ void mac_mix_one(const uint8_t* __restrict__ a0, cons
                                             const uint32_t* __restrict__ tws, uint32_t tw_step, uint8_t* __restrict__ out) {
     using M = typename C::Fp;
     uint32_t sc[8];
-    const uint4* q = reinterpret_cast<const uint4*>(tws + (size_t)i * tw_step * 8);
-    uint4 a = q[0], b = q[1];
-    sc[0] = a.x; sc[1] = a.y; sc[2] = a.z; sc[3] = a.w; sc[4] = b.x; sc[5] = b.y; sc[6] = b.z; sc[7] = b.w;
+    mac_load_twiddle(sc, tws, (size_t)i * tw_step);
     XYZZ<M> hi = load_affine_be_lazy<M>(a1 + (size_t)i * 64);
     XYZZ<M> tm;
     mac30_scalar_mul<C>(&tm, &hi, sc);
@@ -952,21 +950,7 @@ k_mac_finish(const XYZZ<typename C::Fp>* __restrict__ work, uint32_t n, uint8_t*
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     XYZZ<M> p = load_xyzz<M>(work + i);
-    p = xyzz30_to_xyzz<M>(xyzz30_load_lazy<M>(&p));                              // the work array's lazy memory form
-    uint8_t* dst = out + (size_t)i * 64;
-    if (xyzz_is_inf<M>(p)) {
-        uint4 z = make_uint4(0, 0, 0, 0);
-        uint4* q = reinterpret_cast<uint4*>(dst);
-        q[0] = z; q[1] = z; q[2] = z; q[3] = z;
-        return;
-    }
-    Fe<M> inv = fe_inv_safegcd<M>(p.zzz);
-    Affine<M> a = xyzz_to_affine_with_inv<M>(p, inv);
-    Fe<M> one = fe_zero<M>();
-    one.v[0] = 1;
-    Fe<M> x = fe_mul_call<M>(a.x, one), y = fe_mul_call<M>(a.y, one);
-    store_be256(dst, x.v);
-    store_be256(dst + 32, y.v);
+    store_affine_be<M>(out + (size_t)i * 64, xyzz30_to_xyzz<M>(xyzz30_load_lazy<M>(&p)));     // the work array's lazy memory form
 }
 
 }  // namespace porla

@@ -7,14 +7,14 @@
 // at least one request), so the launch sequence depends on n_total and on the number of groups, never on K within a group:
 //
 //   the front (server_rebuild_batch.hip: sr_enqueue_front), over all K requests
-//     upload, k_sr_store, the passes of the data network but the last (k_sr_data), k_sr_mac_load, stage 1 .. log2 n_total, k_sr_mac_scale
+//     upload, k_sr_store, the passes of the data network but the last (k_sr_data), k_sr_mac_load, stage 1 .. log2 n_total, k_sr_mac_scale_*
 //   per group
-//     k_sr_data_aligned      the last pass: rows mod p_icc into data X / data Y, the alignment scalars into the workspace
+//     k_sr_data, SR_ALIGNED  the last pass: rows mod p_icc into data X / data Y, the alignment scalars into the workspace
 //     fb_commit / fb_fold    ONE commitment pass over the group's rows (the resident SRS table, or the generators' fixed base), sums projective
-//     k_sr_close_aligned     + complements, to affine, into MAC X / MAC Y; the sums to affine into align X / align Y
+//     k_sr_close, ALIGNED    + complements, to affine, into MAC X / MAC Y; the sums to affine into align X / align Y
 #include "kzg_state.hpp"
 #include "server_rebuild_host.hpp"
-#include "server_rebuild_aligned_batch.hip.h"
+#include "server_rebuild_batch.hip.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -34,16 +34,12 @@ static size_t sra_rows_max() {
     return v;
 }
 
-template <class C> struct SraCurve;
-template <> struct SraCurve<Bn254G1> { using Q = IccBn254Fr; static constexpr int id = 0; };
-template <> struct SraCurve<Secp256k1G> { using Q = IccSecp256k1Fn; static constexpr int id = 1; };
-
 // the last pass of the data network for requests g0 .. g0 + kg - 1, under the data side's table lease
 template <class Q>
 static int sra_launch_data(int curve, const SrFront& F, size_t g0, size_t kg, size_t n, size_t ncols, uint8_t* d_scalars, hipStream_t stream) {
-    SrPass plan[SR_MAX_PASSES];
-    const int passes = sr_pass_plan(ilog2u(n), ncols, ICC_TILE_LOG, plan);
-    const SrPass& P = plan[passes - 1];
+    IccPass plan[ICC_MAX_PASSES];
+    const int passes = icc_pass_plan(ilog2u(n), ncols, plan);
+    const IccPass& P = plan[passes - 1];
     const uint32_t *twp = nullptr, *twq = nullptr;
     int rc;
     if ((rc = icc_encode_tables_acquire(curve, n, stream, &twp, &twq))) return rc;
@@ -52,7 +48,7 @@ static int sra_launch_data(int curve, const SrFront& F, size_t g0, size_t kg, si
         const dim3 grid((unsigned)(P.col_tiles * (n >> P.ns)), (unsigned)kg);
         uint32_t* planes = F.planes ? F.planes + g0 * 2 * F.plane_words : nullptr;
 #define PORLA_SRA_LAUNCH(FIRST)                                                                                                       \
-    hipLaunchKernelGGL((k_sr_data_aligned<Q, FIRST>), grid, dim3(ICC30_SPLIT_THREADS), 0, stream, F.d_desc + g0, planes, F.plane_words, twp, \
+    hipLaunchKernelGGL((k_sr_data<Q, FIRST, SR_ALIGNED>), grid, dim3(ICC30_SPLIT_THREADS), 0, stream, F.d_desc + g0, planes, F.plane_words, twp, \
                        twq, (uint32_t)n, (uint32_t)ncols, P.s, P.ns, P.cc_log, d_scalars)
         if (passes == 1) PORLA_SRA_LAUNCH(true);
         else PORLA_SRA_LAUNCH(false);
@@ -67,27 +63,27 @@ static int sra_launch_data(int curve, const SrFront& F, size_t g0, size_t kg, si
 template <class C>
 static int sra_enqueue(ServerRebuildWs* ws, FixedBase<C>* fb, const porla_server_rebuild_req* reqs, size_t k, size_t n, size_t ncols,
                        hipStream_t stream) {
-    using Q = typename SraCurve<C>::Q;
+    using Q = typename IccCurve<C>::Q;
     using M = typename C::Fp;
     int rc;
     const size_t per_group = std::max<size_t>(1, sra_rows_max() / (2 * n));
     const size_t kg_max = std::min(k, per_group);
     if ((rc = ws->scalars.ensure(kg_max * 2 * n * ncols * 32))) return rc;          // (sr_check: the product does not overflow)
     SrFront F;
-    if ((rc = sr_enqueue_front(ws, SraCurve<C>::id, reqs, k, n, ncols, stream, &F))) return rc;
+    if ((rc = sr_enqueue_front(ws, IccCurve<C>::id, reqs, k, n, ncols, stream, &F))) return rc;
     uint8_t* d_scalars = (uint8_t*)ws->scalars.p;
     for (size_t g0 = 0; g0 < k; g0 += per_group) {
         const size_t kg = std::min(per_group, k - g0);
-        if ((rc = sra_launch_data<Q>(SraCurve<C>::id, F, g0, kg, n, ncols, d_scalars, stream))) return rc;
+        if ((rc = sra_launch_data<Q>(IccCurve<C>::id, F, g0, kg, n, ncols, d_scalars, stream))) return rc;
         auto close = [&](const XYZZ<M>* sums, uint32_t S) {
             ProfScope ps("server_rebuild_close_aligned", stream);
             const unsigned gx = (unsigned)std::min<size_t>((2 * n + 255) / 256, 512);
-            hipLaunchKernelGGL((k_sr_close_aligned<C>), dim3(gx, (unsigned)kg), dim3(256), 0, stream, F.d_desc + g0, (uint32_t)n,
+            hipLaunchKernelGGL((k_sr_close<C, true>), dim3(gx, (unsigned)kg), dim3(256), 0, stream, F.d_desc + g0, (uint32_t)n,
                                (const XYZZ<M>*)F.work + g0 * n, (const XYZZ<M>*)F.work_y + g0 * n, sums, S);
             PORLA_HIP(hipGetLastError());
             return (int)PORLA_OK;
         };
-        if constexpr (SraCurve<C>::id == 0) rc = kzg_commit_rows_raw(d_scalars, kg * 2 * n, stream, close);
+        if constexpr (IccCurve<C>::id == 0) rc = kzg_commit_rows_raw(d_scalars, kg * 2 * n, stream, close);
         else rc = commit_then(*fb, d_scalars, kg * 2 * n, ncols, stream, close);
         if (rc) return rc;
     }

@@ -9,10 +9,11 @@
 //   upload                   one copy of the host-built descriptors (pointers, wt as the data side and the MAC side see it)
 //   k_sr_store               block -> U[index - 1], mac -> MAC_U[index - 1]
 //   k_sr_data                ceil(log2 n_total / 9) passes over 1 024-symbol tiles, grid.y = request, under the data side's table lease;
-//                            the last pass writes data X and data Y = wt X
+//                            the last pass (its SR_CACHED form) writes data X and data Y = wt X
 //   k_sr_mac_load            MAC_U -> the work array of K * n_total points
-//   stage 1 .. log2 n_total  one launch each over the whole work array, under the MAC side's table lease
-//   k_sr_mac_scale           work_y = wt * work, grid.y = request
+//   stage 1 .. log2 n_total  mac_fft.hip's stage loop (mac_stages_leased: k_mac_stage1_quad, k_mac_stage30_oct / _quad / k_mac_stage30
+//                            with per-butterfly scalars), one launch each over the whole work array, under the MAC side's table lease
+//   k_sr_mac_scale_*         work_y = wt * work, grid.y = request
 //   k_sr_close               + complements, to affine, into MAC X / MAC Y; align X / align Y = infinity
 #include "server_rebuild_host.hpp"
 #include "server_rebuild_batch.hip.h"
@@ -29,30 +30,20 @@ namespace porla {
 static PerDevice<ServerRebuildWs> g_sr_ws;
 int sr_workspace(ServerRebuildWs** out) { return g_sr_ws.get(out); }
 
-// dynamic LDS above 64 KiB: a kernel must be told once per device (as mac_fft.hip does for the kernels these are forms of)
-static void sr_lds_attributes(ServerRebuildWs* ws) {
-    if (ws->lds_set) return;
-    auto set = [](const void* f, size_t bytes) { (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
-    set(reinterpret_cast<const void*>(&k_sr_mac_stage_oct<Bn254G1>), sizeof(MacOctLds<Bn254Fp>));
-    set(reinterpret_cast<const void*>(&k_sr_mac_stage_oct<Secp256k1G>), sizeof(MacOctLds<Secp256k1Fp>));
-    set(reinterpret_cast<const void*>(&k_sr_mac_stage_quad<Bn254G1>), sizeof(MacQuadLds<Bn254Fp>));
-    set(reinterpret_cast<const void*>(&k_sr_mac_stage_quad<Secp256k1G>), sizeof(MacQuadLds<Secp256k1Fp>));
-    set(reinterpret_cast<const void*>(&k_sr_mac_scale_quad<Bn254G1>), sizeof(MacQuadLds<Bn254Fp>));
-    set(reinterpret_cast<const void*>(&k_sr_mac_scale_quad<Secp256k1G>), sizeof(MacQuadLds<Secp256k1Fp>));
-    ws->lds_set = true;
+// dynamic LDS above 64 KiB: the four-lane scaling is the one such kernel launched from this file (the stages are mac_fft.hip's)
+static void sr_lds_attributes() {
+    static LdsOnce once;
+    once.set({lds_kernel(&k_sr_mac_scale_quad<Bn254G1>, sizeof(MacQuadLds<Bn254Fp>)),
+              lds_kernel(&k_sr_mac_scale_quad<Secp256k1G>, sizeof(MacQuadLds<Secp256k1Fp>))});
 }
-
-template <class C> struct SrCurve;
-template <> struct SrCurve<Bn254G1> { using Q = IccBn254Fr; static constexpr int id = 0; };
-template <> struct SrCurve<Secp256k1G> { using Q = IccSecp256k1Fn; static constexpr int id = 1; };
 
 // the data network of the K stores: icc_encode_core's passes (icc.hip), every pass one launch with grid.y = request; with_last =
 // false leaves the last pass to the caller (the aligned form's own kernel)
 template <class Q>
 static int sr_launch_data(int curve, const SrDesc* d_desc, uint32_t* d_planes, size_t plane_words, size_t k, size_t n, size_t ncols,
                           bool with_last, hipStream_t stream) {
-    SrPass plan[SR_MAX_PASSES];
-    const int passes = sr_pass_plan(ilog2u(n), ncols, ICC_TILE_LOG, plan);
+    IccPass plan[ICC_MAX_PASSES];
+    const int passes = icc_pass_plan(ilog2u(n), ncols, plan);
     if (!with_last && passes == 1) return PORLA_OK;
     const uint32_t *twp = nullptr, *twq = nullptr;
     int rc;
@@ -62,13 +53,13 @@ static int sr_launch_data(int curve, const SrDesc* d_desc, uint32_t* d_planes, s
         const dim3 grid((unsigned)(plan[pz].col_tiles * (n >> ns)), (unsigned)k);
         const bool first = pz == 0, last = pz == passes - 1;
         ProfScope ps("server_rebuild_data", stream);
-#define PORLA_SR_LAUNCH(F, L)                                                                                                    \
-    hipLaunchKernelGGL((k_sr_data<Q, F, L>), grid, dim3(ICC30_SPLIT_THREADS), 0, stream, d_desc, d_planes, plane_words, twp, twq, \
-                       (uint32_t)n, (uint32_t)ncols, s, ns, cc_log)
-        if (first && last) PORLA_SR_LAUNCH(true, true);
-        else if (first) PORLA_SR_LAUNCH(true, false);
-        else if (last) PORLA_SR_LAUNCH(false, true);
-        else PORLA_SR_LAUNCH(false, false);
+#define PORLA_SR_LAUNCH(F, FIN)                                                                                                    \
+    hipLaunchKernelGGL((k_sr_data<Q, F, FIN>), grid, dim3(ICC30_SPLIT_THREADS), 0, stream, d_desc, d_planes, plane_words, twp, twq, \
+                       (uint32_t)n, (uint32_t)ncols, s, ns, cc_log, (uint8_t*)nullptr)
+        if (first && last) PORLA_SR_LAUNCH(true, SR_CACHED);
+        else if (first) PORLA_SR_LAUNCH(true, SR_PASS);
+        else if (last) PORLA_SR_LAUNCH(false, SR_CACHED);
+        else PORLA_SR_LAUNCH(false, SR_PASS);
 #undef PORLA_SR_LAUNCH
     }
     if (hipGetLastError() != hipSuccess) { set_last_error("porla: server rebuild batch: a data launch failed"); rc = PORLA_ERR_HIP; }
@@ -78,37 +69,23 @@ static int sr_launch_data(int curve, const SrDesc* d_desc, uint32_t* d_planes, s
 
 // the MAC network of the K stores on one work array, the Y part and the close.  The forms: every stage with per-butterfly scalars --
 // eight lanes per butterfly while the whole call has at most MACO_MAX_BUTTERFLIES of them, four above that up to 4 * 2^quad_log points
-// (2^16 by default: where mac_encode_core leaves its four-lane forms), one lane beyond or with PORLA_MAC_QUAD_MAX = 0.  close = false
-// leaves the close to the caller (the aligned form's own kernel, behind its commitments).
+// (2^16 by default: where mac_encode_core leaves its four-lane forms), one lane beyond or with PORLA_MAC_QUAD_MAX = 0 (mac_fft.hip:
+// mac_stages).  close = false leaves the close to the caller (the aligned form's, behind its commitments).
 template <class C>
 static int sr_launch_mac(ServerRebuildWs* ws, const SrDesc* d_desc, size_t k, size_t n, bool close, hipStream_t stream) {
     using M = typename C::Fp;
     const uint32_t* tws = nullptr;
     int quad_log = 0, rc;
-    if ((rc = mac_mix_tables_acquire(SrCurve<C>::id, n, stream, &tws, &quad_log))) return rc;
+    if ((rc = mac_mix_tables_acquire(IccCurve<C>::id, n, stream, &tws, &quad_log))) return rc;
     XYZZ<M>* work = (XYZZ<M>*)ws->work.p;
     XYZZ<M>* work_y = (XYZZ<M>*)ws->work_y.p;
-    const int logn = ilog2u(n);
-    const size_t points = k * n, total = points / 2;
+    const size_t points = k * n;
     const bool quad = quad_log > 0 && points <= ((size_t)4 << quad_log);
     {
         ProfScope ps("server_rebuild_mac_load", stream);
         hipLaunchKernelGGL((k_sr_mac_load<C>), dim3((unsigned)((n + 63) / 64), (unsigned)k), dim3(64), 0, stream, d_desc, (uint32_t)n, work);
     }
-    for (int s = 1; s <= logn; s++) {
-        ProfScope ps("server_rebuild_mac_stage", stream);
-        if (quad && s == 1)
-            hipLaunchKernelGGL((k_mac_stage1_quad<C>), dim3((unsigned)((total + 63) / 64)), dim3(256), 0, stream, work, (uint32_t)points);
-        else if (quad && total <= MACO_MAX_BUTTERFLIES)
-            hipLaunchKernelGGL((k_sr_mac_stage_oct<C>), dim3((unsigned)((total + MACO_BF - 1) / MACO_BF)), dim3(8 * MACO_BF), sizeof(MacOctLds<M>),
-                               stream, work, tws, (uint32_t)n, (uint32_t)total, s);
-        else if (quad)
-            hipLaunchKernelGGL((k_sr_mac_stage_quad<C>), dim3((unsigned)((total + MACQ_BF - 1) / MACQ_BF)), dim3(4 * MACQ_BF), sizeof(MacQuadLds<M>),
-                               stream, work, tws, (uint32_t)n, (uint32_t)total, s);
-        else
-            hipLaunchKernelGGL((k_sr_mac_stage_lane<C>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, work, tws, (uint32_t)n,
-                               (uint32_t)total, s);
-    }
+    mac_stages_leased(IccCurve<C>::id, work, points, n, quad, tws, "server_rebuild_mac_stage", stream);
     {
         ProfScope ps("server_rebuild_mac_scale", stream);
         if (quad)
@@ -121,7 +98,8 @@ static int sr_launch_mac(ServerRebuildWs* ws, const SrDesc* d_desc, size_t k, si
     if (close) {
         ProfScope ps("server_rebuild_close", stream);
         const unsigned gx = (unsigned)std::min<size_t>((2 * n + 255) / 256, 512);
-        hipLaunchKernelGGL((k_sr_close<C>), dim3(gx, (unsigned)k), dim3(256), 0, stream, d_desc, (uint32_t)n, work, work_y);
+        hipLaunchKernelGGL((k_sr_close<C, false>), dim3(gx, (unsigned)k), dim3(256), 0, stream, d_desc, (uint32_t)n, work, work_y,
+                           (const XYZZ<M>*)nullptr, 0u);
     }
     if (hipGetLastError() != hipSuccess) { set_last_error("porla: server rebuild batch: a MAC launch failed"); rc = PORLA_ERR_HIP; }
     const int r1 = mac_mix_tables_release(stream);
@@ -133,7 +111,7 @@ static int sr_launch_mac(ServerRebuildWs* ws, const SrDesc* d_desc, size_t k, si
 template <class C>
 static int sr_enqueue(ServerRebuildWs* ws, const porla_server_rebuild_req* reqs, size_t k, size_t n, size_t ncols, bool cached, hipStream_t stream,
                       SrFront* F) {
-    using Q = typename SrCurve<C>::Q;
+    using Q = typename IccCurve<C>::Q;
     using M = typename C::Fp;
     int rc;
     const int logn = ilog2u(n);
@@ -145,7 +123,7 @@ static int sr_enqueue(ServerRebuildWs* ws, const porla_server_rebuild_req* reqs,
     if (planes && (rc = ws->planes.ensure(k * 2 * plane_words * 4))) return rc;
     if ((rc = ws->work.ensure(k * n * sizeof(XYZZ<M>)))) return rc;
     if ((rc = ws->work_y.ensure(k * n * sizeof(XYZZ<M>)))) return rc;
-    sr_lds_attributes(ws);
+    sr_lds_attributes();
     {
         SrDesc* hd = (SrDesc*)ws->h_list.h;
         for (size_t a = 0; a < k; a++) {
@@ -157,7 +135,7 @@ static int sr_enqueue(ServerRebuildWs* ws, const porla_server_rebuild_req* reqs,
             D.mac_x = (uint8_t*)R.d_mac_x; D.mac_y = (uint8_t*)R.d_mac_y;
             D.align_x = (uint8_t*)R.d_align_x; D.align_y = (uint8_t*)R.d_align_y;
             uint8_t be[32];
-            (void)icc_wt_residues(SrCurve<C>::id, n, R.write_step, D.wt_p, D.wt_q, be);
+            (void)icc_wt_residues(IccCurve<C>::id, n, R.write_step, D.wt_p, D.wt_q, be);
             h_load_be(D.wt_sc, be);
             fe_reduce_plain<Q>(D.wt_sc, 8);                    // the group sees wt mod its order (convert_ZZ_to_scalar / fr.SetBytes)
             D.row = (uint32_t)(R.index - 1); D.pad = 0;
@@ -172,7 +150,7 @@ static int sr_enqueue(ServerRebuildWs* ws, const porla_server_rebuild_req* reqs,
         PORLA_HIP(hipGetLastError());
     }
     if (F) *F = SrFront{d_desc, (uint32_t*)ws->planes.p, plane_words, ws->work.p, ws->work_y.p};
-    if ((rc = sr_launch_data<Q>(SrCurve<C>::id, d_desc, (uint32_t*)ws->planes.p, plane_words, k, n, ncols, cached, stream))) return rc;
+    if ((rc = sr_launch_data<Q>(IccCurve<C>::id, d_desc, (uint32_t*)ws->planes.p, plane_words, k, n, ncols, cached, stream))) return rc;
     return sr_launch_mac<C>(ws, d_desc, k, n, cached, stream);
 }
 
@@ -185,12 +163,10 @@ int sr_enqueue_front(ServerRebuildWs* ws, int curve, const porla_server_rebuild_
 int sr_check(const char* who, const porla_server_rebuild_req* reqs, size_t k, size_t n_total, size_t n_cols, int curve) {
     auto bad = [&](const std::string& what) { return bad_arg(who, what); };
     if (k && !reqs) return bad("reqs is NULL");
-    int ln = 0;
-    while (((size_t)1 << ln) < n_total && ln < 62) ln++;
-    if (n_total < 2 || ((size_t)1 << ln) != n_total) return bad("n_total must be a power of two, 2 .. 2^16");
-    if (n_total > ((size_t)1 << 16))
+    if (n_total > ((size_t)1 << 16) && (n_total & (n_total - 1)) == 0)
         return bad("n_total above 2^16: the batch stops at 2^16 rows; larger files go through the single-file calls "
                    "porla_icc_encode_xy_device and porla_icc_mac_encode_xy_device");
+    if (int rc = check_n_total(who, n_total, 16)) return rc;
     if (n_cols == 0) return bad("n_cols is 0");
     if (curve != 0 && curve != 1) return bad("curve must be 0 (BN254 / KZG) or 1 (secp256k1 / IPA)");
     if (k > 0xffffu) return bad("more than 65535 requests in one call");

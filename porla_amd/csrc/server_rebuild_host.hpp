@@ -1,6 +1,6 @@
 // Host pieces the two server rebuild calls share (server_rebuild_batch.hip: the CRebuild_Cached form, which defines them;
-// server_rebuild_aligned_batch.hip: the CRebuild_No_Cached form): the workspace, the plan of the data network's passes, the argument
-// checks, and the front of the launch sequence -- everything up to the point where the two forms part.
+// server_rebuild_aligned_batch.hip: the CRebuild_No_Cached form): the workspace, the argument checks, and the front of the launch
+// sequence -- everything up to the point where the two forms part.
 #pragma once
 #include "batch_host.hpp"
 #include "icc_host.hpp"
@@ -17,26 +17,7 @@ struct ServerRebuildWs {
     Buf scalars;                  // the aligned form's rows of alignment scalars, one group of requests at a time
     PinnedList h_list;
     UseFence fence;
-    bool lds_set = false;
 };
-
-// the passes of the data network over n = 2^logn rows of ncols symbols (icc_encode_core's, icc.hip): pass z runs stages
-// s .. s + ns - 1 on tiles of 2^ns rows x 2^cc_log columns = ICC_TILE_ELEMS symbols, no wider than the row
-struct SrPass { int s, ns, cc_log; size_t col_tiles; };
-constexpr int SR_MAX_PASSES = 8;
-static inline int sr_pass_plan(int logn, size_t ncols, int tile_log, SrPass out[SR_MAX_PASSES]) {
-    const int max_ns = tile_log - 1;
-    const int passes = (logn + max_ns - 1) / max_ns;
-    int s = 1;
-    for (int pz = 0; pz < passes; pz++) {
-        const int ns = (logn - (s - 1) + (passes - pz) - 1) / (passes - pz);
-        int cc_log = tile_log - ns;
-        while (cc_log > 0 && ((size_t)1 << (cc_log - 1)) >= ncols) cc_log--;
-        out[pz] = SrPass{s, ns, cc_log, (ncols + ((size_t)1 << cc_log) - 1) >> cc_log};
-        s += ns;
-    }
-    return passes;
-}
 
 // what the front leaves for the rest of a call (device pointers into the workspace; work / work_y: K * n_total projective points)
 struct SrFront {

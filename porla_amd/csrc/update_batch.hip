@@ -12,6 +12,7 @@
 //   k_update_close           incoming half over resident half at the request's level, then the complements onto MAC X / MAC Y
 #include "kzg_state.hpp"
 #include "update_batch.hip.h"
+#include "icc_host.hpp"
 #include "../../include/porla_gpu.h"
 
 #include <algorithm>
@@ -32,26 +33,18 @@ struct UpdateBatchWs {
     Buf list, scalars;
     PinnedList h_list;
     UseFence fence;
-    bool lds_set = false;
 };
 static PerDevice<UpdateBatchWs> g_upd_ws;
 
-// dynamic LDS above 64 KiB: a kernel must be told once per device (as mac_fft.hip does for the kernels these are forms of)
-static void update_lds_attributes(UpdateBatchWs* ws) {
-    if (ws->lds_set) return;
-    auto set = [](const void* f, size_t bytes) { (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
-    set(reinterpret_cast<const void*>(&k_update_place<Bn254G1>), sizeof(MacOctLds<Bn254Fp>));
-    set(reinterpret_cast<const void*>(&k_update_place<Secp256k1G>), sizeof(MacOctLds<Secp256k1Fp>));
-    set(reinterpret_cast<const void*>(&k_update_mix_points_oct<Bn254G1>), sizeof(MacOctLds<Bn254Fp>));
-    set(reinterpret_cast<const void*>(&k_update_mix_points_oct<Secp256k1G>), sizeof(MacOctLds<Secp256k1Fp>));
-    set(reinterpret_cast<const void*>(&k_update_mix_points_quad<Bn254G1>), sizeof(MacQuadLds<Bn254Fp>));
-    set(reinterpret_cast<const void*>(&k_update_mix_points_quad<Secp256k1G>), sizeof(MacQuadLds<Secp256k1Fp>));
-    ws->lds_set = true;
+// dynamic LDS above 64 KiB: told once per device (batch_host.hpp:LdsOnce)
+static void update_lds_attributes() {
+    static LdsOnce once;
+    constexpr size_t oct_bn = sizeof(MacOctLds<Bn254Fp>), oct_secp = sizeof(MacOctLds<Secp256k1Fp>);
+    once.set({lds_kernel(&k_update_place<Bn254G1>, oct_bn), lds_kernel(&k_update_place<Secp256k1G>, oct_secp),
+              lds_kernel(&k_update_mix_points_oct<Bn254G1>, oct_bn), lds_kernel(&k_update_mix_points_oct<Secp256k1G>, oct_secp),
+              lds_kernel(&k_update_mix_points_quad<Bn254G1>, sizeof(MacQuadLds<Bn254Fp>)),
+              lds_kernel(&k_update_mix_points_quad<Secp256k1G>, sizeof(MacQuadLds<Secp256k1Fp>))});
 }
-
-template <class C> struct UpdCurve;
-template <> struct UpdCurve<Bn254G1> { using Q = IccBn254Fr; static constexpr int id = 0; };
-template <> struct UpdCurve<Secp256k1G> { using Q = IccSecp256k1Fn; static constexpr int id = 1; };
 
 struct UpdPlan {
     const UpdDesc* d_desc;
@@ -72,13 +65,13 @@ static int launch_place(const UpdPlan& P, const XYZZ<typename C::Fp>* sums, uint
 // the mixes of steps 0 .. lmax - 1 under the table leases (the MAC side's lock first, as mac_fft.hip's matrix form takes them)
 template <class C>
 static int launch_steps(const UpdPlan& P, const std::vector<uint32_t>& active, uint32_t lmax, size_t n_total) {
-    using Q = typename UpdCurve<C>::Q;
+    using Q = typename IccCurve<C>::Q;
     using M = typename C::Fp;
     const uint32_t* tws = nullptr;
     const uint32_t* tw30 = nullptr;
     int quad_log = 0, rc;
-    if ((rc = mac_mix_tables_acquire(UpdCurve<C>::id, n_total, P.stream, &tws, &quad_log))) return rc;
-    if ((rc = icc_mix_tables_acquire(UpdCurve<C>::id, n_total, P.stream, &tw30))) { (void)mac_mix_tables_release(P.stream); return rc; }
+    if ((rc = mac_mix_tables_acquire(IccCurve<C>::id, n_total, P.stream, &tws, &quad_log))) return rc;
+    if ((rc = icc_mix_tables_acquire(IccCurve<C>::id, n_total, P.stream, &tw30))) { (void)mac_mix_tables_release(P.stream); return rc; }
     for (uint32_t i = 0; i < lmax && !rc; i++) {
         const uint32_t a = active[i], tw_step = (uint32_t)(n_total >> i);
         {
@@ -109,7 +102,7 @@ static int launch_steps(const UpdPlan& P, const std::vector<uint32_t>& active, u
 template <class C>
 static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_update_req* reqs, size_t k, size_t ncols, size_t n_total,
                           hipStream_t stream) {
-    using Q = typename UpdCurve<C>::Q;
+    using Q = typename IccCurve<C>::Q;
     int rc;
     // ---- the plan: requests by level, highest first (stable), so that the requests step i concerns are the first active[i]
     std::vector<uint32_t> order(k);
@@ -133,7 +126,7 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
             UpdDesc& D = hd[a];
             D.block = (const uint8_t*)R.d_block; D.mac = (const uint8_t*)R.d_mac; D.comp = (const uint8_t*)R.d_complements;
             uint8_t be[32];
-            (void)icc_wt_residues(UpdCurve<C>::id, n_total, R.write_step, D.wt_p, D.wt_q, be);
+            (void)icc_wt_residues(IccCurve<C>::id, n_total, R.write_step, D.wt_p, D.wt_q, be);
             h_load_be(D.wt_sc, be);
             fe_reduce_plain<Q>(D.wt_sc, 8);                    // the group sees wt mod its order (convert_ZZ_to_scalar / fr.SetBytes)
             D.level = (uint32_t)R.level; D.pad = 0;
@@ -144,7 +137,7 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
     }
     if ((rc = ws->list.ensure(list_b))) return rc;
     if ((rc = ws->scalars.ensure(k * ncols * 32))) return rc;
-    update_lds_attributes(ws);
+    update_lds_attributes();
     if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
     UpdPlan P;
     P.d_desc = (const UpdDesc*)ws->list.p;
@@ -159,7 +152,7 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
     }
     // ---- 2. the K commitments, then the four point slots
     auto place = [&](const XYZZ<typename C::Fp>* sums, uint32_t S) { return launch_place<C>(P, sums, S); };
-    if constexpr (UpdCurve<C>::id == 0) rc = kzg_commit_rows_raw((const uint8_t*)ws->scalars.p, k, stream, place);
+    if constexpr (IccCurve<C>::id == 0) rc = kzg_commit_rows_raw((const uint8_t*)ws->scalars.p, k, stream, place);
     else rc = commit_then(*fb, (const uint8_t*)ws->scalars.p, k, ncols, stream, place);
     if (rc) return rc;
     // ---- 3. the rebuild steps
@@ -179,9 +172,7 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
 static int update_check(const char* who, const porla_update_req* reqs, size_t k, size_t n_total) {
     auto bad = [&](const std::string& what) { return bad_arg(who, what); };
     if (k && !reqs) return bad("reqs is NULL");
-    int ln = 0;
-    while (((size_t)1 << ln) < n_total && ln < 62) ln++;
-    if (n_total < 2 || ((size_t)1 << ln) != n_total || n_total > ((size_t)1 << 30)) return bad("n_total must be a power of two, 2 .. 2^30");
+    if (int rc = check_n_total(who, n_total, 30)) return rc;
     if (k > 0xffffu) return bad("more than 65535 requests in one call");
     std::unordered_set<const void*> seen;
     for (size_t a = 0; a < k; a++) {
