@@ -89,19 +89,6 @@ static int ensure_mac_codes(MacWs* ws, int curve, size_t n, hipStream_t stream) 
     return PORLA_OK;
 }
 
-// dynamic LDS of the four- and eight-lane kernels (mac_fft.hip.h:MACQ_LDS / MACO_LDS) is above 64 KiB: told once per device
-// (batch_host.hpp:LdsOnce), before the first launch of any of them from this file
-template <class C> constexpr size_t macq_lds_bytes() { return sizeof(MacQuadLds<typename C::Fp>); }
-template <class C> constexpr size_t maco_lds_bytes() { return sizeof(MacOctLds<typename C::Fp>); }
-template <class C>
-static void mac_lds_attributes() {
-    static LdsOnce once;
-    constexpr size_t quad = macq_lds_bytes<C>(), oct = maco_lds_bytes<C>();
-    once.set({lds_kernel(&k_mac_stage30_quad<C, false, uint32_t>, quad), lds_kernel(&k_mac_stage30_quad<C, true>, quad),
-              lds_kernel(&k_mac_load30_quad<C, false>, quad), lds_kernel(&k_mac_load30_quad<C, true>, quad), lds_kernel(&k_mac_mix_quad<C>, quad),
-              lds_kernel(&k_mac_stage30_oct<C>, oct), lds_kernel(&k_mac_stage30_oct_uniform<C>, oct), lds_kernel(&k_mac_mix_oct<C>, oct)});
-}
-
 template <class C, class Q>
 static int mac_mix_core(MacWs* ws, int curve, const uint8_t* d_a0, const uint8_t* d_a1, size_t len, size_t n_total, uint8_t* d_out,
                         hipStream_t stream, const uint8_t* d_b0 = nullptr, const uint8_t* d_b1 = nullptr, uint8_t* d_out_b = nullptr) {

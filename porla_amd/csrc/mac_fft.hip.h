@@ -12,7 +12,13 @@
 // lazy memory form of ec30.hip.h) stay in HBM between stages: 2 * 128 B per MAC per stage, against ~2 000 field products per
 // butterfly -- VALU (integer multiply) bound.  Up to 2^16 rows a butterfly runs on the four lanes of a quad with its accumulator
 // in registers (k_mac_stage30_quad), above that one lane per butterfly (k_mac_stage30).
+//
+// Checked per form by tools/ladder_check.hip / tests/test_ladder_gpu.py: the stage kernels and the by-value scalings below are
+// launched on a scalar table of the test's in place of the twiddles (stage s reads entry j (n >> (s-1)): mac_stage_index), scalars
+// built from their endomorphism halves, expected points from Python integers (tests/ladder_vectors.py); mac_wnaf5_step and
+// k_mac_wnaf_codes word for word against a Python model.  End to end (tests/test_mac_fft_gpu.py) the ladders only meet twiddles.
 #pragma once
+#include "batch_host.hpp"
 #include "fixed_base.hip.h"
 #include "icc.hip.h"
 #include "quad30.hip.h"
@@ -385,7 +391,7 @@ constexpr int MACQ_BF = 64;                       // butterflies per block: 256 
 // guest-room form of k_fb_commit) 128 registers are free.  Held to 128 they start at once there (the arithmetic is one field
 // product per lane at a time).  secp256k1 has no such neighbour and a fold that wants more registers: C::MACQ_WAVES = 2 there.
 #define MACQ_GUEST_ATTR __attribute__((amdgpu_waves_per_eu(C::MACQ_WAVES, C::MACQ_WAVES)))
-// ... and their LDS state is DYNAMIC shared memory (sizeof(MacQuadLds<M>) at the launch, mac_fft.hip:macq_lds_bytes): with the
+// ... and their LDS state is DYNAMIC shared memory (sizeof(MacQuadLds<M>) at the launch, macq_lds_bytes below): with the
 // state declared statically the compiler knows that one block fits a compute unit, concludes "occupancy 1" and gives the kernel
 // descriptor 264 registers whatever the code uses -- the guest would not fit again
 #define MACQ_LDS(L) extern __shared__ __align__(16) unsigned char macq_lds_raw[]; \
@@ -951,6 +957,20 @@ k_mac_finish(const XYZZ<typename C::Fp>* __restrict__ work, uint32_t n, uint8_t*
     if (i >= n) return;
     XYZZ<M> p = load_xyzz<M>(work + i);
     store_affine_be<M>(out + (size_t)i * 64, xyzz30_to_xyzz<M>(xyzz30_load_lazy<M>(&p)));     // the work array's lazy memory form
+}
+
+// ---------------------------------------------------------------- host: what a launch of the four- and eight-lane kernels needs
+// Their dynamic LDS (MACQ_LDS / MACO_LDS) is above 64 KiB: told once per device (batch_host.hpp:LdsOnce) before the first launch of
+// any of them from the translation unit that launches (mac_fft.hip; tools/ladder_check.hip, the per-form driver of the tests)
+template <class C> constexpr size_t macq_lds_bytes() { return sizeof(MacQuadLds<typename C::Fp>); }
+template <class C> constexpr size_t maco_lds_bytes() { return sizeof(MacOctLds<typename C::Fp>); }
+template <class C>
+static void mac_lds_attributes() {
+    static LdsOnce once;
+    constexpr size_t quad = macq_lds_bytes<C>(), oct = maco_lds_bytes<C>();
+    once.set({lds_kernel(&k_mac_stage30_quad<C, false, uint32_t>, quad), lds_kernel(&k_mac_stage30_quad<C, true>, quad),
+              lds_kernel(&k_mac_load30_quad<C, false>, quad), lds_kernel(&k_mac_load30_quad<C, true>, quad), lds_kernel(&k_mac_mix_quad<C>, quad),
+              lds_kernel(&k_mac_stage30_oct<C>, oct), lds_kernel(&k_mac_stage30_oct_uniform<C>, oct), lds_kernel(&k_mac_mix_oct<C>, oct)});
 }
 
 }  // namespace porla

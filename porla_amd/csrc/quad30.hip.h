@@ -2,6 +2,9 @@
 // (ec30.hip.h: xyzz30_dbl_quadreg / xyzz30_add_quadreg): the MAC-side encode's ladders (mac_fft.hip.h) and the batched MSM's tiny
 // entries and window fold (msm_batch.hip.h).  The signed 4-bit recoding of a 128-bit half-scalar, the quad-private LDS ordering, the
 // memory form of one residue, the general addition with its rare equal-x fallback, and the windowed ladder built on them.
+// Checked per form by tools/ladder_check.hip / tests/test_ladder_gpu.py: mac_signed_digit word for word against a Python model on
+// chosen 128-bit patterns, macq_ladder inside k_mac_stage30_quad on scalars built from their endomorphism halves
+// (tests/ladder_vectors.py), and through the batched MSM's tiny entries by tests/test_msm_batch_gpu.py.
 #pragma once
 #include "ec30.hip.h"
 #include "glv.hip.h"

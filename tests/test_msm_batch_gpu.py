@@ -125,6 +125,36 @@ def test_edge_values(mx, curve):
     assert got[8] == INF and got[10] == INF and got[11] == INF and got[14] == INF
 
 
+@pytest.mark.parametrize("curve", CURVES)
+def test_scalars_built_from_their_endomorphism_halves(mx, curve):
+    """the public path by which user scalars reach quad30.hip.h:macq_ladder: the scalar families of tests/ladder_vectors.py (edge
+    values, halves built from digit patterns with every sign pair, a set 33rd window, NAF shapes) as one-pair tiny entries over one
+    point, then the same scalars eight to an entry over eight points -- against the oracle and the single calls"""
+    from tests import ec_vectors as ev
+    from tests import ladder_vectors as lv
+    C = ev.CURVES[curve]
+    fam = lv.families(C, "abcd")
+    counts = {f: sum(1 for g, _ in fam if g == f) for f in "abcd"}
+    assert counts["b"] >= 1000 and counts["c"] == (32 if curve == "secp256k1" else 0) and counts["d"] == 12 and lv.order(C) == R[curve]
+    ks = [k for _, k in fam]
+    ks += ks[:-len(ks) % 8]                                         # whole entries of eight
+    base = points_for(curve, 8)
+    pts8 = [base[64 * i:64 * i + 64] for i in range(8)]
+    entries = [([k], [pts8[0]]) for k in ks] + [(ks[i:i + 8], pts8) for i in range(0, len(ks), 8)]
+    sc = b"".join(be(x) for e in entries for x in e[0])
+    pts = b"".join(p for e in entries for p in e[1])
+    offsets = mx.batch_offsets([len(e[0]) for e in entries])
+    got, (d_sc, d_pt) = run_batch(mx, curve, sc, pts, offsets)
+    ones = singles(mx, curve, d_sc, d_pt, offsets)
+    checked = 0
+    for i, e in enumerate(entries):
+        lo, hi = offsets[i], offsets[i + 1]
+        assert got[i] == oracle(curve, sc[32 * lo:32 * hi], pts[64 * lo:64 * hi], hi - lo), "entry %d: scalars %s" % (i, [hex(x) for x in e[0]])
+        assert got[i] == ones[i], "entry %d differs from the single call" % i
+        checked += 1
+    assert checked == len(entries) and len(ks) >= sum(counts.values()) > 1200 and len(ks) % 8 == 0
+
+
 def test_reference_constants_kat_through_one_batch(mx):
     """tests.c:4738-4751: the 32 842 keys as one-pair secp256k1 entries over G in ONE batch call, hashed with tests.c's
     accumulate; no oracle in between"""
