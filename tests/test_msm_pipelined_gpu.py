@@ -7,6 +7,7 @@ compositions (P and -P, P twice, points at infinity, among ordinary points) and 
 buckets: over that many buckets every composition meets every position -- first (the copy), second (the affine + affine form),
 third (the first iteration of the straight-line loop) and last -- and every such meeting is a lane that leaves the fast loop with
 that entry still to do.  The same buckets feed k_tree_front2 infinite, equal and opposite operands in neighbouring buckets.
+Pinned positions are tests/test_bucket_sum_gpu.py's: it launches the accumulation kernels on bucket lists it wrote itself.
 """
 import random
 
