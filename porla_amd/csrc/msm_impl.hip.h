@@ -4,6 +4,7 @@
 #include "engine.hpp"
 #include "host_fold64.hpp"
 #include "msm_small.hip.h"
+#include "msm_tree.hip.h"
 #include <cstdlib>
 #include <chrono>
 #include <thread>
@@ -14,21 +15,6 @@
 namespace porla {
 
 static inline int ilog2(size_t n) { int l = 0; while (n >>= 1) l++; return l; }
-
-// threads of the per-window tail block: the tail takes over at the first level whose additions per window fit one pass (four
-// lanes per addition).  Same-box sweep of a blocking 2^20-pair MSM, profiles/r05_f_tree_tail_sweep.txt: 256 threads 1.58 ms,
-// 512 threads 1.53-1.55, 1 024 threads 1.55-1.64 (one block per window then holds a compute unit for eight levels).
-static inline uint32_t tree_tail_threads() { return 512u; }
-// quad = four lanes per addition: a pass of the tail holds threads / 4 additions
-static inline bool tree_quad() { return true; }
-constexpr uint32_t TREE_QUAD_MAX_TASKS = 16384;         // levels up to this many additions run four lanes per addition ...
-constexpr uint32_t TREE_QUAD_MAX_TASKS_LONE = 65536;    // ... for a caller that waits for this MSM alone (idle lanes to spend on latency; same sweep)
-static inline uint32_t tree_tail_start(uint32_t B, uint32_t nlev, bool quad) {
-    const uint32_t cap = quad ? tree_tail_threads() / 4 : tree_tail_threads();
-    uint32_t l = 0;
-    while (l + 1 < nlev && (l + 1) * (B >> (l + 1)) > cap) l++;
-    return l;
-}
 
 // Window width for m sub-scalars of `bits` bits, from a time model in microseconds fitted to the sweeps in profiles/
 // (2^7 .. 2^20 pairs):
@@ -393,13 +379,19 @@ template <class C>
 static int msm_tree_launch(Workspace* ws, const XYZZ<typename C::Fp>* buckets, int c, int W, bool glv, hipStream_t stream) {
     using M = typename C::Fp;
     int rc;
-    const uint32_t B = 1u << (c - 1);
-    const size_t nb = (size_t)W * B;
-    const uint32_t nlev = (uint32_t)(c - 1);
-    // (sizes for the two halves of the window set, each with its own end slack)
-    if ((rc = ws->tree_s.ensure((nb + 2) * sizeof(XYZZ<M>)))) return rc;               // all S levels: nb/2 + nb/4 + ...
-    if ((rc = ws->tree_m.ensure((2 * (nb / 4) + 6) * sizeof(XYZZ<M>)))) return rc;     // two ping-pong halves
-    if ((rc = ws->tree_mt.ensure((2 * (size_t)W * (B / 4 + 1) + 4) * sizeof(XYZZ<M>)))) return rc;  // the tail's private halves
+    // the schedule and the buffer layout: msm_tree.hip.h, with the product's own choices
+    // (kept per thread from call to call: a pipeline runs one shape over and over)
+    static thread_local TreePlan plan;
+    static thread_local int plan_c = 0, plan_W = 0, plan_lone = -1;
+    if (plan_c != c || plan_W != W || plan_lone != (ws->lone ? 1 : 0)) {
+        plan_c = 0;
+        const std::string refused = tree_plan(plan, c, W, ws->lone, C::F30_LAZY);
+        if (!refused.empty()) { set_last_error("porla: reduction tree: " + refused); return PORLA_ERR_STATE; }
+        plan_c = c; plan_W = W; plan_lone = ws->lone ? 1 : 0;
+    }
+    if ((rc = ws->tree_s.ensure(plan.s_entries * sizeof(XYZZ<M>)))) return rc;
+    if ((rc = ws->tree_m.ensure(plan.m_entries * sizeof(XYZZ<M>)))) return rc;
+    if ((rc = ws->tree_mt.ensure(plan.mt_entries * sizeof(XYZZ<M>)))) return rc;
     if (ws->h_windows_cap < (size_t)W * c * sizeof(XYZZ<M>) || ws->h_windows_cap < 64 * 1024) {
         if (ws->h_windows) PORLA_HIP(hipHostFree(ws->h_windows));
         ws->h_windows_cap = 64 * 1024;
@@ -407,12 +399,7 @@ static int msm_tree_launch(Workspace* ws, const XYZZ<typename C::Fp>* buckets, i
     }
     void* h_windows_dev = nullptr;
     PORLA_HIP(hipHostGetDevicePointer(&h_windows_dev, ws->h_windows, 0));
-    // The windows are independent trees.  With enough buckets they run as TWO halves on two streams: the first levels of a tree
-    // are throughput bound, the last ones (quad levels, the tail) latency bound -- side by side the latency-bound levels of one
-    // half run under the large levels of the other.
-    // (only for a caller that waits for this one device-resident MSM: -1.7 % at 2^18 and 2^20 pairs; with a second MSM in
-    // flight -- the two-phase API -- the other MSM already fills those gaps and the extra stream costs 5 % of the pipelined rate)
-    const int parts = (ws->lone && W >= 4 && nb >= ((size_t)1 << 18)) ? 2 : 1;
+    const int parts = (int)plan.parts;
     if (parts == 2) {
         if (!ws->aux_stream) PORLA_HIP(hipStreamCreateWithFlags(&ws->aux_stream, hipStreamNonBlocking));
         if (!ws->fork_ev) PORLA_HIP(hipEventCreateWithFlags(&ws->fork_ev, hipEventDisableTiming));
@@ -420,81 +407,8 @@ static int msm_tree_launch(Workspace* ws, const XYZZ<typename C::Fp>* buckets, i
         PORLA_HIP(hipEventRecord(ws->fork_ev, stream));
         PORLA_HIP(hipStreamWaitEvent(ws->aux_stream, ws->fork_ev, 0));
     }
-    size_t s_off = 0, m_off = 0, mt_off = 0;
-    for (int part = 0, w0 = 0; part < parts; part++) {
-        const int Wp = parts == 1 ? W : (part == 0 ? W / 2 : W - W / 2);
-        hipStream_t st = part == 0 ? stream : ws->aux_stream;
-        const size_t nbp = (size_t)Wp * B;
-        const XYZZ<M>* bk = buckets + (size_t)w0 * B;
-        // S level l at s_base + (nbp - (nbp >> l)) (nbp/2 + ... + nbp/2^l entries before it); M slots of level l in half l & 1
-        XYZZ<M>* s_base = (XYZZ<M>*)ws->tree_s.p + s_off;
-        XYZZ<M>* m_half[2] = {(XYZZ<M>*)ws->tree_m.p + m_off, (XYZZ<M>*)ws->tree_m.p + m_off + nbp / 4 + 1};
-        XYZZ<M>* mt_base = (XYZZ<M>*)ws->tree_mt.p + mt_off;
-        auto s_level = [&](uint32_t l) { return s_base + (nbp - (nbp >> l)); };
-        const bool quad = C::F30_LAZY && tree_quad();
-        const uint32_t l0 = tree_tail_start(B, nlev, quad);
-        {
-            ProfScope ps("tree_levels", st);
-            uint32_t l_first = 0;
-            // levels 0 and 1 as one launch (k_tree_front2) where both are full-width levels and another MSM is in flight: the chip
-            // time the tree takes from that MSM's accumulation is what counts there, not the tree's depth
-            if (!ws->lone && l0 >= 2 && (nbp & 3) == 0 && nbp / 2 > (size_t)TREE_QUAD_MAX_TASKS) {
-                TreeLevelArgs<M> a;
-                a.s_prev = bk; a.s_prev2 = bk; a.m_prev = m_half[0];
-                a.s_out = s_level(0);
-                a.m_out = m_half[1];                          // M^1, slot 0
-                a.fin = nullptr;
-                a.n = (uint32_t)(nbp >> 2);
-                a.m_prev_stride = 0; a.m_out_stride = a.n;
-                a.l = 1; a.nlev = nlev; a.last = 0;
-                hipLaunchKernelGGL((k_tree_front2<C>), dim3((a.n + 255) / 256), dim3(256), 0, st, a, s_level(1));
-                l_first = 2;
-            }
-            for (uint32_t l = l_first; l < l0; l++) {
-                TreeLevelArgs<M> a;
-                a.s_prev = l ? s_level(l - 1) : bk;
-                a.s_prev2 = l >= 2 ? s_level(l - 2) : bk;
-                a.m_prev = m_half[(l + 1) & 1];
-                a.s_out = s_level(l);
-                a.m_out = m_half[l & 1];
-                a.fin = nullptr;   // only the tail holds the last level
-                a.n = (uint32_t)(nbp >> (l + 1));
-                a.m_prev_stride = 2 * a.n; a.m_out_stride = a.n;
-                a.l = l; a.nlev = nlev; a.last = 0;
-                const size_t tasks = (size_t)(l + 1) * a.n;
-                if constexpr (C::F30_LAZY) {
-                    // a caller that waits for this MSM alone has idle lanes to spend on latency: more levels on four lanes per
-                    // addition; with another MSM in flight the extra lane work would cost throughput
-                    if (quad && tasks <= (ws->lone ? (size_t)TREE_QUAD_MAX_TASKS_LONE : (size_t)TREE_QUAD_MAX_TASKS)) {
-                        hipLaunchKernelGGL((k_tree_level_quad<C>), dim3((unsigned)((4 * tasks + 255) / 256)), dim3(256), 0, st, a);
-                        continue;
-                    }
-                }
-                hipLaunchKernelGGL((k_tree_level<C>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, st, a);
-            }
-        }
-        {
-            ProfScope ps("tree_tail", st);
-            TreeTailArgs<M> t;
-            t.buckets = bk;
-            for (uint32_t l = 0; l < 24; l++) t.s_lev[l] = l < nlev ? s_level(l) : nullptr;
-            t.m_global = m_half[(l0 + 1) & 1];
-            t.per_window = B / 4 + 1;
-            t.m_tail[0] = mt_base; t.m_tail[1] = mt_base + (size_t)Wp * t.per_window + 1;
-            t.fin = (XYZZ<M>*)h_windows_dev + (size_t)w0 * c;
-            t.nb = (uint32_t)nbp; t.B = B; t.l0 = l0; t.nlev = nlev;
-            uint32_t need = (l0 + 2) * (B >> (l0 + 1)) * (quad ? 4u : 1u);
-            uint32_t threads = (need + 63) / 64 * 64;
-            if (threads > tree_tail_threads()) threads = tree_tail_threads();
-            if (threads < 64) threads = 64;
-            hipLaunchKernelGGL((k_tree_tail<C, true>), dim3(Wp), dim3(threads), 0, st, t);
-        }
-        // no copy packet: the last level stores its W * c results straight into the pinned host buffer (a D2H hipMemcpyAsync
-        // was seen to block the launching thread for milliseconds while another MSM is in flight)
-        PORLA_HIP(hipGetLastError());
-        s_off += nbp + 1; m_off += 2 * (nbp / 4) + 2; mt_off += 2 * (size_t)Wp * (B / 4 + 1) + 2;
-        w0 += Wp;
-    }
+    PORLA_HIP((tree_enqueue<C, ProfScope>(plan, buckets, (XYZZ<M>*)ws->tree_s.p, (XYZZ<M>*)ws->tree_m.p, (XYZZ<M>*)ws->tree_mt.p,
+                                          (XYZZ<M>*)h_windows_dev, stream, ws->aux_stream)));
     if (parts == 2) {
         PORLA_HIP(hipEventRecord(ws->join_ev, ws->aux_stream));
         PORLA_HIP(hipStreamWaitEvent(stream, ws->join_ev, 0));
