@@ -849,6 +849,51 @@ int porla_kzg_server_rebuild_aligned_batch_device(const porla_server_rebuild_req
 int porla_ipa_server_rebuild_aligned_batch_device(porla_fixed_base *generators_fb, const porla_server_rebuild_req *reqs, size_t k,
                                                   size_t n_total, void *hip_stream);
 
+/* ---- the ICC decode: the coded rows of a level back to its blocks, for K independent levels in ONE asynchronous call ----
+ * The retrieval step of the protocol, which the reference never wrote in C++ (its icc/ toy demonstrates it): the inverse of the data
+ * network.  Output row i is input i of the network whose output is d_rows -- the inverse of porla_icc_encode_device with part = 0 and
+ * equally of the chain of porla_icc_mix_device calls that built a level: the X half of level l decodes to its 2^l blocks in write
+ * order, oldest first.  Request a is one level:
+ *   d_rows         n_rows x n_cols symbols of the form's width, row-major
+ *   d_out          n_rows x n_cols x 32 bytes little-endian
+ *   d_write_steps  n_rows values, or NULL (residue forms only): output position i is multiplied by wt_i^-1 =
+ *                  w^(N - reverse_bits(step_i % N, log2 N)), N = n_total -- a Y half, whose rows are (chunk * wt_i) mod p_icc, gives
+ *                  chunk mod p_icc
+ *   d_bad          one counter, or NULL (EXACT only; the call zeroes it)
+ * form:
+ *   PORLA_ICC_DECODE_EXACT      64-byte rows < LCM -> the 256-bit chunks, both residues joined.  A symbol whose joined value is >= 2^256
+ *                               cannot be a chunk (an altered row decodes to such values in its whole column): it is written as its
+ *                               residue mod p_icc and counted in *d_bad.
+ *   PORLA_ICC_DECODE_RESIDUE64  64-byte rows < LCM -> chunk mod p_icc, canonical; only the p_icc plane runs
+ *   PORLA_ICC_DECODE_RESIDUE32  32-byte rows < p_icc (the aligned store, d_rows32) -> chunk mod p_icc
+ * n_rows: a power of two, 2 .. 2^16, <= n_total.  n_total: a power of two <= 2^16 that fixes w for the unscale (and which resident
+ * twiddle table is used: the twiddles of the network itself do not depend on it).
+ * Contract: that of the other batches -- asynchronous on hip_stream, no host wait, no side stream; the launch sequence depends on
+ * n_rows, not on k (the upload, the counters' reset, ceil(log2 n_rows / 9) passes with the request in blockIdx.y); the twiddle tables
+ * are the encode's, plus one table of inverses mod q per (n_total, curve), used under the ICC workspace's lock and fence.
+ * PORLA_ERR_ARG (with a message, before the device is touched): NULL reqs with k > 0; NULL d_rows or d_out; d_rows or d_out not
+ * 16-byte aligned, d_write_steps not 8-byte aligned, d_bad not 4-byte aligned; a bad n_rows, n_total, n_cols (0 or > 65535), curve or
+ * form; d_write_steps or d_bad given with a form that does not take it; an output overlapping any request's input or output; more than
+ * 65535 requests; a byte size that overflows.  k = 0 returns 0; valid arguments without a device: PORLA_ERR_NO_DEVICE.
+ * porla_icc_decode_host is one level from host memory (upload, the same kernels, download; it waits).
+ * tools/bench_icc_decode.py times the EXACT form beside porla_icc_encode_device on the same rows in the same run, every output byte
+ * compared with the encode's input (profiles/r17_a_icc_decode.jsonl, DESIGN s4: one level of 2^15 x 128 in 0.95 ms, 1.41x the encode;
+ * 8 levels in 6.4 ms, 1.32x; 64 levels of 2^10 in 1.29 ms, 0.40x the 64 encode calls). */
+#define PORLA_ICC_DECODE_EXACT      0
+#define PORLA_ICC_DECODE_RESIDUE64  1
+#define PORLA_ICC_DECODE_RESIDUE32  2
+#define PORLA_ICC_DECODE_REQ_BYTES 32   /* sizeof(porla_icc_decode_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    const void *d_rows;
+    void *d_out;
+    const unsigned long long *d_write_steps;
+    unsigned int *d_bad;
+} porla_icc_decode_req;
+int porla_icc_decode_batch_device(const porla_icc_decode_req *reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve,
+                                  int form, void *hip_stream);
+int porla_icc_decode_host(const uint8_t *rows, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form,
+                          const unsigned long long *write_steps, uint8_t *out, unsigned int *bad);
+
 /* ---- audit row combine (Server::audit, Server.hpp:790-828) + the scalar part of align_MAC on the result (:531-541) ----
  * B_j = sum_i coeff_i * row_i[j] (exact integer), then aligned_j = B_j mod p_icc, c_j = (aligned_j - B_j) mod q.
  * The challenged rows are addressed inside row stores resident in HBM:

@@ -5,6 +5,7 @@
 #include "icc.hip.h"
 #include "icc30.hip.h"
 #include "icc30_split.hip.h"
+#include "icc_decode.hip.h"
 #include "icc_host.hpp"
 
 #include <cstdlib>
@@ -17,10 +18,12 @@ namespace porla {
 
 struct IccWs {
     int device = -1;
-    Buf work, tw, tw30, tw30p, tw30q, wpow, in, xo, al, sc, park_y;
+    Buf work, tw, tw30, tw30p, tw30q, tw30qi, wpow, in, xo, al, sc, park_y;
     uint32_t tw_n = 0, tw30_n = 0;   // tw30: the same table in the reduced-radix form of icc30.hip.h (80-byte slots)
     uint32_t tw30s_n = 0;            // tw30p / tw30q: the plane tables of icc30_split.hip.h (40-byte slots)
     int tw30_curve = -1, tw30s_curve = -1;
+    uint32_t tw30qi_n = 0;           // tw30qi: the q plane's INVERSE twiddles of icc_decode.hip.h (40-byte slots)
+    int tw30qi_curve = -1;
     int tw_curve = -1;
     UseFence fence;   // work / twiddle buffers are shared between calls that may come on different streams
     std::mutex mu;    // one encode at a time per device (the column-range splitter runs one host thread per device)
@@ -47,6 +50,7 @@ static int ensure_twiddles(IccWs* ws, int curve, size_t n, hipStream_t stream) {
     ws->tw_curve = curve;
     ws->tw30_n = 0;
     ws->tw30s_n = 0;
+    ws->tw30qi_n = 0;
     return PORLA_OK;
 }
 
@@ -242,6 +246,32 @@ int icc_encode_tables_acquire(int curve, size_t n_total, hipStream_t stream, con
     if (rc) { (void)icc_mix_tables_release(stream); return rc; }
     *twp = (const uint32_t*)ws->tw30p.p;
     *twq = (const uint32_t*)ws->tw30q.p;
+    return PORLA_OK;
+}
+// For icc_decode.hip: icc_encode_tables_acquire and -- want_q -- the inverse twiddles of the q plane (icc_decode.hip.h) beside them,
+// one inversion mod q per entry, rebuilt only when (n_total, curve) changes; twq is not handed out: the decode multiplies by inverses.
+template <class Q>
+static int ensure_qinv_twiddles(IccWs* ws, int curve, size_t n, hipStream_t stream) {
+    if (ws->tw30qi_n == n && ws->tw30qi_curve == curve) return PORLA_OK;
+    int rc;
+    if ((rc = ws->tw30qi.ensure(n * ICC30_PSLOT_WORDS * 4))) return rc;
+    hipLaunchKernelGGL((k_icd_twiddles_qinv<Q>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const IccElem<Q>*)ws->tw.p,
+                       (uint32_t)n, (uint32_t*)ws->tw30qi.p);
+    ws->tw30qi_n = (uint32_t)n;
+    ws->tw30qi_curve = curve;
+    return PORLA_OK;
+}
+int icc_decode_tables_acquire(int curve, size_t n_total, bool want_q, hipStream_t stream, const uint32_t** twp, const uint32_t** twqi) {
+    const uint32_t* twq = nullptr;
+    int rc = icc_encode_tables_acquire(curve, n_total, stream, twp, &twq);
+    if (rc) return rc;
+    *twqi = nullptr;
+    if (!want_q) return PORLA_OK;
+    IccWs* ws = nullptr;
+    rc = g_icc_ws.get(&ws);
+    if (!rc) rc = curve == 0 ? ensure_qinv_twiddles<IccBn254Fr>(ws, 0, n_total, stream) : ensure_qinv_twiddles<IccSecp256k1Fn>(ws, 1, n_total, stream);
+    if (rc) { (void)icc_mix_tables_release(stream); return rc; }
+    *twqi = (const uint32_t*)ws->tw30qi.p;
     return PORLA_OK;
 }
 int icc_mix_tables_release(hipStream_t stream) {

@@ -1,0 +1,230 @@
+// The batched ICC decode (include/porla_gpu.h: porla_icc_decode_batch_device / porla_icc_decode_host): the coded rows of K levels
+// back to their blocks in ONE asynchronous call.  Kernels and arithmetic: icc_decode.hip.h.  Every step is on the caller's stream
+// and the launch sequence depends on n_rows, never on K:
+//
+//   upload          one copy of the requests (the kernels read them as they are: IcdDesc)
+//   k_icd_clear     EXACT: the counters of the requests that have one
+//   k_icd_exact /   ceil(log2 n_rows / 9) passes over 1 024-symbol tiles, the encode's plan in reverse order, grid.y = request, under
+//   k_icd_residue   the data side's table lease; the first reads the rows, the last writes the blocks; between them the residue
+//                   planes travel through this workspace
+#include "batch_host.hpp"
+#include "icc_decode.hip.h"
+#include "icc_host.hpp"
+
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+#include <string>
+
+namespace porla {
+
+struct IccDecodeWs {
+    std::mutex mu;
+    int device = -1;
+    Buf list, planes;
+    Buf io_rows, io_out, io_steps, io_bad;     // the host form's device images
+    PinnedList h_list;
+    UseFence fence;
+};
+static PerDevice<IccDecodeWs> g_icd_ws;
+
+static const char* const ICD_WHO = "porla_icc_decode_batch_device";
+
+static inline size_t icd_symbol_bytes(int form) { return form == PORLA_ICC_DECODE_RESIDUE32 ? 32 : 64; }
+
+// the refusals that concern the shape of the call
+static int icd_check_shape(const char* who, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form) {
+    auto bad = [&](const std::string& what) { return bad_arg(who, what); };
+    if (int rc = check_n_total(who, n_total, 16)) return rc;
+    if (n_rows < 2 || (n_rows & (n_rows - 1)) != 0 || n_rows > n_total) return bad("n_rows must be a power of two, 2 .. n_total");
+    if (n_cols == 0) return bad("n_cols is 0");
+    if (curve != 0 && curve != 1) return bad("curve must be 0 (BN254 / KZG) or 1 (secp256k1 / IPA)");
+    if (form != PORLA_ICC_DECODE_EXACT && form != PORLA_ICC_DECODE_RESIDUE64 && form != PORLA_ICC_DECODE_RESIDUE32)
+        return bad("form must be PORLA_ICC_DECODE_EXACT, _RESIDUE64 or _RESIDUE32");
+    size_t t;
+    if (!mul_ok(n_rows, n_cols, &t) || !mul_ok(t, 64, &t) || !mul_ok(t, 2, &t))
+        return bad("a byte size overflows: n_rows * n_cols symbols do not fit a buffer");
+    if (n_cols > 0xffffu) return bad("n_cols above 65535");
+    return PORLA_OK;
+}
+
+// the checks made before the device is touched
+static int icd_check(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form) {
+    auto bad = [&](const std::string& what) { return bad_arg(ICD_WHO, what); };
+    if (k && !reqs) return bad("reqs is NULL");
+    if (int rc = icd_check_shape(ICD_WHO, n_rows, n_cols, n_total, curve, form)) return rc;
+    if (k > 0xffffu) return bad("more than 65535 requests in one call");
+    size_t t;
+    if (k && (!mul_ok(n_rows * n_cols * 2 * ICC30_PLANE_WORDS * 4, k, &t)))
+        return bad("a byte size overflows: the residue planes of k requests do not fit a buffer");
+    const size_t symbols = n_rows * n_cols;
+    const size_t in_b = symbols * icd_symbol_bytes(form), out_b = symbols * 32;
+    struct Range { uintptr_t lo, hi; bool out; };
+    std::vector<Range> ranges;
+    ranges.reserve(4 * k);
+    for (size_t a = 0; a < k; a++) {
+        const porla_icc_decode_req& R = reqs[a];
+        const std::string at = "request " + std::to_string(a) + ": ";
+        if (!R.d_rows || !R.d_out) return bad(at + "a NULL d_rows or d_out");
+        if (((uintptr_t)R.d_rows | (uintptr_t)R.d_out) & 15u) return bad(at + "d_rows or d_out is not 16-byte aligned");
+        if ((uintptr_t)R.d_write_steps & 7u) return bad(at + "d_write_steps is not 8-byte aligned");
+        if ((uintptr_t)R.d_bad & 3u) return bad(at + "d_bad is not 4-byte aligned");
+        if (R.d_write_steps && form == PORLA_ICC_DECODE_EXACT) return bad(at + "d_write_steps with PORLA_ICC_DECODE_EXACT: the unscale is the residue forms'");
+        if (R.d_bad && form != PORLA_ICC_DECODE_EXACT) return bad(at + "d_bad with a residue form: only PORLA_ICC_DECODE_EXACT counts");
+        if ((uintptr_t)R.d_rows + in_b < (uintptr_t)R.d_rows || (uintptr_t)R.d_out + out_b < (uintptr_t)R.d_out)
+            return bad(at + "a byte size overflows: a buffer wraps around the address space");
+        ranges.push_back(Range{(uintptr_t)R.d_rows, (uintptr_t)R.d_rows + in_b, false});
+        ranges.push_back(Range{(uintptr_t)R.d_out, (uintptr_t)R.d_out + out_b, true});
+        if (R.d_write_steps) ranges.push_back(Range{(uintptr_t)R.d_write_steps, (uintptr_t)R.d_write_steps + n_rows * 8, false});
+        if (R.d_bad) ranges.push_back(Range{(uintptr_t)R.d_bad, (uintptr_t)R.d_bad + 4, true});
+    }
+    // an output may overlap nothing, inputs may be shared: sorted by start, an output must begin at or after the end of everything
+    // before it and an input at or after the end of every output before it
+    std::sort(ranges.begin(), ranges.end(), [](const Range& x, const Range& y) { return x.lo < y.lo; });
+    uintptr_t end_any = 0, end_out = 0;
+    for (const Range& r : ranges) {
+        if (r.lo < (r.out ? end_any : end_out))
+            return bad("an output (d_out or d_bad) overlaps an input or output of this call: outputs must be disjoint from everything");
+        end_any = std::max(end_any, r.hi);
+        if (r.out) end_out = std::max(end_out, r.hi);
+    }
+    return PORLA_OK;
+}
+
+// 2^e mod the modulus of M as a plain integer (e >= 0): e doublings of 1
+template <class M>
+static void icd_pow2(int e, uint32_t out[8]) {
+    Fe<M> x = fe_zero<M>();
+    x.v[0] = 1;
+    for (int i = 0; i < e; i++) x = fe_add<M>(x, x);
+    for (int k = 0; k < 8; k++) out[k] = x.v[k];
+}
+
+// ws->mu held, ws->fence entered; arguments checked
+template <class Q>
+static int icd_enqueue(IccDecodeWs* ws, int curve, const porla_icc_decode_req* reqs, size_t k, size_t n, size_t ncols, size_t n_total, int form,
+                       hipStream_t stream) {
+    int rc;
+    const int logn = ilog2u(n);
+    const bool exact = form == PORLA_ICC_DECODE_EXACT;
+    IccPass plan[ICC_MAX_PASSES];
+    const int passes = icc_pass_plan(logn, ncols, plan);
+    const size_t plane_words = n * ncols * ICC30_PLANE_WORDS;
+    const size_t desc_b = k * sizeof(IcdDesc);
+    static_assert(sizeof(IcdDesc) == sizeof(porla_icc_decode_req), "the requests are uploaded as they are");
+    if ((rc = ws->h_list.stage(desc_b))) return rc;
+    if ((rc = ws->list.ensure(desc_b))) return rc;
+    if (passes > 1 && (rc = ws->planes.ensure(k * (exact ? 2 : 1) * plane_words * 4))) return rc;
+    memcpy(ws->h_list.h, reqs, desc_b);
+    if ((rc = ws->h_list.send(ws->list.p, desc_b, stream))) return rc;
+    const IcdDesc* d_desc = (const IcdDesc*)ws->list.p;
+    IcdScale sc;
+    icd_pow2<IccFp>(270 - logn, sc.p);
+    icd_pow2<Q>(270 - logn, sc.q);
+    if (exact) {
+        hipLaunchKernelGGL(k_icd_clear, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, stream, d_desc, (uint32_t)k);
+        PORLA_HIP(hipGetLastError());
+    }
+    const uint32_t *twp = nullptr, *twqi = nullptr;
+    if ((rc = icc_decode_tables_acquire(curve, n_total, exact, stream, &twp, &twqi))) return rc;
+    uint32_t* planes = (uint32_t*)ws->planes.p;
+    for (int pz = passes - 1; pz >= 0; pz--) {
+        const int s = plan[pz].s, ns = plan[pz].ns, cc_log = plan[pz].cc_log;
+        const dim3 grid((unsigned)(plan[pz].col_tiles * (n >> ns)), (unsigned)k);
+        const dim3 block(ICC30_SPLIT_THREADS);
+        const bool first = pz == passes - 1, last = pz == 0;
+        ProfScope ps("icc_decode", stream);
+#define PORLA_ICD_EXACT(F, L)                                                                                                       \
+    hipLaunchKernelGGL((k_icd_exact<Q, F, L>), grid, block, 0, stream, d_desc, planes, plane_words, twp, twqi, (uint32_t)n_total,   \
+                       (uint32_t)n, (uint32_t)ncols, s, ns, cc_log, sc)
+#define PORLA_ICD_RESIDUE(S, L)                                                                                                     \
+    hipLaunchKernelGGL((k_icd_residue<S, L>), grid, block, 0, stream, d_desc, planes, plane_words, twp, (uint32_t)n_total,          \
+                       ilog2u(n_total), (uint32_t)n, (uint32_t)ncols, s, ns, cc_log, sc)
+        if (exact) {
+            if (first && last) PORLA_ICD_EXACT(true, true);
+            else if (first) PORLA_ICD_EXACT(true, false);
+            else if (last) PORLA_ICD_EXACT(false, true);
+            else PORLA_ICD_EXACT(false, false);
+        } else if (!first) {
+            if (last) PORLA_ICD_RESIDUE(ICD_WORK, true);
+            else PORLA_ICD_RESIDUE(ICD_WORK, false);
+        } else if (form == PORLA_ICC_DECODE_RESIDUE64) {
+            if (last) PORLA_ICD_RESIDUE(ICD_ROWS64, true);
+            else PORLA_ICD_RESIDUE(ICD_ROWS64, false);
+        } else {
+            if (last) PORLA_ICD_RESIDUE(ICD_ROWS32, true);
+            else PORLA_ICD_RESIDUE(ICD_ROWS32, false);
+        }
+#undef PORLA_ICD_EXACT
+#undef PORLA_ICD_RESIDUE
+    }
+    if (hipGetLastError() != hipSuccess) { set_last_error("porla: ICC decode batch: a launch failed"); rc = PORLA_ERR_HIP; }
+    const int r1 = icc_mix_tables_release(stream);
+    return rc ? rc : r1;
+}
+
+static int icd_run(IccDecodeWs* ws, const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form,
+                   hipStream_t stream) {
+    return curve == 0 ? icd_enqueue<IccBn254Fr>(ws, 0, reqs, k, n_rows, n_cols, n_total, form, stream)
+                      : icd_enqueue<IccSecp256k1Fn>(ws, 1, reqs, k, n_rows, n_cols, n_total, form, stream);
+}
+
+}  // namespace porla
+
+using namespace porla;
+
+static_assert(sizeof(porla_icc_decode_req) == PORLA_ICC_DECODE_REQ_BYTES, "porla_icc_decode_req size");
+static_assert(offsetof(porla_icc_decode_req, d_rows) == 0 && offsetof(porla_icc_decode_req, d_out) == 8 &&
+              offsetof(porla_icc_decode_req, d_write_steps) == 16 && offsetof(porla_icc_decode_req, d_bad) == 24,
+              "porla_icc_decode_req offsets (include/porla_gpu.h)");
+static_assert(offsetof(IcdDesc, rows) == 0 && offsetof(IcdDesc, out) == 8 && offsetof(IcdDesc, steps) == 16 && offsetof(IcdDesc, bad) == 24,
+              "IcdDesc is porla_icc_decode_req field for field");
+
+extern "C" int porla_icc_decode_batch_device(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total,
+                                             int curve, int form, void* hip_stream) {
+    int rc = icd_check(reqs, k, n_rows, n_cols, n_total, curve, form);
+    if (rc) return rc;
+    if (k == 0) return PORLA_OK;
+    if ((rc = ensure_device())) return rc;
+    IccDecodeWs* ws = nullptr;
+    if ((rc = g_icd_ws.get(&ws))) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    return FencedCall(ws, stream).run([&] { return icd_run(ws, reqs, k, n_rows, n_cols, n_total, curve, form, stream); });
+}
+
+// one level from host memory: upload, the batch of one request on the engine's stream, download
+extern "C" int porla_icc_decode_host(const uint8_t* rows, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form,
+                                     const unsigned long long* write_steps, uint8_t* out, unsigned int* bad) {
+    static const char* const who = "porla_icc_decode_host";
+    if (!rows || !out) return bad_arg(who, "rows or out is NULL");
+    int rc = icd_check_shape(who, n_rows, n_cols, n_total, curve, form);
+    if (rc) return rc;
+    if (write_steps && form == PORLA_ICC_DECODE_EXACT) return bad_arg(who, "write_steps with PORLA_ICC_DECODE_EXACT: the unscale is the residue forms'");
+    if (bad && form != PORLA_ICC_DECODE_EXACT) return bad_arg(who, "bad with a residue form: only PORLA_ICC_DECODE_EXACT counts");
+    if ((rc = ensure_device())) return rc;
+    IccDecodeWs* ws = nullptr;
+    if ((rc = g_icd_ws.get(&ws))) return rc;
+    const size_t symbols = n_rows * n_cols, in_b = symbols * icd_symbol_bytes(form), out_b = symbols * 32;
+    hipStream_t s = engine_stream();
+    FencedCall call(ws, s);
+    rc = call.run([&] {
+        int r;
+        if ((r = ws->io_rows.ensure(in_b)) || (r = ws->io_out.ensure(out_b))) return r;
+        if (write_steps && (r = ws->io_steps.ensure(n_rows * 8))) return r;
+        if (bad && (r = ws->io_bad.ensure(4))) return r;
+        PORLA_HIP(hipMemcpyAsync(ws->io_rows.p, rows, in_b, hipMemcpyHostToDevice, s));
+        if (write_steps) PORLA_HIP(hipMemcpyAsync(ws->io_steps.p, write_steps, n_rows * 8, hipMemcpyHostToDevice, s));
+        porla_icc_decode_req R;
+        R.d_rows = ws->io_rows.p;
+        R.d_out = ws->io_out.p;
+        R.d_write_steps = write_steps ? (const unsigned long long*)ws->io_steps.p : nullptr;
+        R.d_bad = bad ? (unsigned int*)ws->io_bad.p : nullptr;
+        if ((r = icd_run(ws, &R, 1, n_rows, n_cols, n_total, curve, form, s))) return r;
+        PORLA_HIP(hipMemcpyAsync(out, ws->io_out.p, out_b, hipMemcpyDeviceToHost, s));
+        if (bad) PORLA_HIP(hipMemcpyAsync(bad, ws->io_bad.p, 4, hipMemcpyDeviceToHost, s));
+        return (int)PORLA_OK;
+    });
+    if (rc) return rc;
+    PORLA_HIP(hipStreamSynchronize(s));        // (the lock is held to here: the images are this call's until the copies are done)
+    return PORLA_OK;
+}

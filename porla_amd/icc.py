@@ -4,7 +4,7 @@ C ABI (include/porla_gpu.h: porla_icc_encode_*).  Rows are in the reference's ow
 little-endian chunks in (utils.h:353-364), 64-byte little-endian values mod LCM out (utils.h:473-517)."""
 import ctypes
 
-from .loader import ServerRebuildReq, UpdateReq, lib
+from .loader import IccDecodeReq, ServerRebuildReq, UpdateReq, lib
 
 CURVE = {"bn254": 0, "secp256k1": 1}
 NUM_CHUNKS = 128  # config.hpp:22
@@ -228,3 +228,42 @@ def kzg_server_rebuild_aligned_batch_device(reqs, n_total, stream=0):
     server_rebuild_requests takes them.  The IPA twin is FixedBase.ipa_server_rebuild_aligned_batch_device."""
     arr = server_rebuild_requests(reqs)
     _check(lib.porla_kzg_server_rebuild_aligned_batch_device(arr, len(reqs), n_total, ctypes.c_void_p(stream)))
+
+
+# ---- the ICC decode: the rows of K levels back to their blocks in one asynchronous call (include/porla_gpu.h:
+# porla_icc_decode_batch_device) ----
+DECODE_FORM = {"exact": 0, "residue64": 1, "residue32": 2}
+
+
+def decode_requests(reqs):
+    """a ctypes array of porla_icc_decode_req from per-level tuples (d_rows, d_out, d_write_steps or 0, d_bad or 0): device addresses
+    as integers"""
+    arr = (IccDecodeReq * max(len(reqs), 1))()
+    for i, r in enumerate(reqs):
+        if len(r) != 4:
+            raise ValueError("decode_batch_device: request %d has %d fields, want 4" % (i, len(r)))
+        arr[i] = IccDecodeReq(*[(x or None) for x in r])
+    return arr
+
+
+def decode_batch_device(reqs, n_rows, n_cols, n_total, curve, form, stream=0):
+    """the inverse of the data network on len(reqs) levels of n_rows rows in ONE asynchronous call on `stream`: output row i is input i
+    of the network whose output is d_rows.  form: "exact" (64-byte rows -> the 256-bit chunks; a symbol that cannot be a chunk is
+    counted in d_bad), "residue64" / "residue32" (64- / 32-byte rows -> chunk mod p_icc; with d_write_steps position i is unscaled by
+    wt_i^-1).  `reqs`: tuples as decode_requests takes them; curve: "bn254" or "secp256k1"."""
+    arr = decode_requests(reqs)
+    _check(lib.porla_icc_decode_batch_device(arr, len(reqs), n_rows, n_cols, n_total, CURVE[curve], DECODE_FORM[form],
+                                             ctypes.c_void_p(stream)))
+
+
+def decode_host(rows, n_rows, n_cols, n_total, curve="bn254", form="exact", write_steps=None, want_bad=None):
+    """one level from host memory.  Returns (out, bad): n_rows * n_cols * 32 bytes, and the count of symbols that cannot be chunks
+    ("exact"; None for the residue forms unless want_bad is forced, which the library refuses)."""
+    out = ctypes.create_string_buffer(32 * n_rows * n_cols)
+    if want_bad is None:
+        want_bad = form == "exact"
+    bad = ctypes.c_uint(0xffffffff) if want_bad else None
+    steps = (ctypes.c_ulonglong * n_rows)(*write_steps) if write_steps is not None else None
+    _check(lib.porla_icc_decode_host(bytes(rows), n_rows, n_cols, n_total, CURVE[curve], DECODE_FORM[form], steps,
+                                     ctypes.cast(out, ctypes.c_void_p), ctypes.byref(bad) if want_bad else None))
+    return out.raw, (bad.value if want_bad else None)

@@ -88,6 +88,15 @@ PORLA_SERVER_REBUILD_REQ_BYTES = 104
 assert ctypes.sizeof(ServerRebuildReq) == PORLA_SERVER_REBUILD_REQ_BYTES
 
 
+class IccDecodeReq(ctypes.Structure):
+    """porla_icc_decode_req, include/porla_gpu.h: one level of porla_icc_decode_batch_device (PORLA_ICC_DECODE_REQ_BYTES = 32)."""
+    _fields_ = [("d_rows", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("d_write_steps", ctypes.c_void_p), ("d_bad", ctypes.c_void_p)]
+
+
+PORLA_ICC_DECODE_REQ_BYTES = 32
+assert ctypes.sizeof(IccDecodeReq) == PORLA_ICC_DECODE_REQ_BYTES
+
+
 def load():
     """Load the engine.  When torch is importable it is imported FIRST so that the HIP runtime the process
     ends up with is the one torch ships (both have soname libamdhip64.so.7; two runtimes in one process
@@ -210,6 +219,11 @@ def _declare(L):
     L.porla_kzg_server_rebuild_aligned_batch_device.restype = ctypes.c_int
     L.porla_ipa_server_rebuild_aligned_batch_device.argtypes = [vp, ctypes.POINTER(ServerRebuildReq), sz, sz, vp]
     L.porla_ipa_server_rebuild_aligned_batch_device.restype = ctypes.c_int
+    L.porla_icc_decode_batch_device.argtypes = [ctypes.POINTER(IccDecodeReq), sz, sz, sz, sz, ctypes.c_int, ctypes.c_int, vp]
+    L.porla_icc_decode_batch_device.restype = ctypes.c_int
+    L.porla_icc_decode_host.argtypes = [u8p, sz, sz, sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), vp,
+                                        ctypes.POINTER(ctypes.c_uint)]
+    L.porla_icc_decode_host.restype = ctypes.c_int
     L.porla_ipa_prove_batch_device.argtypes = [vp, vp, vp, sz, vp, vp]; L.porla_ipa_prove_batch_device.restype = ctypes.c_int
     L.porla_ipa_verify_batch_device.argtypes = [vp, ctypes.POINTER(IpaVerifyReq), sz, vp, vp, vp]
     L.porla_ipa_verify_batch_device.restype = ctypes.c_int

@@ -224,6 +224,42 @@ def check_icc_chain(stages=ICC_STAGES):
     return ok
 
 
+ICC_DECODE_STAGES = 16
+
+
+def check_icc_decode_chain(stages=ICC_DECODE_STAGES):
+    """the symbol bound chain of icc_decode.hip.h closes for the three moduli: EVERY symbol of the stream is below 2 p.  In the decode
+    a + b adds two unreduced symbols and row 0 of a tile is never multiplied, so the sum is reduced at every butterfly:
+      load      64-byte symbol: hi C526 + lo < (p + 2^242) + 2^256, icc30_reduce_top -> [0, 2 p); 32-byte row: < 2^256 <= 2 p_icc
+      butterfly a, b < 2 p:  a + b < 4 p -> icc30_reduce_top -> [0, 2 p);  d = a - b + 3 p < 5 p (icc30_sub<3>: the table takes b
+                up to 2 p - 1, check_sub_tables);  d * inverse twiddle (a product's result, < T <= 2^257 as an operand) < T <= 2 p
+      finish    products with n^-1 (< p) and wt^-1 (a table twiddle): < T; icc30_reduce_top on any v < 2^263, then icc30_canonical
+    The walk carries the largest symbol through `stages` stages and checks every operand at its consumer.  Bounds are exclusive."""
+    ok = True
+    for name, p in ICC_MODULI.items():
+        T = icc_product_top(p)                       # a product's result over the whole operand domain (a < 2^263, w < 2^257)
+        good = T <= 2 * p and T <= 2**ICC_W_BITS     # ... is below 2 p, and fits a twiddle operand (the inverse table, the finish)
+        good = good and icc_sub_operands(p)[3] == 2 * p - 1
+        load64 = (p + 2**242) + 2**256               # hi * (2^256 in the 2^270 form) + the raw lower half
+        good = good and load64 <= 2**ICC_A_BITS and icc_reduce_top_ok(p)
+        sym = 2 * p                                  # after the load step's short reduction
+        if name == "p_icc":
+            good = good and 2**256 <= 2 * p          # a 32-byte row enters as it is
+        worst_sum = worst_diff = 0
+        for _ in range(stages):
+            s, d = 2 * sym, sym + 3 * p              # a + b;  a - b + 3 p with b >= 0
+            worst_sum, worst_diff = max(worst_sum, s), max(worst_diff, d)
+            good = good and s <= 2**ICC_A_BITS and d <= 2**ICC_A_BITS and sym <= 2 * p
+            sym = max(2 * p, T)                      # the reduced sum, the product
+            good = good and sym <= 2 * p
+        # the inverse table's entry: (v^-1 + k q < 4 q) * C540 / 2^270; the finish's factors
+        good = good and 4 * p <= 2**ICC_A_BITS and p <= 2**ICC_W_BITS
+        print("icc:%-11s decode stream: sums below %.2f p, differences below %.2f p = %.5f x 2^263, symbols below 2 p at each of %d stages  %s"
+              % (name, worst_sum / p, worst_diff / p, worst_diff / 2**ICC_A_BITS, stages, "ok" if good else "BAD"))
+        ok = ok and good
+    return ok
+
+
 if __name__ == "__main__":
     import sys
     ok = all([check(n, p) for n, p in MODULI.items()])
@@ -234,4 +270,5 @@ if __name__ == "__main__":
     ok = check_sub_tables() and ok
     # result bound of the ICC product: a b / 2^270 + p < p + 2^250 for a < 2^263, b < 2^257: limb 8 stays far below 2^30
     ok = check_icc_chain() and ok
+    ok = check_icc_decode_chain() and ok
     sys.exit(0 if ok else 1)
