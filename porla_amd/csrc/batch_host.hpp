@@ -46,6 +46,11 @@ static inline int check_n_total(const char* who, size_t n_total, int max_log) {
     return bad_arg(who, "n_total must be a power of two, 2 .. 2^" + std::to_string(max_log));
 }
 
+// "more than 65535 requests in one call": the request is a launch's grid.y, which stops there
+static inline int check_request_count(const char* who, size_t k) {
+    return k > 0xffffu ? bad_arg(who, "more than 65535 requests in one call") : PORLA_OK;
+}
+
 // Dynamic LDS above 64 KiB: a kernel must be told once per device before its first launch.  One static LdsOnce per group of
 // kernels that are launched together; set() does its work the first time it is called on a device.
 struct LdsKernel { const void* f; size_t bytes; };

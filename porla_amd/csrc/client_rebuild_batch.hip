@@ -13,11 +13,11 @@
 //   k_cr_close               (new - T) mod q and (new - wt T) mod q as the big-endian rows of the h pass
 //   h pass                   K (2 n_total + 1) one-coefficient rows against the one-point table of the hiding base -> affine bytes
 //   k_cr_place               the 2 n_total points to d_complements_out, MAC = block commitment + comp0
+// (the two passes and the KZG build's precheck: client_block_pass.hip.h; wt and the IPA bases: write_batch_host.hpp)
 #include "client_rebuild_batch.hip.h"
-#include "icc_host.hpp"
+#include "write_batch_host.hpp"
 
 #include <cstddef>
-#include <cstring>
 #include <mutex>
 #include <string>
 #include <unordered_set>
@@ -84,11 +84,7 @@ static int cr_enqueue(ClientRebuildWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>*
             CrDesc& D = hd[a];
             D.block = (const uint8_t*)R.d_block; D.prf = (const uint8_t*)R.d_prf;
             D.mac_out = (uint8_t*)R.d_mac_out; D.comp_out = (uint8_t*)R.d_complements_out;
-            uint32_t wt_p[8], wt_q[8];
-            uint8_t be[32];
-            (void)icc_wt_residues(IccCurve<C>::id, n_total, R.write_step, wt_p, wt_q, be);
-            h_load_be(D.wt_sc, be);
-            fe_reduce_plain<Q>(D.wt_sc, 8);                    // the group sees wt mod its order (convert_ZZ_to_scalar / fr.SetBytes)
+            write_wt<C>(n_total, R.write_step, D.wt_sc);
         }
     }
     if ((rc = ws->h_list.send(ws->list.p, desc_b, stream))) return rc;
@@ -117,12 +113,7 @@ static int cr_enqueue(ClientRebuildWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>*
         PORLA_HIP(hipGetLastError());
     }
     // ---- 4. the h pass
-    if constexpr (IccCurve<C>::id == 0) {
-        if ((rc = porla_kzg_complement_batch_device(d_scal, n_rows, d_hpts, stream))) return rc;
-    } else {
-        std::lock_guard<std::mutex> lk(fb_h->mu);
-        if ((rc = fb_h->commit_device(d_scal, n_rows, 1, 32, d_hpts, stream))) return rc;
-    }
+    if ((rc = client_h_pass<C>(fb_h, d_scal, n_rows, d_hpts, stream))) return rc;
     // ---- 5. the outputs
     {
         ProfScope ps("client_rebuild_place", stream);
@@ -139,7 +130,7 @@ static int cr_check(const char* who, const porla_client_rebuild_req* reqs, size_
     auto bad = [&](const std::string& what) { return bad_arg(who, what); };
     if (k && !reqs) return bad("reqs is NULL");
     if (int rc = check_n_total(who, n_total, 30)) return rc;
-    if (k > 0xffffu) return bad("more than 65535 requests in one call");
+    if (int rc = check_request_count(who, k)) return rc;
     std::unordered_set<const void*> seen;
     for (size_t a = 0; a < k; a++) {
         const porla_client_rebuild_req& R = reqs[a];
@@ -168,11 +159,8 @@ extern "C" int porla_kzg_client_rebuild_batch_device(const porla_client_rebuild_
     if (rc) return rc;
     if (k == 0) return PORLA_OK;
     if ((rc = ensure_device())) return rc;
-    // the key and the SRS, before any device work: an empty digest batch makes exactly that check
-    if ((rc = porla_kzg_digest_batch_device(nullptr, 0, nullptr, nullptr))) return rc;
-    const size_t ncols = kzg_n_samples();
-    if (ncols == 0) return kzg_no_srs();
-    if (ncols > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
+    size_t ncols;
+    if ((rc = client_kzg_row_width(&ncols))) return rc;
     ClientRebuildWs* ws = nullptr;
     if ((rc = g_cr_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -187,14 +175,12 @@ extern "C" int porla_ipa_client_rebuild_batch_device(porla_fixed_base* alpha_gen
     if (k == 0) return PORLA_OK;
     if (!alpha_generators_fb || !h_fb) return bad_arg(who, "a NULL base");
     if ((rc = ensure_device())) return rc;
-    // (a handle exists only where a device does: it is read after ensure_device, and still before any device work)
-    if (alpha_generators_fb->curve != 1 || alpha_generators_fb->secp.n_points < CU_IPA_COLS)
-        return bad_arg(who, "alpha_generators_fb must be a secp256k1 fixed base over at least the 128 generators");
-    if (h_fb->curve != 1 || h_fb->secp.n_points != 1) return bad_arg(who, "h_fb must be a secp256k1 fixed base over exactly one point");
+    if ((rc = ipa_check_generators(who, "alpha_generators_fb", alpha_generators_fb))) return rc;
+    if ((rc = ipa_check_hiding_base(who, "h_fb", h_fb))) return rc;
     ClientRebuildWs* ws = nullptr;
     if ((rc = g_cr_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     return FencedCall(ws, stream).run([&] {
-        return cr_enqueue<Secp256k1G>(ws, &alpha_generators_fb->secp, &h_fb->secp, reqs, k, CU_IPA_COLS, n_total, stream);
+        return cr_enqueue<Secp256k1G>(ws, &alpha_generators_fb->secp, &h_fb->secp, reqs, k, IPA_COLS, n_total, stream);
     });
 }

@@ -16,15 +16,14 @@
 //   for i < Lmax:            k_update_mix_points_* with two families (X, Y) of the requests with level > i
 //   k_cu_close               new complement - mixed complement, to affine
 //
-// Both passes leave affine bytes (k_fb_finish: the table's own conversion), which is what the mix bodies read.
-#include "kzg_state.hpp"
+// Both passes leave affine bytes (k_fb_finish: the table's own conversion), which is what the mix bodies read.  Shared: the passes and
+// the KZG precheck (client_block_pass.hip.h), wt, level plan, IPA bases (write_batch_host.hpp), a step's form (update_batch.hip.h).
 #include "client_update_batch.hip.h"
-#include "icc_host.hpp"
+#include "write_batch_host.hpp"
 #include "../../include/porla_gpu.h"
 
 #include <algorithm>
 #include <cstddef>
-#include <cstring>
 #include <mutex>
 #include <string>
 #include <unordered_set>
@@ -41,15 +40,6 @@ struct ClientUpdateWs {
 };
 static PerDevice<ClientUpdateWs> g_cu_ws;
 
-// dynamic LDS above 64 KiB: told once per device (batch_host.hpp:LdsOnce)
-template <class C>
-static void cu_lds_attributes() {
-    using M = typename C::Fp;
-    static LdsOnce once;
-    once.set({lds_kernel(&k_cu_place<C>, sizeof(MacOctLds<M>)), lds_kernel(&k_update_mix_points_oct<C, 1, 0, CU_PARTS>, sizeof(MacOctLds<M>)),
-              lds_kernel(&k_update_mix_points_quad<C, 1, 0, CU_PARTS>, sizeof(MacQuadLds<M>))});
-}
-
 struct CuPlan {
     const CuDesc* d_desc;
     uint8_t* const* d_ptrs;
@@ -57,26 +47,16 @@ struct CuPlan {
     hipStream_t stream;
 };
 
-// the mixes of steps 0 .. lmax - 1 under the MAC side's table lease, the form by the step's butterfly count as mac_mix_core picks it
+// the mixes of steps 0 .. lmax - 1 under the MAC side's table lease
 template <class C>
 static int cu_launch_steps(const CuPlan& P, const std::vector<uint32_t>& active, uint32_t lmax, size_t n_total) {
-    using M = typename C::Fp;
     const uint32_t* tws = nullptr;
     int quad_log = 0, rc;
     if ((rc = mac_mix_tables_acquire(IccCurve<C>::id, n_total, P.stream, &tws, &quad_log))) return rc;
     for (uint32_t i = 0; i < lmax && !rc; i++) {
         const uint32_t a = active[i], tw_step = (uint32_t)(n_total >> i);
         ProfScope ps("client_update_mix", P.stream);
-        const size_t bf = ((size_t)CU_PARTS * a) << i, quad_max = (size_t)1 << quad_log;
-        if (quad_log > 0 && bf <= quad_max && bf <= MACO_MAX_BUTTERFLIES)
-            hipLaunchKernelGGL((k_update_mix_points_oct<C, 1, 0, CU_PARTS>), dim3((unsigned)((bf + MACO_BF - 1) / MACO_BF)), dim3(8 * MACO_BF),
-                               sizeof(MacOctLds<M>), P.stream, P.d_ptrs, P.l1, a, i, tws, tw_step);
-        else if (quad_log > 0 && bf <= quad_max)
-            hipLaunchKernelGGL((k_update_mix_points_quad<C, 1, 0, CU_PARTS>), dim3((unsigned)((bf + MACQ_BF - 1) / MACQ_BF)), dim3(4 * MACQ_BF),
-                               sizeof(MacQuadLds<M>), P.stream, P.d_ptrs, P.l1, a, i, tws, tw_step);
-        else
-            hipLaunchKernelGGL((k_update_mix_points_lane<C, 1, 0, CU_PARTS>), dim3((unsigned)((bf + 63) / 64)), dim3(64), 0, P.stream, P.d_ptrs,
-                               P.l1, a, i, tws, tw_step);
+        update_mix_points_launch<C, 1, 0, CU_PARTS>(P.d_ptrs, P.l1, a, i, tws, tw_step, quad_log, P.stream);   // the two parts: 2^1 families from 0
         if (hipGetLastError() != hipSuccess) { set_last_error("porla: client update batch: a mix launch failed"); rc = PORLA_ERR_HIP; }
     }
     const int r1 = mac_mix_tables_release(P.stream);
@@ -87,19 +67,9 @@ static int cu_launch_steps(const CuPlan& P, const std::vector<uint32_t>& active,
 template <class C>
 static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* fb_h, const porla_client_update_req* reqs, size_t k,
                       size_t ncols, size_t n_total, hipStream_t stream) {
-    using Q = typename IccCurve<C>::Q;
     int rc;
-    // ---- the plan: requests by level, highest first (stable), so that the requests step i concerns are the first active[i]
-    std::vector<uint32_t> order(k);
-    for (size_t a = 0; a < k; a++) order[a] = (uint32_t)a;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return reqs[x].level > reqs[y].level; });
-    const uint32_t lmax = (uint32_t)reqs[order[0]].level, l1 = lmax + 1;
-    std::vector<uint32_t> active(lmax);
-    for (uint32_t i = 0; i < lmax; i++) {
-        uint32_t a = 0;
-        while (a < k && (uint32_t)reqs[order[a]].level > i) a++;
-        active[i] = a;
-    }
+    const LevelPlan plan(k, [&](size_t a) { return reqs[a].level; });
+    const uint32_t lmax = plan.lmax, l1 = lmax + 1;
     // ---- sizes: the h pass' rows, and the pyramid at 4 * 2^level points per part and request
     size_t n_prf = 0, pyr_pts = 0;
     for (size_t a = 0; a < k; a++) {
@@ -127,15 +97,11 @@ static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* 
         size_t prf0 = 0;
         uint8_t* pyr = (uint8_t*)ws->pyramid.p;
         for (size_t a = 0; a < k; a++) {
-            const porla_client_update_req& R = reqs[order[a]];
+            const porla_client_update_req& R = reqs[plan.order[a]];
             CuDesc& D = hd[a];
             D.block = (const uint8_t*)R.d_block; D.prf = (const uint8_t*)R.d_prf;
             D.mac_out = (uint8_t*)R.d_mac_out; D.comp_out = (uint8_t*)R.d_complements_out;
-            uint32_t wt_p[8], wt_q[8];
-            uint8_t be[32];
-            (void)icc_wt_residues(IccCurve<C>::id, n_total, R.write_step, wt_p, wt_q, be);
-            h_load_be(D.wt_sc, be);
-            fe_reduce_plain<Q>(D.wt_sc, 8);                    // the group sees wt mod its order (convert_ZZ_to_scalar / fr.SetBytes)
+            write_wt<C>(n_total, R.write_step, D.wt_sc);
             D.level = (uint32_t)R.level; D.prf0 = (uint32_t)prf0;
             prf0 += ((size_t)4 << R.level) - 1;
             const size_t part_b = (size_t)256 << R.level;      // 4 * 2^level points
@@ -144,7 +110,6 @@ static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* 
                     hp[(a * CU_PARTS + part) * l1 + l] = l <= (uint32_t)R.level ? pyr + (size_t)128 * (((size_t)1 << l) - 1) : nullptr;
         }
     }
-    cu_lds_attributes<C>();
     if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
     CuPlan P;
     P.d_desc = (const CuDesc*)ws->list.p;
@@ -164,12 +129,7 @@ static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* 
     }
     // ---- 2. the block pass and the h pass
     if ((rc = client_block_pass<C>(fb_alpha, d_rows, k, ncols, d_blk, stream))) return rc;
-    if constexpr (IccCurve<C>::id == 0) {
-        if ((rc = porla_kzg_complement_batch_device(d_scal, n_prf, d_hpts, stream))) return rc;
-    } else {
-        std::lock_guard<std::mutex> lk(fb_h->mu);
-        if ((rc = fb_h->commit_device(d_scal, n_prf, 1, 32, d_hpts, stream))) return rc;
-    }
+    if ((rc = client_h_pass<C>(fb_h, d_scal, n_prf, d_hpts, stream))) return rc;
     // ---- 3. level 0 of the pyramid and the MAC
     if (lmax) {
         ProfScope ps("client_update_scatter", stream);
@@ -179,13 +139,15 @@ static int cu_enqueue(ClientUpdateWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* 
         PORLA_HIP(hipGetLastError());
     }
     {
+        static LdsOnce once;                           // dynamic LDS above 64 KiB: told once per device
+        once.set({lds_kernel(&k_cu_place<C>, sizeof(MacOctLds<typename C::Fp>))});
         ProfScope ps("client_update_place", stream);
         hipLaunchKernelGGL((k_cu_place<C>), dim3((unsigned)((k + MACO_BF - 1) / MACO_BF)), dim3(8 * MACO_BF), sizeof(MacOctLds<typename C::Fp>),
                            stream, P.d_desc, P.d_ptrs, l1, (uint32_t)k, d_blk, d_hpts);
         PORLA_HIP(hipGetLastError());
     }
     // ---- 4. the rebuild steps
-    if (lmax && (rc = cu_launch_steps<C>(P, active, lmax, n_total))) return rc;
+    if (lmax && (rc = cu_launch_steps<C>(P, plan.active, lmax, n_total))) return rc;
     // ---- 5. the close
     {
         ProfScope ps("client_update_close", stream);
@@ -201,7 +163,7 @@ static int cu_check(const char* who, const porla_client_update_req* reqs, size_t
     auto bad = [&](const std::string& what) { return bad_arg(who, what); };
     if (k && !reqs) return bad("reqs is NULL");
     if (int rc = check_n_total(who, n_total, 30)) return rc;
-    if (k > 0xffffu) return bad("more than 65535 requests in one call");
+    if (int rc = check_request_count(who, k)) return rc;
     std::unordered_set<const void*> seen;
     for (size_t a = 0; a < k; a++) {
         const porla_client_update_req& R = reqs[a];
@@ -234,11 +196,8 @@ extern "C" int porla_kzg_client_update_batch_device(const porla_client_update_re
     if (rc) return rc;
     if (k == 0) return PORLA_OK;
     if ((rc = ensure_device())) return rc;
-    // the key and the SRS, before any device work: an empty digest batch makes exactly that check
-    if ((rc = porla_kzg_digest_batch_device(nullptr, 0, nullptr, nullptr))) return rc;
-    const size_t n = kzg_n_samples();
-    if (n == 0) return kzg_no_srs();
-    if (n > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
+    size_t n;
+    if ((rc = client_kzg_row_width(&n))) return rc;
     ClientUpdateWs* ws = nullptr;
     if ((rc = g_cu_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -253,14 +212,12 @@ extern "C" int porla_ipa_client_update_batch_device(porla_fixed_base* alpha_gene
     if (k == 0) return PORLA_OK;
     if (!alpha_generators_fb || !h_fb) return bad_arg(who, "a NULL base");
     if ((rc = ensure_device())) return rc;
-    // (a handle exists only where a device does: it is read after ensure_device, and still before any device work)
-    if (alpha_generators_fb->curve != 1 || alpha_generators_fb->secp.n_points < CU_IPA_COLS)
-        return bad_arg(who, "alpha_generators_fb must be a secp256k1 fixed base over at least the 128 generators");
-    if (h_fb->curve != 1 || h_fb->secp.n_points != 1) return bad_arg(who, "h_fb must be a secp256k1 fixed base over exactly one point");
+    if ((rc = ipa_check_generators(who, "alpha_generators_fb", alpha_generators_fb))) return rc;
+    if ((rc = ipa_check_hiding_base(who, "h_fb", h_fb))) return rc;
     ClientUpdateWs* ws = nullptr;
     if ((rc = g_cu_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     return FencedCall(ws, stream).run([&] {
-        return cu_enqueue<Secp256k1G>(ws, &alpha_generators_fb->secp, &h_fb->secp, reqs, k, CU_IPA_COLS, n_total, stream);
+        return cu_enqueue<Secp256k1G>(ws, &alpha_generators_fb->secp, &h_fb->secp, reqs, k, IPA_COLS, n_total, stream);
     });
 }

@@ -311,7 +311,7 @@ hipStream_t engine_stream();  // this device's engine-owned non-blocking stream
 // icc.hip: wt = w^reverse_bits(write_step % n_total, height - 1) mod p_icc as a 32-byte big-endian integer (the MAC-side scalar of
 // Server::HAdd / Client::HAdd / CRebuild's Y halves)
 int icc_wt_scalar_be(size_t n_total, unsigned long long write_step, uint8_t out[32]);
-// icc.hip / mac_fft.hip, for update_batch.hip: wt of one write as both sides use it, and the tables the data mix (tw30: the
+// icc.hip / mac_fft.hip, for the write batches: wt of one write as both sides use it (write_batch_host.hpp: write_wt), and the tables the data mix (tw30: the
 // reduced-radix twiddles of k_icc_mix30) and the point mixes (tws: w^e mod p_icc reduced mod the group order) read.  An acquire that
 // succeeds returns with the owner's mutex held and its fence entered on `stream`; the release records the fence and unlocks.  Order
 // when both are held: the MAC side first (mac_fft.hip's matrix form takes them in that order).

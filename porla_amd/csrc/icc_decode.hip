@@ -53,7 +53,7 @@ static int icd_check(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, 
     auto bad = [&](const std::string& what) { return bad_arg(ICD_WHO, what); };
     if (k && !reqs) return bad("reqs is NULL");
     if (int rc = icd_check_shape(ICD_WHO, n_rows, n_cols, n_total, curve, form)) return rc;
-    if (k > 0xffffu) return bad("more than 65535 requests in one call");
+    if (int rc = check_request_count(ICD_WHO, k)) return rc;
     size_t t;
     if (k && (!mul_ok(n_rows * n_cols * 2 * ICC30_PLANE_WORDS * 4, k, &t)))
         return bad("a byte size overflows: the residue planes of k requests do not fit a buffer");

@@ -221,9 +221,8 @@ extern "C" int porla_kzg_audit_batch_device(const porla_kzg_audit_req* reqs, siz
     if (!mul_ok(k, 3 * 32 * 65536, &pt_b) || !mul_ok((size_t)pairs, 96, &pt_b)) return bad_arg(who, "the batch's byte size overflows");
     if (k == 0) return PORLA_OK;
     if ((rc = ensure_device())) return rc;
-    const size_t n = kzg_n_samples();
-    if (n == 0) return kzg_no_srs();
-    if (n > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
+    size_t n;
+    if ((rc = kzg_row_width(&n))) return rc;
     KzgAuditBatchWs* ws = nullptr;
     if ((rc = g_kab_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;

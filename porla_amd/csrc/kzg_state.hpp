@@ -4,6 +4,8 @@
 #include "batch_host.hpp"
 #include "pairing_host.hpp"
 
+#include <type_traits>
+
 namespace porla {
 
 // HBM copies, one set per device that has been used (the row-range splitter of porla_kzg_commit_batch_host_multi runs one host thread
@@ -54,6 +56,14 @@ static inline int kzg_no_srs() {
     return PORLA_ERR_STATE;
 }
 
+// the SRS size as the width of a commitment row, refused before there is an SRS and above what a row takes
+static inline int kzg_row_width(size_t* n) {
+    *n = kzg_n_samples();
+    if (*n == 0) return kzg_no_srs();
+    if (*n > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
+    return PORLA_OK;
+}
+
 // The one way to the resident SRS table.  Lock order: the state, then a table; a registry's mutex (PerDevice) is a leaf, held for
 // lookup only.  acquire() makes the table current under the state's lock and takes the table's mutex BEFORE the state is let go, so
 // that neither init_SRS_from_data / porla_kzg_set_commit_window nor porla_kzg_release_device_memory can rebuild or free the table
@@ -86,6 +96,13 @@ static int kzg_commit_rows_raw(const uint8_t* d_rows, size_t n_rows, hipStream_t
     if (rc) return rc;
     if (t.len == 0) { set_last_error("porla: more coefficients than SRS points"); return PORLA_ERR_STATE; }
     return commit_then_locked(*t.fb, d_rows, n_rows, t.len, stream, then);
+}
+// the same for either build of a write batch: the caller's fixed base (IPA), or fb == nullptr: the resident SRS (KZG, its own width)
+template <class C, class Then>
+static int commit_rows_then(FixedBase<C>* fb, const uint8_t* d_rows, size_t n_rows, size_t n_coeffs, hipStream_t stream, Then then) {
+    if constexpr (std::is_same<C, Bn254G1>::value)
+        if (!fb) return kzg_commit_rows_raw(d_rows, n_rows, stream, then);
+    return commit_then(*fb, d_rows, n_rows, n_coeffs, stream, then);
 }
 
 // for the batched verifier (kzg_verify_batch.hip): G1[0] as 64 bytes big-endian affine, PORLA_ERR_STATE without an SRS and its G2

@@ -97,31 +97,24 @@ static int mac_mix_core(MacWs* ws, int curve, const uint8_t* d_a0, const uint8_t
     mac_lds_attributes<C>();
     ProfScope ps("mac_mix", stream);
     const unsigned sets = d_b0 ? 2u : 1u;               // the second array pair (MAC alignments beside the MAC commitments)
-    const size_t quad_max = (size_t)1 << macq_max_log(14);
-    if (macq_max_log(14) > 0 && len * sets <= quad_max && len * sets <= MACO_MAX_BUTTERFLIES) {   // half the chip idle at four lanes: eight
+    const int quad_log = macq_max_log(14), form = mac_mix_form(len * sets, quad_log);
+    if (form == 8) {                                    // half the chip idle at four lanes
         hipLaunchKernelGGL((k_mac_mix_oct<C>), dim3((unsigned)((len + MACO_BF - 1) / MACO_BF), sets), dim3(8 * MACO_BF), maco_lds_bytes<C>(), stream, d_a0,
                            d_a1, (uint32_t)len, (const uint32_t*)ws->tws.p, (uint32_t)(n_total / len), d_out, d_b0, d_b1, d_out_b);
-        PORLA_HIP(hipGetLastError());
-        return PORLA_OK;
-    }
-    if (macq_max_log(14) > 0 && len * sets <= quad_max) {   // latency bound: four lanes per element (k_mac_stage30_quad's ladder)
+    } else if (form == 4) {
         hipLaunchKernelGGL((k_mac_mix_quad<C>), dim3((unsigned)((len + MACQ_BF - 1) / MACQ_BF), sets), dim3(4 * MACQ_BF), macq_lds_bytes<C>(), stream, d_a0,
                            d_a1, (uint32_t)len, (const uint32_t*)ws->tws.p, (uint32_t)(n_total / len), d_out, d_b0, d_b1, d_out_b);
-        PORLA_HIP(hipGetLastError());
-        return PORLA_OK;
-    }
-    if (macq_max_log(14) > 0 && sets == 2 && len <= quad_max) {
-        // two arrays of a length the four-lane kernel still takes one at a time (2^14 rows: 0.63 ms each; both in one launch of
-        // the one-lane kernel: 1.36 ms): two launches, one after the other
+    } else if (sets == 2 && mac_mix_form(len, quad_log) != 1) {
+        // one lane by the shared rule, but two arrays of a length the four-lane kernel still takes one at a time (2^14 rows: 0.63 ms
+        // each; both in one launch of the one-lane kernel: 1.36 ms): two launches, one after the other
         hipLaunchKernelGGL((k_mac_mix_quad<C>), dim3((unsigned)((len + MACQ_BF - 1) / MACQ_BF), 1), dim3(4 * MACQ_BF), macq_lds_bytes<C>(), stream, d_a0, d_a1,
                            (uint32_t)len, (const uint32_t*)ws->tws.p, (uint32_t)(n_total / len), d_out, d_b0, d_b1, d_out_b);
         hipLaunchKernelGGL((k_mac_mix_quad<C>), dim3((unsigned)((len + MACQ_BF - 1) / MACQ_BF), 1), dim3(4 * MACQ_BF), macq_lds_bytes<C>(), stream, d_b0, d_b1,
                            (uint32_t)len, (const uint32_t*)ws->tws.p, (uint32_t)(n_total / len), d_out_b, d_b0, d_b1, d_out_b);
-        PORLA_HIP(hipGetLastError());
-        return PORLA_OK;
+    } else {
+        hipLaunchKernelGGL((k_mac_mix<C>), dim3((unsigned)((len + 63) / 64), sets), dim3(64), 0, stream, d_a0, d_a1, (uint32_t)len,
+                           (const uint32_t*)ws->tws.p, (uint32_t)(n_total / len), d_out, d_b0, d_b1, d_out_b);
     }
-    hipLaunchKernelGGL((k_mac_mix<C>), dim3((unsigned)((len + 63) / 64), sets), dim3(64), 0, stream, d_a0, d_a1, (uint32_t)len,
-                       (const uint32_t*)ws->tws.p, (uint32_t)(n_total / len), d_out, d_b0, d_b1, d_out_b);
     PORLA_HIP(hipGetLastError());
     return PORLA_OK;
 }
@@ -260,7 +253,7 @@ static int mac_encode_core(MacWs* ws, int curve, const uint8_t* d_in, size_t n, 
 
 // For update_batch.hip: the scalar table the point mixes read (w^e mod p_icc, reduced mod the group order), under the lock and the
 // fence mac_mix_core's callers hold.  acquire returns with g_mac_mu HELD when it succeeds; release records the fence and lets go.
-// quad_max_log: the row count (log2) up to which mac_mix_core takes its four- and eight-lane forms (PORLA_MAC_QUAD_MAX).
+// quad_max_log: mac_mix_form's quad_log (mac_fft.hip.h), as mac_mix_core passes it (PORLA_MAC_QUAD_MAX).
 int mac_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** tws, int* quad_max_log) {
     g_mac_mu.lock();
     MacWs* ws = nullptr;

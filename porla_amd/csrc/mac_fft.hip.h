@@ -572,6 +572,12 @@ __device__ __forceinline__ void store_affine_be(uint8_t* dst, const XYZZ<M>& p);
 constexpr int MACO_BF = 32;
 // butterflies (or mix elements) up to which a launch leaves half the chip idle at four lanes each: eight lanes per butterfly
 constexpr size_t MACO_MAX_BUTTERFLIES = 8192;      // same-box A/B against four lanes: profiles/r05_k_mac_octet_ab.txt
+// Lanes per butterfly of one mix launch (Server::mix, the update batches' point mixes): up to 2^quad_log butterflies (PORLA_MAC_QUAD_MAX,
+// 0: never) eight while at most MACO_MAX_BUTTERFLIES, four above (latency bound: k_mac_stage30_quad's ladder); one beyond
+inline int mac_mix_form(size_t butterflies, int quad_log) {
+    if (quad_log <= 0 || butterflies > ((size_t)1 << quad_log)) return 1;
+    return butterflies <= MACO_MAX_BUTTERFLIES ? 8 : 4;
+}
 // (these kernels only run where the chip is under-filled: no neighbour to leave registers to -- two waves per SIMD, 256 registers)
 #define MACO_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
 template <class M>

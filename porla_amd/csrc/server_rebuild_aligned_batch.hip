@@ -12,6 +12,7 @@
 //     k_sr_data, SR_ALIGNED  the last pass: rows mod p_icc into data X / data Y, the alignment scalars into the workspace
 //     fb_commit / fb_fold    ONE commitment pass over the group's rows (the resident SRS table, or the generators' fixed base), sums projective
 //     k_sr_close, ALIGNED    + complements, to affine, into MAC X / MAC Y; the sums to affine into align X / align Y
+// (the commitment pass of either build: kzg_state.hpp's commit_rows_then; the IPA row width and base check: write_batch_host.hpp)
 #include "kzg_state.hpp"
 #include "server_rebuild_host.hpp"
 #include "server_rebuild_batch.hip.h"
@@ -21,7 +22,6 @@
 
 namespace porla {
 
-constexpr size_t SRA_IPA_COLS = 128;           // NUM_CHUNKS: the row width of the IPA build
 constexpr size_t SRA_ROWS_CEIL = (size_t)1 << 18;
 
 // rows of alignment scalars the workspace holds at most (PORLA_REBUILD_ROWS_MAX lowers it; read once per process)
@@ -83,9 +83,7 @@ static int sra_enqueue(ServerRebuildWs* ws, FixedBase<C>* fb, const porla_server
             PORLA_HIP(hipGetLastError());
             return (int)PORLA_OK;
         };
-        if constexpr (IccCurve<C>::id == 0) rc = kzg_commit_rows_raw(d_scalars, kg * 2 * n, stream, close);
-        else rc = commit_then(*fb, d_scalars, kg * 2 * n, ncols, stream, close);
-        if (rc) return rc;
+        if ((rc = commit_rows_then(fb, d_scalars, kg * 2 * n, ncols, stream, close))) return rc;
     }
     return PORLA_OK;
 }
@@ -112,17 +110,15 @@ extern "C" int porla_kzg_server_rebuild_aligned_batch_device(const porla_server_
 extern "C" int porla_ipa_server_rebuild_aligned_batch_device(porla_fixed_base* generators_fb, const porla_server_rebuild_req* reqs, size_t k,
                                                              size_t n_total, void* hip_stream) {
     static const char* who = "porla_ipa_server_rebuild_aligned_batch_device";
-    int rc = sr_check(who, reqs, k, n_total, SRA_IPA_COLS, 1);
+    int rc = sr_check(who, reqs, k, n_total, IPA_COLS, 1);
     if (rc) return rc;
     if (k == 0) return PORLA_OK;
     if (!generators_fb) return bad_arg(who, "generators_fb is NULL");
     if ((rc = ensure_device())) return rc;
-    // (a handle exists only where a device does: it is read after ensure_device, and still before any device work)
-    if (generators_fb->curve != 1 || generators_fb->secp.n_points < SRA_IPA_COLS)
-        return bad_arg(who, "generators_fb must be a secp256k1 fixed base over at least the 128 generators");
+    if ((rc = ipa_check_generators(who, "generators_fb", generators_fb))) return rc;
     ServerRebuildWs* ws = nullptr;
     if ((rc = sr_workspace(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     return FencedCall(ws, stream).run(
-        [&] { return sra_enqueue<Secp256k1G>(ws, &generators_fb->secp, reqs, k, n_total, SRA_IPA_COLS, stream); });
+        [&] { return sra_enqueue<Secp256k1G>(ws, &generators_fb->secp, reqs, k, n_total, IPA_COLS, stream); });
 }

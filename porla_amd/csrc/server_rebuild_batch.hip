@@ -20,8 +20,6 @@
 
 #include <algorithm>
 #include <cstddef>
-#include <cstring>
-#include <mutex>
 #include <string>
 #include <unordered_set>
 
@@ -134,10 +132,7 @@ static int sr_enqueue(ServerRebuildWs* ws, const porla_server_rebuild_req* reqs,
             D.data_x = (uint8_t*)R.d_data_x; D.data_y = (uint8_t*)R.d_data_y;
             D.mac_x = (uint8_t*)R.d_mac_x; D.mac_y = (uint8_t*)R.d_mac_y;
             D.align_x = (uint8_t*)R.d_align_x; D.align_y = (uint8_t*)R.d_align_y;
-            uint8_t be[32];
-            (void)icc_wt_residues(IccCurve<C>::id, n, R.write_step, D.wt_p, D.wt_q, be);
-            h_load_be(D.wt_sc, be);
-            fe_reduce_plain<Q>(D.wt_sc, 8);                    // the group sees wt mod its order (convert_ZZ_to_scalar / fr.SetBytes)
+            write_wt<C>(n, R.write_step, D.wt_sc, D.wt_p, D.wt_q);
             D.row = (uint32_t)(R.index - 1); D.pad = 0;
         }
     }
@@ -169,7 +164,7 @@ int sr_check(const char* who, const porla_server_rebuild_req* reqs, size_t k, si
     if (int rc = check_n_total(who, n_total, 16)) return rc;
     if (n_cols == 0) return bad("n_cols is 0");
     if (curve != 0 && curve != 1) return bad("curve must be 0 (BN254 / KZG) or 1 (secp256k1 / IPA)");
-    if (k > 0xffffu) return bad("more than 65535 requests in one call");
+    if (int rc = check_request_count(who, k)) return rc;
     size_t rows, t;
     if (!mul_ok(n_total, n_cols, &rows) || !mul_ok(rows, 128, &t) || !mul_ok(rows, 8 * ICC30_PLANE_WORDS, &t) || (k && !mul_ok(t, k, &t)))
         return bad("a byte size overflows: n_total * n_cols symbols do not fit a buffer");

@@ -1,9 +1,8 @@
 // Host pieces the two server rebuild calls share (server_rebuild_batch.hip: the CRebuild_Cached form, which defines them;
 // server_rebuild_aligned_batch.hip: the CRebuild_No_Cached form): the workspace, the argument checks, and the front of the launch
-// sequence -- everything up to the point where the two forms part.
+// sequence -- everything up to the point where the two forms part.  (Shared with the other write batches: write_batch_host.hpp.)
 #pragma once
-#include "batch_host.hpp"
-#include "icc_host.hpp"
+#include "write_batch_host.hpp"
 #include "../../include/porla_gpu.h"
 
 namespace porla {

@@ -10,22 +10,20 @@
 //   k_update_place           MAC X, MAC Y = wt * MAC, align X = infinity, align Y = Commit(c)
 //   for i < Lmax:            k_update_mix_data (both parts) and k_update_mix_points (the four point families) of the requests with level > i
 //   k_update_close           incoming half over resident half at the request's level, then the complements onto MAC X / MAC Y
+// (what the write batches decide alike is written once: write_batch_host.hpp and the places it names; a mix's form: update_batch.hip.h)
 #include "kzg_state.hpp"
 #include "update_batch.hip.h"
-#include "icc_host.hpp"
+#include "write_batch_host.hpp"
 #include "../../include/porla_gpu.h"
 
 #include <algorithm>
 #include <cstddef>
-#include <cstring>
 #include <mutex>
 #include <string>
 #include <unordered_set>
 #include <vector>
 
 namespace porla {
-
-constexpr size_t UPD_IPA_COLS = 128;           // NUM_CHUNKS: the row width of the IPA build
 
 struct UpdateBatchWs {
     std::mutex mu;
@@ -36,16 +34,6 @@ struct UpdateBatchWs {
 };
 static PerDevice<UpdateBatchWs> g_upd_ws;
 
-// dynamic LDS above 64 KiB: told once per device (batch_host.hpp:LdsOnce)
-static void update_lds_attributes() {
-    static LdsOnce once;
-    constexpr size_t oct_bn = sizeof(MacOctLds<Bn254Fp>), oct_secp = sizeof(MacOctLds<Secp256k1Fp>);
-    once.set({lds_kernel(&k_update_place<Bn254G1>, oct_bn), lds_kernel(&k_update_place<Secp256k1G>, oct_secp),
-              lds_kernel(&k_update_mix_points_oct<Bn254G1>, oct_bn), lds_kernel(&k_update_mix_points_oct<Secp256k1G>, oct_secp),
-              lds_kernel(&k_update_mix_points_quad<Bn254G1>, sizeof(MacQuadLds<Bn254Fp>)),
-              lds_kernel(&k_update_mix_points_quad<Secp256k1G>, sizeof(MacQuadLds<Secp256k1Fp>))});
-}
-
 struct UpdPlan {
     const UpdDesc* d_desc;
     uint8_t* const* d_ptrs;
@@ -55,6 +43,8 @@ struct UpdPlan {
 
 template <class C>
 static int launch_place(const UpdPlan& P, const XYZZ<typename C::Fp>* sums, uint32_t S) {
+    static LdsOnce once;                               // dynamic LDS above 64 KiB: told once per device
+    once.set({lds_kernel(&k_update_place<C>, sizeof(MacOctLds<typename C::Fp>))});
     ProfScope ps("update_place", P.stream);
     hipLaunchKernelGGL((k_update_place<C>), dim3((P.k + MACO_BF - 1) / MACO_BF), dim3(8 * MACO_BF), sizeof(MacOctLds<typename C::Fp>), P.stream,
                        P.d_desc, P.d_ptrs, P.l1, P.k, sums, S);
@@ -66,7 +56,6 @@ static int launch_place(const UpdPlan& P, const XYZZ<typename C::Fp>* sums, uint
 template <class C>
 static int launch_steps(const UpdPlan& P, const std::vector<uint32_t>& active, uint32_t lmax, size_t n_total) {
     using Q = typename IccCurve<C>::Q;
-    using M = typename C::Fp;
     const uint32_t* tws = nullptr;
     const uint32_t* tw30 = nullptr;
     int quad_log = 0, rc;
@@ -81,17 +70,7 @@ static int launch_steps(const UpdPlan& P, const std::vector<uint32_t>& active, u
                                tw30, tw_step);
         }
         ProfScope ps("update_mix_points", P.stream);
-        // the form by the step's total butterfly count, with mac_mix_core's thresholds
-        const size_t bf = ((size_t)4 * a) << i, quad_max = (size_t)1 << quad_log;
-        if (quad_log > 0 && bf <= quad_max && bf <= MACO_MAX_BUTTERFLIES)
-            hipLaunchKernelGGL((k_update_mix_points_oct<C>), dim3((unsigned)((bf + MACO_BF - 1) / MACO_BF)), dim3(8 * MACO_BF), sizeof(MacOctLds<M>),
-                               P.stream, P.d_ptrs, P.l1, a, i, tws, tw_step);
-        else if (quad_log > 0 && bf <= quad_max)
-            hipLaunchKernelGGL((k_update_mix_points_quad<C>), dim3((unsigned)((bf + MACQ_BF - 1) / MACQ_BF)), dim3(4 * MACQ_BF), sizeof(MacQuadLds<M>),
-                               P.stream, P.d_ptrs, P.l1, a, i, tws, tw_step);
-        else
-            hipLaunchKernelGGL((k_update_mix_points_lane<C>), dim3((unsigned)((bf + 63) / 64)), dim3(64), 0, P.stream, P.d_ptrs, P.l1, a, i, tws,
-                               tw_step);
+        update_mix_points_launch<C>(P.d_ptrs, P.l1, a, i, tws, tw_step, quad_log, P.stream);
         if (hipGetLastError() != hipSuccess) { set_last_error("porla: update batch: a mix launch failed"); rc = PORLA_ERR_HIP; }
     }
     const int r1 = icc_mix_tables_release(P.stream), r2 = mac_mix_tables_release(P.stream);
@@ -104,17 +83,8 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
                           hipStream_t stream) {
     using Q = typename IccCurve<C>::Q;
     int rc;
-    // ---- the plan: requests by level, highest first (stable), so that the requests step i concerns are the first active[i]
-    std::vector<uint32_t> order(k);
-    for (size_t a = 0; a < k; a++) order[a] = (uint32_t)a;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return reqs[x].level > reqs[y].level; });
-    const uint32_t lmax = (uint32_t)reqs[order[0]].level, l1 = lmax + 1;
-    std::vector<uint32_t> active(lmax);
-    for (uint32_t i = 0; i < lmax; i++) {
-        uint32_t a = 0;
-        while (a < k && (uint32_t)reqs[order[a]].level > i) a++;
-        active[i] = a;
-    }
+    const LevelPlan plan(k, [&](size_t a) { return reqs[a].level; });
+    const uint32_t lmax = plan.lmax, l1 = lmax + 1;
     // ---- the work list: descriptors | level pointers, one pinned buffer, one copy
     const size_t desc_b = k * sizeof(UpdDesc), ptr_b = k * UPD_FAMILIES * l1 * sizeof(void*), list_b = desc_b + ptr_b;
     if ((rc = ws->h_list.stage(list_b))) return rc;
@@ -122,13 +92,10 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
         UpdDesc* hd = (UpdDesc*)ws->h_list.h;
         void** hp = (void**)((uint8_t*)ws->h_list.h + desc_b);
         for (size_t a = 0; a < k; a++) {
-            const porla_update_req& R = reqs[order[a]];
+            const porla_update_req& R = reqs[plan.order[a]];
             UpdDesc& D = hd[a];
             D.block = (const uint8_t*)R.d_block; D.mac = (const uint8_t*)R.d_mac; D.comp = (const uint8_t*)R.d_complements;
-            uint8_t be[32];
-            (void)icc_wt_residues(IccCurve<C>::id, n_total, R.write_step, D.wt_p, D.wt_q, be);
-            h_load_be(D.wt_sc, be);
-            fe_reduce_plain<Q>(D.wt_sc, 8);                    // the group sees wt mod its order (convert_ZZ_to_scalar / fr.SetBytes)
+            write_wt<C>(n_total, R.write_step, D.wt_sc, D.wt_p, D.wt_q);
             D.level = (uint32_t)R.level; D.pad = 0;
             void* const* fam[UPD_FAMILIES] = {R.data_x, R.data_y, R.mac_x, R.mac_y, R.align_x, R.align_y};
             for (uint32_t f = 0; f < UPD_FAMILIES; f++)
@@ -137,7 +104,6 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
     }
     if ((rc = ws->list.ensure(list_b))) return rc;
     if ((rc = ws->scalars.ensure(k * ncols * 32))) return rc;
-    update_lds_attributes();
     if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
     UpdPlan P;
     P.d_desc = (const UpdDesc*)ws->list.p;
@@ -152,11 +118,9 @@ static int update_enqueue(UpdateBatchWs* ws, FixedBase<C>* fb, const porla_updat
     }
     // ---- 2. the K commitments, then the four point slots
     auto place = [&](const XYZZ<typename C::Fp>* sums, uint32_t S) { return launch_place<C>(P, sums, S); };
-    if constexpr (IccCurve<C>::id == 0) rc = kzg_commit_rows_raw((const uint8_t*)ws->scalars.p, k, stream, place);
-    else rc = commit_then(*fb, (const uint8_t*)ws->scalars.p, k, ncols, stream, place);
-    if (rc) return rc;
+    if ((rc = commit_rows_then(fb, (const uint8_t*)ws->scalars.p, k, ncols, stream, place))) return rc;
     // ---- 3. the rebuild steps
-    if (lmax && (rc = launch_steps<C>(P, active, lmax, n_total))) return rc;
+    if (lmax && (rc = launch_steps<C>(P, plan.active, lmax, n_total))) return rc;
     // ---- 4. the close
     {
         ProfScope ps("update_close", stream);
@@ -173,7 +137,7 @@ static int update_check(const char* who, const porla_update_req* reqs, size_t k,
     auto bad = [&](const std::string& what) { return bad_arg(who, what); };
     if (k && !reqs) return bad("reqs is NULL");
     if (int rc = check_n_total(who, n_total, 30)) return rc;
-    if (k > 0xffffu) return bad("more than 65535 requests in one call");
+    if (int rc = check_request_count(who, k)) return rc;
     std::unordered_set<const void*> seen;
     for (size_t a = 0; a < k; a++) {
         const porla_update_req& R = reqs[a];
@@ -210,9 +174,8 @@ extern "C" int porla_kzg_update_batch_device(const porla_update_req* reqs, size_
     if (rc) return rc;
     if (k == 0) return PORLA_OK;
     if ((rc = ensure_device())) return rc;
-    const size_t n = kzg_n_samples();
-    if (n == 0) return kzg_no_srs();
-    if (n > 0xffffu) { set_last_error("porla: SRS longer than a commitment row takes"); return PORLA_ERR_STATE; }
+    size_t n;
+    if ((rc = kzg_row_width(&n))) return rc;
     UpdateBatchWs* ws = nullptr;
     if ((rc = g_upd_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -227,12 +190,10 @@ extern "C" int porla_ipa_update_batch_device(porla_fixed_base* generators_fb, co
     if (k == 0) return PORLA_OK;
     if (!generators_fb) return bad_arg(who, "generators_fb is NULL");
     if ((rc = ensure_device())) return rc;
-    // (a handle exists only where a device does: it is read after ensure_device, and still before any device work)
-    if (generators_fb->curve != 1 || generators_fb->secp.n_points < UPD_IPA_COLS)
-        return bad_arg(who, "generators_fb must be a secp256k1 fixed base over at least the 128 generators");
+    if ((rc = ipa_check_generators(who, "generators_fb", generators_fb))) return rc;
     UpdateBatchWs* ws = nullptr;
     if ((rc = g_upd_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     return FencedCall(ws, stream).run(
-        [&] { return update_enqueue<Secp256k1G>(ws, &generators_fb->secp, reqs, k, UPD_IPA_COLS, n_total, stream); });
+        [&] { return update_enqueue<Secp256k1G>(ws, &generators_fb->secp, reqs, k, IPA_COLS, n_total, stream); });
 }

@@ -113,7 +113,7 @@ k_update_mix_data(uint8_t* const* __restrict__ ptrs, uint32_t l1, uint32_t activ
 }
 
 // ---- step i, the point families of the first `active` requests: butterfly g of the step belongs to item g >> i = (request, family)
-// and is row g & (2^i - 1) of it.  FORM 8 / 4 / 1: lanes per butterfly, the forms of mac_mix_core.  A request's point families are
+// and is row g & (2^i - 1) of it.  _oct / _quad / _lane: 8 / 4 / 1 lanes per butterfly, picked by update_mix_points_launch below.  A request's point families are
 // 2^LOGF consecutive ones from FIRST on, of STRIDE families per request in the pointer table: the server's four (MAC X, MAC Y,
 // align X, align Y) of its six by default; the client update batch (client_update_batch.hip.h) mixes its two complement parts.
 template <class C, uint32_t LOGF, uint32_t FIRST, uint32_t STRIDE>
@@ -160,6 +160,28 @@ k_update_mix_points_lane(uint8_t* const* __restrict__ ptrs, uint32_t l1, uint32_
     const uint8_t* a0; uint8_t* out; uint32_t row;
     upd_point_item<C, LOGF, FIRST, STRIDE>(ptrs, l1, i, g, a0, out, row);
     mac_mix_one<C>(a0, a0 + ((size_t)64 << i), row, 1u << i, tws, tw_step, out);
+}
+// host: step i's launch in the form mac_mix_form gives for its butterfly count (tws, quad_log: mac_mix_tables_acquire's, the lease
+// held).  Dynamic LDS above 64 KiB is told here, once per device and instantiation (LdsOnce): what is told is what is launched.
+template <class C, uint32_t LOGF = 2, uint32_t FIRST = UPD_MAC_X, uint32_t STRIDE = UPD_FAMILIES>
+static void update_mix_points_launch(uint8_t* const* d_ptrs, uint32_t l1, uint32_t active, uint32_t i, const uint32_t* tws, uint32_t tw_step,
+                                     int quad_log, hipStream_t stream) {
+    using M = typename C::Fp;
+    const size_t bf = ((size_t)active << LOGF) << i;
+    const int form = mac_mix_form(bf, quad_log);       // (the step's butterflies: 2^LOGF families of 2^i rows per request)
+    if (form == 8) {
+        static LdsOnce once;
+        once.set({lds_kernel(&k_update_mix_points_oct<C, LOGF, FIRST, STRIDE>, sizeof(MacOctLds<M>))});
+        hipLaunchKernelGGL((k_update_mix_points_oct<C, LOGF, FIRST, STRIDE>), dim3((unsigned)((bf + MACO_BF - 1) / MACO_BF)), dim3(8 * MACO_BF),
+                           sizeof(MacOctLds<M>), stream, d_ptrs, l1, active, i, tws, tw_step);
+    } else if (form == 4) {
+        static LdsOnce once;
+        once.set({lds_kernel(&k_update_mix_points_quad<C, LOGF, FIRST, STRIDE>, sizeof(MacQuadLds<M>))});
+        hipLaunchKernelGGL((k_update_mix_points_quad<C, LOGF, FIRST, STRIDE>), dim3((unsigned)((bf + MACQ_BF - 1) / MACQ_BF)), dim3(4 * MACQ_BF),
+                           sizeof(MacQuadLds<M>), stream, d_ptrs, l1, active, i, tws, tw_step);
+    } else
+        hipLaunchKernelGGL((k_update_mix_points_lane<C, LOGF, FIRST, STRIDE>), dim3((unsigned)((bf + 63) / 64)), dim3(64), 0, stream, d_ptrs, l1,
+                           active, i, tws, tw_step);
 }
 
 // ---- the close: blockIdx.y = the request.  The incoming half of level `level` over its resident half in all six families
