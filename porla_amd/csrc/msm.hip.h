@@ -228,6 +228,46 @@ static inline int sort_lowbits(int c, size_t m, int W) {
     return lb;
 }
 
+// The launch shape of the sort front for n pairs in W windows of c bits: one owner for msm_launch and tools/sort_check.hip.
+//   tile_cap  items a tile can hold per window (two sub-scalars per scalar with the split)     T_tiles  tiles of TILE scalars
+//   lowbits   a partition = 2^lowbits buckets                                                  P        partitions per window
+//   sort_half k_partition_sort in its half-size instantiation                                  wg       blocks of k_digits_partition per tile
+struct SortFrontPlan {
+    uint32_t tile_cap, T_tiles;
+    int lowbits;
+    bool sort_half;
+    int P;
+    unsigned wg;
+};
+static inline SortFrontPlan sort_front_plan(size_t n, bool glv, int c, int W) {
+    SortFrontPlan pl;
+    const size_t n_sub = glv ? 2 * n : n;                 // sub-scalars = entries per window at most
+    pl.tile_cap = glv ? 2 * TILE : TILE;
+    pl.T_tiles = (uint32_t)((n + TILE - 1) / TILE);
+    pl.lowbits = sort_lowbits(c, n_sub, W);
+    // Half-size partitions -- twice the blocks, half the staging area (78 KiB of LDS): TWO sort blocks per compute unit, whose
+    // load -> LDS-atomic chains then overlap -- where a partition's expected entries fit the smaller staging area and a tile's run
+    // of a partition still holds 64 items (one coalesced load per wave).  Same box, profiles/r05_ag_sort_half_ab.txt: blocking calls of
+    // 2^18 / 2^19 / 2^20 pairs -2 % / -2.3 % / -1.2 %, three in flight -1 % / -2.3 % / 0; 2^21 pairs (32-item runs) would lose 1.5 %.
+    pl.sort_half = false;
+    {
+        const int lb2 = pl.lowbits - 1, parts_log = c - 1 - lb2;
+        if (lb2 >= 0 && lb2 <= 11 && parts_log <= 7 && (n_sub >> parts_log) <= 16384 && (pl.tile_cap >> parts_log) >= 64) {
+            pl.lowbits = lb2;
+            pl.sort_half = true;
+        }
+    }
+    pl.P = 1 << (c - 1 - pl.lowbits);
+    // blocks per tile: up to 2^19 pairs the windows of a tile are split over enough blocks to give every CU one (a block
+    // walks its windows one after the other: 74 -> 50 us at 2^18 with four blocks per tile); larger inputs keep one block
+    // per tile -- every extra block re-reads the tile's scalars: 0.07 -> 0.18 ms at 2^20 with four
+    // (profiles/r02_g_digits_blocks_per_tile.jsonl)
+    pl.wg = pl.T_tiles < 256 ? 256u / pl.T_tiles : 1u;
+    if (pl.wg > 16) pl.wg = 16;
+    if (pl.wg > (unsigned)W) pl.wg = (unsigned)W;
+    return pl;
+}
+
 // exclusive scan of one value per thread over a 1024-thread block; returns the exclusive prefix, *total = block sum
 __device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t* wsum /* 16 */, uint32_t* total) {
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -402,7 +442,7 @@ k_digits_partition(const uint8_t* __restrict__ scalars, uint32_t n, int c, int W
 }
 
 // grid = W * P blocks of 1024 threads (16 waves; wave v takes tiles v, v+16, ...).  STAGE_CAP / MAX_LOW: the staging area and the
-// bucket counters in LDS -- the full size (one block per compute unit) or half of each (two: msm_impl.hip.h)
+// bucket counters in LDS -- the full size (one block per compute unit) or half of each (two: sort_front_plan)
 template <int STAGE_CAP, int MAX_LOW>
 __global__ void __launch_bounds__(1024)
 k_partition_sort(const uint32_t* __restrict__ tile_items, const uint16_t* __restrict__ tile_off, uint32_t T, uint32_t tile_cap,

@@ -241,16 +241,19 @@ static int msm_launch(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_
         if (used < 250 && used < bits) bits = used;       // < 2^250 < both group orders: no reduction happens
     }
     const size_t n_sub = glv ? 2 * n : n;                 // sub-scalars = entries per window at most
-    const uint32_t tile_cap = glv ? 2 * TILE : TILE;
     const int c = forced ? forced->c : choose_window(n_sub, bits);
     const int W = (bits + 1 + c - 1) / c;
+    // the launch shape of the sort front: partition width, half-size partitions, blocks per tile (msm.hip.h:sort_front_plan)
+    const SortFrontPlan sf = sort_front_plan(n, glv, c, W);
+    const uint32_t tile_cap = sf.tile_cap, T_tiles = sf.T_tiles;
+    const int lowbits = sf.lowbits, P = sf.P;
+    const bool sort_half = sf.sort_half;
     const uint32_t B = 1u << (c - 1);
     const size_t nb = (size_t)W * B;
     const uint32_t n32 = (uint32_t)n;
 
     int rc;
     if ((rc = ws->pts.ensure(n_sub * sizeof(Affine<M>)))) return rc;
-    const uint32_t T_tiles = (uint32_t)((n + TILE - 1) / TILE);
     const uint32_t nblk = (uint32_t)((nb + 1023) / 1024);
     const size_t max_entries = (size_t)W * n_sub;
     // the sort's cursor, starts[] and the entry offsets are 32-bit
@@ -299,34 +302,13 @@ static int msm_launch(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_
                                (Affine<M>*)ws->pts.p, n32);
     }
     if (front_split) PORLA_HIP(hipEventRecord(ws->front_join_ev, ws->aux_stream));
-    int lowbits = sort_lowbits(c, n_sub, W);
-    // Half-size partitions -- twice the blocks, half the staging area (78 KiB of LDS): TWO sort blocks per compute unit, whose
-    // load -> LDS-atomic chains then overlap -- where a partition's expected entries fit the smaller staging area and a tile's run
-    // of a partition still holds 64 items (one coalesced load per wave).  Same box, profiles/r05_ag_sort_half_ab.txt: blocking calls of
-    // 2^18 / 2^19 / 2^20 pairs -2 % / -2.3 % / -1.2 %, three in flight -1 % / -2.3 % / 0; 2^21 pairs (32-item runs) would lose 1.5 %.
-    bool sort_half = false;
-    {
-        const int lb2 = lowbits - 1, parts_log = c - 1 - lb2;
-        if (lb2 >= 0 && lb2 <= 11 && parts_log <= 7 && (n_sub >> parts_log) <= 16384 && (tile_cap >> parts_log) >= 64) {
-            lowbits = lb2;
-            sort_half = true;
-        }
-    }
-    const int P = 1 << (c - 1 - lowbits);
     {
         ProfScope ps("digits_partition", stream);
-        // blocks per tile: up to 2^19 pairs the windows of a tile are split over enough blocks to give every CU one (a block
-        // walks its windows one after the other: 74 -> 50 us at 2^18 with four blocks per tile); larger inputs keep one block
-        // per tile -- every extra block re-reads the tile's scalars: 0.07 -> 0.18 ms at 2^20 with four
-        // (profiles/r02_g_digits_blocks_per_tile.jsonl)
-        unsigned wg = T_tiles < 256 ? 256u / T_tiles : 1u;
-        if (wg > 16) wg = 16;
-        if (wg > (unsigned)W) wg = (unsigned)W;
         if (glv)
-            hipLaunchKernelGGL((k_digits_partition<C, true>), dim3(T_tiles, wg), dim3(TILE_THREADS), 0, stream, d_scalars, n32, c, W,
+            hipLaunchKernelGGL((k_digits_partition<C, true>), dim3(T_tiles, sf.wg), dim3(TILE_THREADS), 0, stream, d_scalars, n32, c, W,
                                lowbits, (uint32_t*)ws->keys.p, (uint16_t*)ws->tile_off.p, ctrl);
         else
-            hipLaunchKernelGGL((k_digits_partition<C, false>), dim3(T_tiles, wg), dim3(TILE_THREADS), 0, stream, d_scalars, n32, c, W,
+            hipLaunchKernelGGL((k_digits_partition<C, false>), dim3(T_tiles, sf.wg), dim3(TILE_THREADS), 0, stream, d_scalars, n32, c, W,
                                lowbits, (uint32_t*)ws->keys.p, (uint16_t*)ws->tile_off.p, ctrl);
     }
     {
