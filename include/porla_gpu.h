@@ -661,8 +661,9 @@ int porla_ipa_update_batch_device(porla_fixed_base *generators_fb, const porla_u
  * compute_MAC_complement for every slot below the level the write lands on, Client::HAdd -> HRebuildX / HRebuildY :978-1038 on them,
  * mix :921-976, and the differences "new complement - mixed complement" that go on the wire) ----
  * The other side of porla_*_update_batch_device: d_mac_out and d_complements_out are what porla_update_req takes as d_mac and
- * d_complements, and d_block is the SAME buffer.  AES stays on the host: the caller passes the 16-byte AES_encrypt outputs of
- * compute_MAC_complement raw.  Request a is one write:
+ * d_complements, and d_block is the SAME buffer.  AES may stay on the host -- the caller passes the 16-byte AES_encrypt outputs of
+ * compute_MAC_complement raw -- or d_prf is made on the device by porla_mac_prf_batch_device from porla_client_prf_runs' list.
+ * Request a is one write:
  *   d_block            n_cols x 32 bytes little-endian raw chunks (any 256-bit values; reduced mod the group order)
  *   d_prf              2^(level+2) - 1 PRF outputs of 16 raw bytes: [0] the block's own complement (compute_MAC_complement(0, block_id),
  *                      :467); then for i = 0 .. level-1 level i's resident complements, X part j = 0 .. 2^i-1, then Y part (the values
@@ -893,6 +894,111 @@ int porla_icc_decode_batch_device(const porla_icc_decode_req *reqs, size_t k, si
                                   int form, void *hip_stream);
 int porla_icc_decode_host(const uint8_t *rows, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form,
                           const unsigned long long *write_steps, uint8_t *out, unsigned int *bad);
+
+/* ---- AES on the device: the MAC PRF of the client writes, the audit challenge from its seed, the client's complement scalar ----
+ * These calls PRODUCE the buffers the batches above consume (d_prf; d_idx* / d_coef* / d_mac_*; the 32-byte scalars of
+ * porla_kzg_complement_batch_device or of a one-point fixed base) and change none of them.  Both uses are standard AES-128
+ * (FIPS-197): the reference's PRG (porla/Utils/prg.h:44-50, 84-97) and AES_encrypt under SECRET_KEY (Client.hpp:423-443).
+ * Definitions, written once for host and device: porla_amd/csrc/challenge_host.hpp; INTEGRATION s3g has the flow.
+ *
+ * The MAC PRF.  A run names count triples: slot t is (level, index0 + t, time0 + t * time_stride), index wrapping as an int32 does,
+ * and its value the 16 raw bytes of AES(key16, level int32 LE | index int32 LE | time int64 LE).  porla_mac_prf_batch_device writes
+ * the values of all runs back to back in run order into d_out (device memory, 16-byte aligned, 16 * sum count bytes), asynchronously
+ * on hip_stream: no host wait, no side stream.  runs is a HOST array.  One lane per AES block; the round keys are expanded on the
+ * host and travel as a kernel argument; the one 1 KiB table lives in LDS.  porla_mac_prf_host is the same on the host, no device.
+ * PORLA_ERR_ARG (with a message, before the device is touched): key16, runs or d_out NULL while there is something to write; d_out
+ * not 16-byte aligned; more than 2^38 values in one call.  n_runs = 0 or all counts 0 returns 0; valid arguments without a device:
+ * PORLA_ERR_NO_DEVICE. */
+#define PORLA_PRF_RUN_BYTES 32   /* sizeof(porla_prf_run) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    int level; int index0;                     /* offsets 0, 4 */
+    unsigned long long count;                  /* 8 */
+    long long time0; long long time_stride;    /* 16, 24 */
+} porla_prf_run;
+int porla_mac_prf_batch_device(const uint8_t key16[16], const porla_prf_run *runs, size_t n_runs, void *d_out, void *hip_stream);
+int porla_mac_prf_host(const uint8_t key16[16], const porla_prf_run *runs, size_t n_runs, uint8_t *out);
+/* the run list whose values are the d_prf of one request of porla_*_client_update_batch_device (PORLA_PRF_UPDATE: level + 2 runs,
+ * 2^(level+2) - 1 values) or porla_*_client_rebuild_batch_device (PORLA_PRF_REBUILD: 3 runs, 3 * n_total + 1 values; level is
+ * ignored), in the order those requests document.  write_step is the request's (after the ++ of Client.hpp:480).  Host only.
+ *   update:  (0, block_id, W - 1); for i < level: (i, j, t_i), j < 2^(i+1), t_i = (W & ~2^level) | (2^level - 2^i); (level, j, W), j < 2^(level+1)
+ *   rebuild: (0, block_id, W - 1); (0, i + 1, W - n_total + i), i < n_total; (log2 n_total, j, W), j < 2 n_total
+ * PORLA_ERR_ARG: what the batches refuse (n_total not a power of two in 2 .. 2^30; update: level < 0 or 2^level > n_total / 2,
+ * write_step % n_total == 0), an unknown kind, a NULL output, max_runs too small. */
+#define PORLA_PRF_UPDATE  0
+#define PORLA_PRF_REBUILD 1
+int porla_client_prf_runs(int kind, int block_id, unsigned long long write_step, int level, size_t n_total, porla_prf_run *runs_out,
+                          size_t max_runs, size_t *n_runs, size_t *n_values);
+
+/* The audit challenge from its 16-byte seed (Server.hpp:595-732, Client.hpp:682-744).  s = the int stream of the PRG keyed with the
+ * seed: int t is the little-endian int32 at byte 4t of AES(seed, counter as u64 LE | 0), counters from 0.  N = num_blocks (a power of
+ * two, 2 .. 2^24), H = log2 N + 1, ws = write_step % N.  Level i (l = 2^i) is challenged iff bit i of ws is set or i = H - 1; with
+ * 2l > 128 it has 128 points, index = mag(s[pos + j]) mod 2l, coef = mag(s[pos + 128 + j]), pos += 256; otherwise its 2l rows, index =
+ * j, coef = mag(s[pos + j]), pos += 2l.  index >= l is row index - l of the Y half, otherwise row index of the X half.
+ * mag(v) = |v| as a uint32 with mag(INT32_MIN) = 2^31: the one place the library DEFINES what the reference leaves undefined (abs).
+ * levels is a HOST array of H descriptors: the row numbers at which level i's halves begin inside the caller's stores (data_*: in
+ * the store the level's form names, 0 = the 64-byte rows of d_rows64, 1 = the 32-byte rows of d_rows32; mac_*: in d_mac_store /
+ * d_align_store).  For point p (numbered in walk order) at level i, row r of half X / Y:
+ *   d_mac_idx[p] = mac_{x|y}[i] + r, d_mac_coef[p] = coef, and the pair (data_{x|y}[i] + r, coef) is appended, in point order, to
+ *   (d_idx64, d_coef64) or (d_idx32, d_coef32).
+ * infos_out[k] is HOST memory, filled before the call returns (it needs the seed, write_step, num_blocks, the forms and two AES
+ * blocks): the list lengths, KZG's random_point = (uint64)(int64) s[pos] (Server.hpp:907) and IPA's a = s[n_points] (:861) raw and as
+ * a_value (32 bytes big-endian, a mod n: a negative a is n - |a|).  A caller fills porla_kzg_audit_req / porla_ipa_audit_req from it
+ * and enqueues the audit batch right behind this call on the same stream.  The six outputs are device memory (idx 8-, coef 4-byte
+ * aligned); a request with all six NULL is planned only, and a call of such requests touches no device.
+ * porla_audit_challenge_host: the same with the six outputs in HOST memory; no device.
+ * Asynchronous on hip_stream, no host wait, no side stream.  PORLA_ERR_ARG (with a message, before the device is touched): reqs or
+ * infos_out NULL while k > 0; levels NULL; num_blocks not a power of two in 2 .. 2^24; form > 1; pad != 0; a NULL or misaligned list
+ * whose count is > 0 (unless all six are NULL); more than 65535 requests.  k = 0 returns 0; valid arguments without a device:
+ * PORLA_ERR_NO_DEVICE. */
+#define PORLA_AUDIT_LEVEL_BYTES 40            /* sizeof(porla_audit_level) */
+#define PORLA_AUDIT_CHALLENGE_REQ_BYTES 88    /* sizeof(porla_audit_challenge_req) on LP64 */
+#define PORLA_AUDIT_CHALLENGE_INFO_BYTES 72   /* sizeof(porla_audit_challenge_info) */
+typedef struct {
+    unsigned long long data_x, data_y, mac_x, mac_y;   /* offsets 0, 8, 16, 24 */
+    int form; int pad;                                 /* 32, 36 */
+} porla_audit_level;
+typedef struct {
+    uint8_t seed[16];                                  /* 0 */
+    unsigned long long write_step, num_blocks;         /* 16, 24 */
+    const porla_audit_level *levels;                   /* 32 */
+    uint64_t *d_idx64; uint32_t *d_coef64;             /* 40, 48 */
+    uint64_t *d_idx32; uint32_t *d_coef32;             /* 56, 64 */
+    uint64_t *d_mac_idx; uint32_t *d_mac_coef;         /* 72, 80 */
+} porla_audit_challenge_req;
+typedef struct {
+    unsigned long long n64, n32, n_macs;               /* 0, 8, 16 */
+    unsigned long long random_point;                   /* 24 */
+    int a_raw; int pad;                                /* 32, 36 */
+    uint8_t a_value[32];                               /* 40 */
+} porla_audit_challenge_info;
+int porla_audit_challenge_batch_device(const porla_audit_challenge_req *reqs, size_t k, porla_audit_challenge_info *infos_out,
+                                       void *hip_stream);
+int porla_audit_challenge_host(const porla_audit_challenge_req *reqs, size_t k, porla_audit_challenge_info *infos_out);
+
+/* The client's side of a MAC check without a complement store.  Every complement is prf * h, so sum_p coef_p * comp[idx_p] =
+ * (sum_p coef_p * val_p) * h: d_scalars[k] (device memory, 32 bytes big-endian each) is that sum for the challenge of reqs[k], val_p the
+ * PRF output of (i, index, write_step & ~(2^i - 1)) -- the FULL write_step, Client.hpp:646-650 -- read as the write batches read it
+ * (curve 0, KZG: a big-endian 128-bit integer; curve 1, IPA: r.d[0], r.d[1], a little-endian one).  The sum is exact: every term is
+ * < 2^160 and there are fewer than 2^12 of them, so it stays below 2^172 and below either group order.  ONE point P_k = s_k * h
+ * (porla_kzg_complement_batch_device, or a commit against the one-point base h_fb) then stands in for the whole store in
+ * porla_*_verify_batch_device: d_comp_store = P_k, idx = [0], coef = [1], n = 1.  One work-group per request.
+ * Asynchronous on hip_stream.  PORLA_ERR_ARG: key16, reqs or d_scalars NULL while k > 0; curve not 0 or 1; num_blocks as above; more
+ * than 65535 requests.  k = 0 returns 0; no device: PORLA_ERR_NO_DEVICE.  _host: scalars in host memory, no device. */
+#define PORLA_AUDIT_SCALAR_REQ_BYTES 32
+typedef struct {
+    uint8_t seed[16];
+    unsigned long long write_step, num_blocks;
+} porla_audit_scalar_req;
+int porla_audit_complement_scalar_batch_device(const uint8_t key16[16], const porla_audit_scalar_req *reqs, size_t k, int curve,
+                                               void *d_scalars, void *hip_stream);
+int porla_audit_complement_scalar_host(const uint8_t key16[16], const porla_audit_scalar_req *reqs, size_t k, int curve,
+                                       uint8_t *scalars);
+/* diagnostic (tests): the walk of porla_audit_challenge_* over an int stream the caller wrote in place of the PRG's, on the host
+ * (on_device = 0) or through the device kernel (1; blocking).  Everything is HOST memory; all six lists and info are required and
+ * hold up to n_macs entries; n_ints must cover every int the walk and its tail read. */
+int porla_diag_audit_walk(const int32_t *stream_ints, size_t n_ints, unsigned long long write_step, unsigned long long num_blocks,
+                          const porla_audit_level *levels, int on_device, uint64_t *idx64, uint32_t *coef64, uint64_t *idx32,
+                          uint32_t *coef32, uint64_t *mac_idx, uint32_t *mac_coef, porla_audit_challenge_info *info);
 
 /* ---- audit row combine (Server::audit, Server.hpp:790-828) + the scalar part of align_MAC on the result (:531-541) ----
  * B_j = sum_i coeff_i * row_i[j] (exact integer), then aligned_j = B_j mod p_icc, c_j = (aligned_j - B_j) mod q.

@@ -97,6 +97,60 @@ PORLA_ICC_DECODE_REQ_BYTES = 32
 assert ctypes.sizeof(IccDecodeReq) == PORLA_ICC_DECODE_REQ_BYTES
 
 
+class PrfRun(ctypes.Structure):
+    """porla_prf_run, include/porla_gpu.h: count triples (level, index0 + t, time0 + t * time_stride) of the MAC PRF
+    (PORLA_PRF_RUN_BYTES = 32)."""
+    _fields_ = [("level", ctypes.c_int), ("index0", ctypes.c_int), ("count", ctypes.c_ulonglong), ("time0", ctypes.c_longlong),
+                ("time_stride", ctypes.c_longlong)]
+
+
+PORLA_PRF_RUN_BYTES = 32
+assert ctypes.sizeof(PrfRun) == PORLA_PRF_RUN_BYTES
+
+
+class AuditLevel(ctypes.Structure):
+    """porla_audit_level, include/porla_gpu.h: where a level's halves begin inside the caller's stores (PORLA_AUDIT_LEVEL_BYTES = 40)."""
+    _fields_ = [("data_x", ctypes.c_ulonglong), ("data_y", ctypes.c_ulonglong), ("mac_x", ctypes.c_ulonglong), ("mac_y", ctypes.c_ulonglong),
+                ("form", ctypes.c_int), ("pad", ctypes.c_int)]
+
+
+PORLA_AUDIT_LEVEL_BYTES = 40
+assert ctypes.sizeof(AuditLevel) == PORLA_AUDIT_LEVEL_BYTES
+
+
+class AuditChallengeReq(ctypes.Structure):
+    """porla_audit_challenge_req, include/porla_gpu.h: one audit of porla_audit_challenge_batch_device / _host
+    (PORLA_AUDIT_CHALLENGE_REQ_BYTES = 88)."""
+    _fields_ = [("seed", ctypes.c_uint8 * 16), ("write_step", ctypes.c_ulonglong), ("num_blocks", ctypes.c_ulonglong),
+                ("levels", ctypes.POINTER(AuditLevel)), ("d_idx64", ctypes.c_void_p), ("d_coef64", ctypes.c_void_p),
+                ("d_idx32", ctypes.c_void_p), ("d_coef32", ctypes.c_void_p), ("d_mac_idx", ctypes.c_void_p), ("d_mac_coef", ctypes.c_void_p)]
+
+
+PORLA_AUDIT_CHALLENGE_REQ_BYTES = 88
+assert ctypes.sizeof(AuditChallengeReq) == PORLA_AUDIT_CHALLENGE_REQ_BYTES
+
+
+class AuditChallengeInfo(ctypes.Structure):
+    """porla_audit_challenge_info, include/porla_gpu.h: what the host knows of a challenge when the call returns
+    (PORLA_AUDIT_CHALLENGE_INFO_BYTES = 72)."""
+    _fields_ = [("n64", ctypes.c_ulonglong), ("n32", ctypes.c_ulonglong), ("n_macs", ctypes.c_ulonglong), ("random_point", ctypes.c_ulonglong),
+                ("a_raw", ctypes.c_int), ("pad", ctypes.c_int), ("a_value", ctypes.c_uint8 * 32)]
+
+
+PORLA_AUDIT_CHALLENGE_INFO_BYTES = 72
+assert ctypes.sizeof(AuditChallengeInfo) == PORLA_AUDIT_CHALLENGE_INFO_BYTES
+
+
+class AuditScalarReq(ctypes.Structure):
+    """porla_audit_scalar_req, include/porla_gpu.h: one audit of porla_audit_complement_scalar_batch_device / _host
+    (PORLA_AUDIT_SCALAR_REQ_BYTES = 32)."""
+    _fields_ = [("seed", ctypes.c_uint8 * 16), ("write_step", ctypes.c_ulonglong), ("num_blocks", ctypes.c_ulonglong)]
+
+
+PORLA_AUDIT_SCALAR_REQ_BYTES = 32
+assert ctypes.sizeof(AuditScalarReq) == PORLA_AUDIT_SCALAR_REQ_BYTES
+
+
 def load():
     """Load the engine.  When torch is importable it is imported FIRST so that the HIP runtime the process
     ends up with is the one torch ships (both have soname libamdhip64.so.7; two runtimes in one process
@@ -224,6 +278,22 @@ def _declare(L):
     L.porla_icc_decode_host.argtypes = [u8p, sz, sz, sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), vp,
                                         ctypes.POINTER(ctypes.c_uint)]
     L.porla_icc_decode_host.restype = ctypes.c_int
+    L.porla_mac_prf_batch_device.argtypes = [u8p, ctypes.POINTER(PrfRun), sz, vp, vp]; L.porla_mac_prf_batch_device.restype = ctypes.c_int
+    L.porla_mac_prf_host.argtypes = [u8p, ctypes.POINTER(PrfRun), sz, vp]; L.porla_mac_prf_host.restype = ctypes.c_int
+    L.porla_client_prf_runs.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, sz, ctypes.POINTER(PrfRun), sz,
+                                        ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    L.porla_client_prf_runs.restype = ctypes.c_int
+    L.porla_audit_challenge_batch_device.argtypes = [ctypes.POINTER(AuditChallengeReq), sz, ctypes.POINTER(AuditChallengeInfo), vp]
+    L.porla_audit_challenge_batch_device.restype = ctypes.c_int
+    L.porla_audit_challenge_host.argtypes = [ctypes.POINTER(AuditChallengeReq), sz, ctypes.POINTER(AuditChallengeInfo)]
+    L.porla_audit_challenge_host.restype = ctypes.c_int
+    L.porla_audit_complement_scalar_batch_device.argtypes = [u8p, ctypes.POINTER(AuditScalarReq), sz, ctypes.c_int, vp, vp]
+    L.porla_audit_complement_scalar_batch_device.restype = ctypes.c_int
+    L.porla_audit_complement_scalar_host.argtypes = [u8p, ctypes.POINTER(AuditScalarReq), sz, ctypes.c_int, vp]
+    L.porla_audit_complement_scalar_host.restype = ctypes.c_int
+    L.porla_diag_audit_walk.argtypes = [vp, sz, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.POINTER(AuditLevel), ctypes.c_int, vp, vp, vp, vp,
+                                        vp, vp, ctypes.POINTER(AuditChallengeInfo)]
+    L.porla_diag_audit_walk.restype = ctypes.c_int
     L.porla_ipa_prove_batch_device.argtypes = [vp, vp, vp, sz, vp, vp]; L.porla_ipa_prove_batch_device.restype = ctypes.c_int
     L.porla_ipa_verify_batch_device.argtypes = [vp, ctypes.POINTER(IpaVerifyReq), sz, vp, vp, vp]
     L.porla_ipa_verify_batch_device.restype = ctypes.c_int
