@@ -29,6 +29,62 @@
 
 namespace porla {
 
+// ---------------------------------------------------------------- launch shapes (host, pure: FixedBase<C> and tools/fb_check.hip call these)
+// k_fb_multiples: lane groups of 16 entries per lane for small tables, 64 lanes x up to 64 entries for large ones; the scratch holds at
+// most `scratch_budget` bytes of XYZZ entries (`entry_bytes` each) per batch of (point, window) pairs
+constexpr size_t FB_SCRATCH_BUDGET = (size_t)1 << 30;
+struct FbTablePlan {
+    uint32_t H, lanes, K, runs, groups_per_wave;
+    size_t batch_pairs;
+};
+inline FbTablePlan fb_table_plan(int c, size_t pairs, size_t entry_bytes, size_t scratch_budget = FB_SCRATCH_BUDGET) {
+    FbTablePlan p;
+    const uint32_t H = 1u << (c - 1);
+    size_t batch_pairs = scratch_budget / ((size_t)H * entry_bytes);
+    if (batch_pairs < 1) batch_pairs = 1;
+    if (batch_pairs > pairs) batch_pairs = pairs;
+    const uint32_t lanes = H >= 1024 ? 64 : (H >= 16 ? H / 16 : 1);
+    uint32_t K = H / lanes;
+    if (K > 64) K = 64;
+    const uint32_t runs = H / (lanes * K);
+    const uint32_t groups_per_wave = 64 / lanes;
+    p.H = H; p.lanes = lanes; p.K = K; p.runs = runs; p.groups_per_wave = groups_per_wave; p.batch_pairs = batch_pairs;
+    return p;
+}
+
+// k_fb_commit, slices per row: enough lanes for TWO to three rounds of 256 CUs x 4 SIMDs x 3 waves -- with 196 608 (one round and a
+// third: 1024 blocks where 768 are resident) the last third ran at one wave per SIMD: 18.1-18.3 ms for 2^17 rows, 17.8 with 393 216
+// ... but not below 16 additions per lane once every SIMD has two waves anyway (131 072 rows): the fold of a slice pair costs
+// what the shorter chains save (the two-coefficient rows of the MAC batch: 0.455 -> 0.437 ms at 131 072 rows, no difference
+// at 65 536, and below that the slices win)
+inline uint32_t fb_commit_slices(size_t n_rows, size_t n_coeffs, int W) {
+    static const size_t target = 393216;
+    uint32_t S = 1;
+    while ((size_t)n_rows * S < target && S * 2 <= n_coeffs && S < 128 &&
+           !(n_rows >= 131072 && (size_t)(n_coeffs / (2 * S)) * (size_t)W < 16)) S *= 2;
+    return S;
+}
+
+// k_fb_commit_small, slices per row
+inline uint32_t fb_small_slices(size_t n_coeffs, int W) {
+    const uint32_t P = (uint32_t)(n_coeffs * (size_t)W);
+    constexpr uint32_t per_slice = 256;      // (coefficient, window) pairs per slice (512: one row 0.0615 ms, the audit 0.150 ms; 256: 0.060 / 0.142)
+    uint32_t SL = (P + per_slice - 1) / per_slice;
+    if (SL < 1) SL = 1;
+    if (SL > (uint32_t)FB_SMALL_MAX_SLICES) SL = FB_SMALL_MAX_SLICES;
+    return SL;
+}
+
+// k_fb_finish, rows per lane (the kernel's comment below gives the measurements)
+constexpr int FB_FINISH_ROWS_MAX = 4;
+constexpr size_t FB_FINISH_SPREAD = 32768;
+inline int fb_finish_rows(size_t n_rows) {
+    static const size_t spread = FB_FINISH_SPREAD;
+    if (n_rows <= spread) return 1;
+    else if (n_rows <= 2 * spread) return 2;
+    else return FB_FINISH_ROWS_MAX;
+}
+
 // ---------------------------------------------------------------- device-side inversion (Fermat, a^(p-2))
 template <class M>
 __device__ __noinline__ Fe<M> fe_inv_dev(Fe<M> a) {
@@ -477,8 +533,6 @@ k_fb_fold_quad(XYZZ<typename C::Fp>* __restrict__ partial, uint32_t n_rows, uint
 // Up to FB_FINISH_SPREAD rows (two waves per compute unit) a lane takes ONE row, up to twice that two: the chip is idle otherwise,
 // and the three products per row of the trick plus the conversions of four rows are a third of the lane's dependent chain
 // (0.078 -> 0.054 ms up to 16 384 rows, 0.057 at 32 768; at 65 536 rows one row per lane loses: 0.085 against 0.080).
-constexpr int FB_FINISH_ROWS_MAX = 4;
-constexpr size_t FB_FINISH_SPREAD = 32768;
 template <class C, int FB_FINISH_ROWS>
 __global__ void __launch_bounds__(64)
 k_fb_finish(const XYZZ<typename C::Fp>* __restrict__ partial, uint32_t n_rows, uint32_t S, uint8_t* __restrict__ out) {

@@ -77,10 +77,9 @@ int FixedBase<C>::build(const Affine<typename C::Fp>* d_base, size_t n, int wind
     const uint32_t H = 1u << (c - 1);
     const size_t pairs = n * (size_t)W;
     const size_t entries = pairs * H;
-    // scratch: at most 1 GiB of XYZZ entries per batch of (point, window) pairs
-    size_t batch_pairs = ((size_t)1 << 30) / ((size_t)H * sizeof(XYZZ<M>));
-    if (batch_pairs < 1) batch_pairs = 1;
-    if (batch_pairs > pairs) batch_pairs = pairs;
+    // scratch: at most 1 GiB of XYZZ entries per batch of (point, window) pairs; the lane groups of k_fb_multiples
+    const FbTablePlan tp = fb_table_plan(c, pairs, sizeof(XYZZ<M>));
+    const size_t batch_pairs = tp.batch_pairs;
     auto ensure = [](void** ptr, size_t* cap, size_t bytes) -> hipError_t {
         if (bytes <= *cap) return hipSuccess;
         if (*ptr) (void)hipFree(*ptr);
@@ -99,12 +98,7 @@ int FixedBase<C>::build(const Affine<typename C::Fp>* d_base, size_t n, int wind
         ProfScope ps("fb_base_powers", stream);
         hipLaunchKernelGGL((k_fb_base_powers<C>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, d_base, (uint32_t)n, c, W, pow);
     }
-    // lane groups of k_fb_multiples: 16 entries per lane for small tables, 64 lanes x up to 64 entries for large ones
-    const uint32_t lanes = H >= 1024 ? 64 : (H >= 16 ? H / 16 : 1);
-    uint32_t K = H / lanes;
-    if (K > 64) K = 64;
-    const uint32_t runs = H / (lanes * K);
-    const uint32_t groups_per_wave = 64 / lanes;
+    const uint32_t lanes = tp.lanes, K = tp.K, runs = tp.runs, groups_per_wave = tp.groups_per_wave;
     for (size_t p0 = 0; p0 < pairs; p0 += batch_pairs) {
         size_t np = pairs - p0 < batch_pairs ? pairs - p0 : batch_pairs;
         {
@@ -145,15 +139,7 @@ int FixedBase<C>::commit_device(const uint8_t* d_rows, size_t n_rows, size_t n_c
         int rcf = fence.enter(stream);
         if (rcf) return rcf;
     }
-    // slices per row: enough lanes for TWO to three rounds of 256 CUs x 4 SIMDs x 3 waves -- with 196 608 (one round and a third:
-    // 1024 blocks where 768 are resident) the last third ran at one wave per SIMD: 18.1-18.3 ms for 2^17 rows, 17.8 with 393 216
-    static const size_t target = 393216;
-    // ... but not below 16 additions per lane once every SIMD has two waves anyway (131 072 rows): the fold of a slice pair costs
-    // what the shorter chains save (the two-coefficient rows of the MAC batch: 0.455 -> 0.437 ms at 131 072 rows, no difference
-    // at 65 536, and below that the slices win)
-    uint32_t S = 1;
-    while ((size_t)n_rows * S < target && S * 2 <= n_coeffs && S < 128 &&
-           !(n_rows >= 131072 && (size_t)(n_coeffs / (2 * S)) * (size_t)W < 16)) S *= 2;
+    const uint32_t S = fb_commit_slices(n_rows, n_coeffs, W);          // slices per row
     uint32_t G = S < 64 ? S : 64;
     size_t need = n_rows * (size_t)S * sizeof(XYZZ<M>);
     if (need > partial_cap) {
@@ -186,11 +172,11 @@ int FixedBase<C>::commit_device(const uint8_t* d_rows, size_t n_rows, size_t n_c
     last_S = S;
     if (d_out) {
         ProfScope ps("fb_finish", stream);
-        static const size_t spread = FB_FINISH_SPREAD;
-        if (n_rows <= spread)
+        const int per_lane = fb_finish_rows(n_rows);
+        if (per_lane == 1)
             hipLaunchKernelGGL((k_fb_finish<C, 1>), dim3((unsigned)((n_rows + 63) / 64)), dim3(64), 0, stream,
                                (const XYZZ<M>*)partial, (uint32_t)n_rows, S, d_out);
-        else if (n_rows <= 2 * spread)
+        else if (per_lane == 2)
             hipLaunchKernelGGL((k_fb_finish<C, 2>), dim3((unsigned)((n_rows + 127) / 128)), dim3(64), 0, stream,
                                (const XYZZ<M>*)partial, (uint32_t)n_rows, S, d_out);
         else
@@ -241,11 +227,7 @@ int FixedBase<C>::commit_small(const uint8_t* const* row_ptrs, size_t n_rows, si
     if (++small_seq == 0) small_seq = 1;
     volatile uint32_t* hdr = (volatile uint32_t*)hs;
     hdr[0] = 0;
-    const uint32_t P = (uint32_t)(n_coeffs * (size_t)W);
-    constexpr uint32_t per_slice = 256;      // (coefficient, window) pairs per slice (512: one row 0.0615 ms, the audit 0.150 ms; 256: 0.060 / 0.142)
-    uint32_t SL = (P + per_slice - 1) / per_slice;
-    if (SL < 1) SL = 1;
-    if (SL > (uint32_t)FB_SMALL_MAX_SLICES) SL = FB_SMALL_MAX_SLICES;
+    const uint32_t SL = fb_small_slices(n_coeffs, W);
     int rc = fence.enter(stream);
     if (rc) return rc;
     {
