@@ -148,6 +148,9 @@ __global__ void k_points_to_mont(const uint8_t* __restrict__ in, Affine<typename
     Fe<M> x, y;
     load_be256(x.v, in + (size_t)i * 64);
     load_be256(y.v, in + (size_t)i * 64 + 32);
+    // (The product below would reduce an unreduced a < 2^256 by itself -- (a k + m p) / R < 2p for k < p, then its one subtraction;
+    // on secp256k1 a - p < p -- so these two loops are redundant.  The kernel is bound by its 128 MB of traffic, not by them:
+    // without them 38.5 -> 37.2 us against 37.7 us for this same code in another build; profiles/README.md, measured and dropped.)
     fe_reduce_plain<M>(x.v, 6);
     fe_reduce_plain<M>(y.v, 6);
     if constexpr (F30) {
@@ -209,7 +212,8 @@ k_scalar_or(const uint8_t* __restrict__ scalars, uint32_t n, uint32_t* __restric
 // Pass B  k_partition_sort: a block owns one (window, partition) = 2^lowbits buckets (1024 for c <= 18).  Its waves walk
 //         that partition's run in every tile with COALESCED loads (a run is ~TILE / P items = 512 B at c = 16), twice:
 //         first to count per bucket in LDS (-> counts, starts; the partition's slot range comes from ONE cursor atomic
-//         per block), then to place the point indices with LDS cursors.
+//         per block), then to place the point indices with LDS cursors.  Up to 256 tiles the second walk takes the first 128
+//         items of every run from registers the first one left them in (k_partition_sort's HOLD form): one walk over global memory.
 constexpr int TILE = 4096;
 constexpr int TILE_THREADS = 1024;
 constexpr int TILE_SPT = TILE / TILE_THREADS;  // scalars per thread
@@ -267,6 +271,11 @@ static inline SortFrontPlan sort_front_plan(size_t n, bool glv, int c, int W) {
     if (pl.wg > (unsigned)W) pl.wg = (unsigned)W;
     return pl;
 }
+// Which form of k_partition_sort a plan takes (sort_launch below, the one launch site of msm_launch and tools/sort_check.hip): a wave
+// walks T / 16 tiles, and up to SORT_HOLD_TILES of them it holds in registers between the count and the place (one walk over global
+// memory); above that -- more than 2^20 pairs, the <= 2^22-pair ranges of msm_host_multi -- the kernel that walks twice.
+constexpr int SORT_HOLD_TILES = 16;            // tiles per wave whose run heads stay in registers: 2 x 16 VGPRs
+static inline bool sort_holds_runs(const SortFrontPlan& pl) { return pl.T_tiles <= 16u * SORT_HOLD_TILES; }
 
 // exclusive scan of one value per thread over a 1024-thread block; returns the exclusive prefix, *total = block sum
 __device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t* wsum /* 16 */, uint32_t* total) {
@@ -442,8 +451,13 @@ k_digits_partition(const uint8_t* __restrict__ scalars, uint32_t n, int c, int W
 }
 
 // grid = W * P blocks of 1024 threads (16 waves; wave v takes tiles v, v+16, ...).  STAGE_CAP / MAX_LOW: the staging area and the
-// bucket counters in LDS -- the full size (one block per compute unit) or half of each (two: sort_front_plan)
-template <int STAGE_CAP, int MAX_LOW>
+// bucket counters in LDS -- the full size (one block per compute unit) or half of each (two: sort_front_plan).
+// HOLD (T <= 16 SORT_HOLD_TILES, sort_holds_runs): the wave keeps the first 128 items of every run of its tiles in registers from the
+// count to the place -- one walk over global memory instead of two, and all of its loads in flight at once (bounds, then items)
+// instead of tile by tile.  Only what a run holds beyond 128 items is read again, in both phases.
+// (The half-size form is there to have two blocks per compute unit -- eight waves per SIMD, at most 64 VGPRs: the HOLD form takes
+// 63 without a spill, tools/kernel_meta.py --grep k_partition_sort.)
+template <int STAGE_CAP, int MAX_LOW, bool HOLD>
 __global__ void __launch_bounds__(1024)
 k_partition_sort(const uint32_t* __restrict__ tile_items, const uint16_t* __restrict__ tile_off, uint32_t T, uint32_t tile_cap,
                  int c, int lowbits, uint32_t* __restrict__ counts, uint32_t* __restrict__ starts,
@@ -455,7 +469,9 @@ k_partition_sort(const uint32_t* __restrict__ tile_items, const uint16_t* __rest
     const int P = 1 << (c - 1 - lowbits);
     const uint32_t nlow = 1u << lowbits;
     const uint32_t w = blockIdx.x / P, p = blockIdx.x % P;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    // (HOLD: the wave number as a scalar, so that tile numbers, run bounds and the branches on them are scalar too)
+    const uint32_t wv = HOLD ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)) : tid >> 6;
     const uint32_t lowmask = nlow - 1;
     for (uint32_t i = tid; i < nlow; i += 1024) cnt[i] = 0;
     __syncthreads();
@@ -490,7 +506,58 @@ k_partition_sort(const uint32_t* __restrict__ tile_items, const uint16_t* __rest
             atomicAdd(&cnt[low], 1u);
         }
     };
-    {
+    // HOLD: the run heads of tile wv + 16 k are held_a[k], held_b[k], with HELD_NONE (no item: an item has at most 26 bits) in the
+    // lanes behind the run's end -- the word says whether the lane is active, no register per tile has to say it.  The run's bounds
+    // (16 bits each, the same in every lane) are one scalar per tile: lane k fetches those of tile wv + 16 k, one pair of loads for
+    // all of the wave's tiles.  All indices below are compile-time constants after unrolling.
+    constexpr int D = HOLD ? SORT_HOLD_TILES : 1;
+    constexpr uint32_t HELD_NONE = 0xffffffffu;
+    uint32_t held_a[D], held_b[D];
+    uint32_t bounds = 0;                   // lane k < D: lo | hi << 16 of the run in tile wv + 16 k
+    unsigned long long long_runs = 0;      // bit k: that run holds more than 128 items
+    // what a run holds beyond its held head, chunk by chunk from global memory (skewed digits, the sparse top window) -- in both
+    // phases, and rolled: the common case has no such run and pays one scalar test
+    auto beyond_held = [&](auto&& chunk) {
+        for (unsigned long long m = long_runs; m; m &= m - 1) {
+            const int k = __ffsll((long long)m) - 1;
+            const uint32_t lohi = (uint32_t)__builtin_amdgcn_readlane((int)bounds, k), hi = lohi >> 16, t = wv + 16 * (uint32_t)k;
+            const uint32_t* it = tile_items + ((size_t)w * T + t) * tile_cap;
+            for (uint32_t i0 = (lohi & 0xffffu) + 128; i0 < hi; i0 += 64) {
+                const bool active = i0 + lane < hi;
+                chunk(t, active, active ? it[i0 + lane] : 0u);
+            }
+        }
+    };
+    if constexpr (HOLD) {
+        if (lane < (uint32_t)D) {
+            uint32_t lo, hi;
+            run_bounds(wv + 16 * lane, lo, hi);      // (0, 0) from tile T on
+            bounds = lo | (hi << 16);
+        }
+        long_runs = __ballot((bounds >> 16) - (bounds & 0xffffu) > 128u);
+#pragma unroll
+        for (int k = 0; k < D; k++) {
+            // Loads without a branch, so that all 2 D of them are issued back to back: a lane behind the run's end reads the run's
+            // last item again (a line the wave fetches anyway) and drops it.  An empty run reads word 0 of its tile, a tile from T
+            // on word 0 of tile T - 1: always inside tile_items (T >= 1, hi <= tile_cap).
+            const uint32_t lohi = (uint32_t)__builtin_amdgcn_readlane((int)bounds, k);
+            const uint32_t lo = lohi & 0xffffu, hi = lohi >> 16, len = hi - lo, last = hi ? hi - 1 : 0u;
+            const uint32_t t = wv + 16 * k < T ? wv + 16 * k : T - 1;
+            const uint32_t* it = tile_items + ((size_t)w * T + t) * tile_cap;
+            const uint32_t ia = lo + lane < last ? lo + lane : last, ib = lo + 64 + lane < last ? lo + 64 + lane : last;
+            const uint32_t va = it[ia], vb = it[ib];
+            // (lane against the run's length, a scalar: no register per tile lives on for this)
+            held_a[k] = lane < len ? va : HELD_NONE;
+            held_b[k] = lane + 64 < len ? vb : HELD_NONE;
+        }
+#pragma unroll
+        for (int k = 0; k < D; k++) {
+            // (a chunk with no active lane is never counted: its lanes would share the bucket 0xffffffff)
+            if (__ballot(held_a[k] != HELD_NONE)) count_chunk(held_a[k] != HELD_NONE, held_a[k]);
+            if (__ballot(held_b[k] != HELD_NONE)) count_chunk(held_b[k] != HELD_NONE, held_b[k]);
+        }
+        beyond_held([&](uint32_t, bool active, uint32_t item) { count_chunk(active, item); });
+    } else {
         uint32_t lo1, hi1, lo2, hi2, a1, b1;
         run_bounds(wv, lo1, hi1);
         run_bounds(wv + 16, lo2, hi2);
@@ -535,43 +602,78 @@ k_partition_sort(const uint32_t* __restrict__ tile_items, const uint16_t* __rest
         }
     }
     __syncthreads();
-    uint32_t lo1, hi1, lo2, hi2, a1, b1;
-    run_bounds(wv, lo1, hi1);
-    run_bounds(wv + 16, lo2, hi2);
-    run_items(wv, lo1, hi1, a1, b1);
-    for (uint32_t t = wv; t < T; t += 16) {
-        const uint32_t lo = lo1, hi = hi1, a = a1, b = b1;
-        lo1 = lo2; hi1 = hi2;
-        run_bounds(t + 32, lo2, hi2);
-        run_items(t + 16, lo1, hi1, a1, b1);
-        const uint32_t* it = tile_items + ((size_t)w * T + t) * tile_cap;
-        for (uint32_t i0 = lo; i0 < hi; i0 += 64) {
-            const bool active = i0 + lane < hi;
-            const uint32_t item = i0 == lo ? a : (i0 == lo + 64 ? b : (active ? it[i0 + lane] : 0u));
-            const uint32_t low = active ? (item & lowmask) : 0xffffffffu;
-            const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)low);
-            const unsigned long long same = __ballot(low == first);
-            uint32_t pos = 0;
-            if (__popcll(same) >= 8) {
-                const uint32_t leader = (uint32_t)(__ffsll((long long)same) - 1);
-                uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(&cnt[first], (uint32_t)__popcll(same));
-                base = __shfl(base, (int)leader, 64);
-                if (low == first) pos = base + (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
-                else if (active) pos = atomicAdd(&cnt[low], 1u);
-            } else if (active) {
-                pos = atomicAdd(&cnt[low], 1u);
-            }
-            if (active) {
-                const uint32_t val = (t * tile_cap + (item >> (lowbits + 1))) | (((item >> lowbits) & 1u) << 31);
-                if (staged) stage[pos - base_sh] = val;
-                else entries[pos] = val;
+    auto place_chunk = [&](uint32_t t, bool active, uint32_t item) {
+        const uint32_t low = active ? (item & lowmask) : 0xffffffffu;
+        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)low);
+        const unsigned long long same = __ballot(low == first);
+        uint32_t pos = 0;
+        if (__popcll(same) >= 8) {
+            const uint32_t leader = (uint32_t)(__ffsll((long long)same) - 1);
+            uint32_t base = 0;
+            if (lane == leader) base = atomicAdd(&cnt[first], (uint32_t)__popcll(same));
+            base = __shfl(base, (int)leader, 64);
+            if (low == first) pos = base + (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
+            else if (active) pos = atomicAdd(&cnt[low], 1u);
+        } else if (active) {
+            pos = atomicAdd(&cnt[low], 1u);
+        }
+        if (active) {
+            const uint32_t val = (t * tile_cap + (item >> (lowbits + 1))) | (((item >> lowbits) & 1u) << 31);
+            if (staged) stage[pos - base_sh] = val;
+            else entries[pos] = val;
+        }
+    };
+    if constexpr (HOLD) {
+        // (the items are all that is kept from the count: what was derived from them there -- the bucket, the active flag -- is
+        // one instruction each to derive again and would double the registers held if the compiler carried it over)
+#pragma unroll
+        for (int k = 0; k < D; k++) asm volatile("" : "+v"(held_a[k]), "+v"(held_b[k]));
+#pragma unroll
+        for (int k = 0; k < D; k++) {
+            if (__ballot(held_a[k] != HELD_NONE)) place_chunk(wv + 16 * k, held_a[k] != HELD_NONE, held_a[k]);
+            if (__ballot(held_b[k] != HELD_NONE)) place_chunk(wv + 16 * k, held_b[k] != HELD_NONE, held_b[k]);
+        }
+        beyond_held(place_chunk);
+    } else {
+        uint32_t lo1, hi1, lo2, hi2, a1, b1;
+        run_bounds(wv, lo1, hi1);
+        run_bounds(wv + 16, lo2, hi2);
+        run_items(wv, lo1, hi1, a1, b1);
+        for (uint32_t t = wv; t < T; t += 16) {
+            const uint32_t lo = lo1, hi = hi1, a = a1, b = b1;
+            lo1 = lo2; hi1 = hi2;
+            run_bounds(t + 32, lo2, hi2);
+            run_items(t + 16, lo1, hi1, a1, b1);
+            const uint32_t* it = tile_items + ((size_t)w * T + t) * tile_cap;
+            for (uint32_t i0 = lo; i0 < hi; i0 += 64) {
+                const bool active = i0 + lane < hi;
+                const uint32_t item = i0 == lo ? a : (i0 == lo + 64 ? b : (active ? it[i0 + lane] : 0u));
+                place_chunk(t, active, item);
             }
         }
     }
     if (staged) {
         __syncthreads();
         for (uint32_t i = tid; i < total_sh; i += 1024) entries[base_sh + i] = stage[i];
+    }
+}
+
+// The one launch of k_partition_sort: the instantiation a plan takes (half- or full-size LDS arrays; run heads held in registers or
+// walked twice, sort_holds_runs) on W * P blocks.
+static inline void sort_launch(const SortFrontPlan& pl, int c, int W, hipStream_t stream, const uint32_t* tile_items, const uint16_t* tile_off,
+                               uint32_t* counts, uint32_t* starts, uint32_t* entries, uint32_t* cursor) {
+    const dim3 grid((unsigned)(W * pl.P)), block(1024);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, tile_items, tile_off, pl.T_tiles, pl.tile_cap, c, pl.lowbits, counts, starts, entries,
+                           cursor);
+    };
+    const bool hold = sort_holds_runs(pl);
+    if (pl.sort_half) {
+        if (hold) go(k_partition_sort<SORT_STAGE_CAP / 2, SORT_MAX_LOW / 2, true>);
+        else go(k_partition_sort<SORT_STAGE_CAP / 2, SORT_MAX_LOW / 2, false>);
+    } else {
+        if (hold) go(k_partition_sort<SORT_STAGE_CAP, SORT_MAX_LOW, true>);
+        else go(k_partition_sort<SORT_STAGE_CAP, SORT_MAX_LOW, false>);
     }
 }
 

@@ -246,8 +246,7 @@ static int msm_launch(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_
     // the launch shape of the sort front: partition width, half-size partitions, blocks per tile (msm.hip.h:sort_front_plan)
     const SortFrontPlan sf = sort_front_plan(n, glv, c, W);
     const uint32_t tile_cap = sf.tile_cap, T_tiles = sf.T_tiles;
-    const int lowbits = sf.lowbits, P = sf.P;
-    const bool sort_half = sf.sort_half;
+    const int lowbits = sf.lowbits;
     const uint32_t B = 1u << (c - 1);
     const size_t nb = (size_t)W * B;
     const uint32_t n32 = (uint32_t)n;
@@ -313,14 +312,8 @@ static int msm_launch(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_
     }
     {
         ProfScope ps("partition_sort", stream);
-        if (sort_half)
-            hipLaunchKernelGGL((k_partition_sort<SORT_STAGE_CAP / 2, SORT_MAX_LOW / 2>), dim3((unsigned)(W * P)), dim3(1024), 0, stream,
-                               (const uint32_t*)ws->keys.p, (const uint16_t*)ws->tile_off.p, T_tiles, tile_cap, c, lowbits,
-                               (uint32_t*)ws->counts.p, (uint32_t*)ws->starts.p, (uint32_t*)ws->entries.p, ctrl);
-        else
-            hipLaunchKernelGGL((k_partition_sort<SORT_STAGE_CAP, SORT_MAX_LOW>), dim3((unsigned)(W * P)), dim3(1024), 0, stream,
-                               (const uint32_t*)ws->keys.p, (const uint16_t*)ws->tile_off.p, T_tiles, tile_cap, c, lowbits,
-                               (uint32_t*)ws->counts.p, (uint32_t*)ws->starts.p, (uint32_t*)ws->entries.p, ctrl);
+        sort_launch(sf, c, W, stream, (const uint32_t*)ws->keys.p, (const uint16_t*)ws->tile_off.p, (uint32_t*)ws->counts.p,
+                    (uint32_t*)ws->starts.p, (uint32_t*)ws->entries.p, ctrl);
     }
     {
         ProfScope ps("size_order", stream);

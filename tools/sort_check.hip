@@ -160,12 +160,7 @@ static int run(const std::vector<uint32_t>& in, const char* out_path) {
         else
             hipLaunchKernelGGL((k_digits_partition<C, false>), dim3(T, pl.wg), dim3(TILE_THREADS), 0, 0, (const uint8_t*)d_scalars, n, c, W, pl.lowbits,
                                d_items, (uint16_t*)d_off, d_ctrl);
-        if (pl.sort_half)
-            hipLaunchKernelGGL((k_partition_sort<SORT_STAGE_CAP / 2, SORT_MAX_LOW / 2>), dim3((unsigned)(W * pl.P)), dim3(1024), 0, 0,
-                               (const uint32_t*)d_items, (const uint16_t*)d_off, T, pl.tile_cap, c, pl.lowbits, d_counts, d_starts, d_entries, d_ctrl);
-        else
-            hipLaunchKernelGGL((k_partition_sort<SORT_STAGE_CAP, SORT_MAX_LOW>), dim3((unsigned)(W * pl.P)), dim3(1024), 0, 0,
-                               (const uint32_t*)d_items, (const uint16_t*)d_off, T, pl.tile_cap, c, pl.lowbits, d_counts, d_starts, d_entries, d_ctrl);
+        sort_launch(pl, c, W, 0, (const uint32_t*)d_items, (const uint16_t*)d_off, d_counts, d_starts, d_entries, d_ctrl);
         CK(hipGetLastError());
         CK(hipDeviceSynchronize());
         for (auto& a : areas) {
