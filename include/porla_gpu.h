@@ -895,6 +895,48 @@ int porla_icc_decode_batch_device(const porla_icc_decode_req *reqs, size_t k, si
 int porla_icc_decode_host(const uint8_t *rows, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form,
                           const unsigned long long *write_steps, uint8_t *out, unsigned int *bad);
 
+/* ---- the ICC MAC decode: the coded MAC rows of a level back to its per-block MACs, for K independent levels in ONE asynchronous call ----
+ * The MAC-side twin of the ICC decode: a block recovered by porla_icc_decode_batch_device counts only once it has been checked against
+ * its MAC, alpha * commit(block) + PRF * h, and the per-block MACs of a level exist only in coded form (mac_x / mac_y: the MAC network
+ * over MAC_U plus the complements).  Output row i is input i of the network whose output is d_macs - d_sub -- the inverse of
+ * porla_icc_mac_encode_device with part = 0 and equally of the chain of porla_icc_mac_mix_device calls that builds a level.  The stages
+ * run from log2 n_rows down to 1 as (A, B) <- (A + B, vi^-1 (A - B)), vi the integer (w^e mod p_icc) mod q the encode multiplies by and
+ * vi^-1 its inverse mod the group order q; one factor n_rows^-1 mod q per row is applied at the end.  Request a is one level:
+ *   d_macs         n_rows points, 64 bytes X||Y big-endian affine each (reduced as SetBytes does), 64 zero bytes = infinity
+ *   d_out          n_rows points in the same form
+ *   d_write_steps  n_rows values, or NULL: output position i is additionally multiplied by wt_i^-1 mod q, wt_i =
+ *                  (w^reverse_bits(step_i % N, log2 N) mod p_icc) mod q, N = n_total -- the inverse of porla_icc_mac_scale_host and of
+ *                  the Y half's init scaling.  n_rows^-1 wt_i^-1 mod q is computed on the device (one division-step inversion per
+ *                  row) and applied as ONE scalar multiplication per row
+ *   d_sub          n_rows points, or NULL: subtracted from d_macs row by row before the network.  The server rebuild batches leave
+ *                  mac_x[j] = network(MAC_U)[j] + comp[j]: with d_sub = comp the output is MAC_U, byte for byte
+ * It takes one complete half and is no erasure decoder: w has order N and Y = X at every CRebuild, so most n-row subsets of the 2 n
+ * rows of a level are rank-deficient.
+ * n_rows: a power of two, 2 .. 2^16, <= n_total.  n_total: a power of two <= 2^16 that fixes w for the write steps (and which resident
+ * table is used: the twiddles of the network itself do not depend on it).  curve: 0 (BN254) or 1 (secp256k1).
+ * Contract: that of the other batches -- asynchronous on hip_stream, no host wait, no side stream; the launch sequence depends on
+ * n_rows, not on k (the upload, the rows' scalars, the load, log2 n_rows stage launches over the K tables of one work array, the
+ * close); the inverse twiddles as plain scalars and their digit codes are derived per (n_total, curve) from the data decode's table of
+ * inverses mod q, read under the ICC workspace's lock and fence.
+ * PORLA_ERR_ARG (with a message, before the device is touched): NULL reqs with k > 0; NULL d_macs or d_out; d_macs, d_out or d_sub not
+ * 16-byte aligned, d_write_steps not 8-byte aligned; a bad n_rows, n_total or curve; an output overlapping any request's input, sub or
+ * output; more than 65535 requests; a byte size that overflows.  k = 0 returns 0; valid arguments without a device:
+ * PORLA_ERR_NO_DEVICE.  porla_icc_mac_decode_host is one level from host memory (upload, the same kernels, download; it waits).
+ * tools/bench_icc_mac_decode.py times the decode beside porla_icc_mac_encode_device on the same rows in the same run, every output
+ * byte compared with the encode's input (profiles/r20_a_mac_decode.jsonl, DESIGN s4: one level of 2^15 in 6.3 ms, 1.15x the encode;
+ * 8 levels in 50 ms, 1.16x; 64 levels of 2^10 in 9.6 ms, 0.055x the 64 encode calls). */
+#define PORLA_ICC_MAC_DECODE_REQ_BYTES 32   /* sizeof(porla_icc_mac_decode_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    const void *d_macs;
+    void *d_out;
+    const unsigned long long *d_write_steps;
+    const void *d_sub;
+} porla_icc_mac_decode_req;
+int porla_icc_mac_decode_batch_device(const porla_icc_mac_decode_req *reqs, size_t k, size_t n_rows, size_t n_total, int curve,
+                                      void *hip_stream);
+int porla_icc_mac_decode_host(const uint8_t *macs, size_t n_rows, size_t n_total, int curve, const unsigned long long *write_steps,
+                              const uint8_t *sub, uint8_t *out);
+
 /* ---- AES on the device: the MAC PRF of the client writes, the audit challenge from its seed, the client's complement scalar ----
  * These calls PRODUCE the buffers the batches above consume (d_prf; d_idx* / d_coef* / d_mac_*; the 32-byte scalars of
  * porla_kzg_complement_batch_device or of a one-point fixed base) and change none of them.  Both uses are standard AES-128

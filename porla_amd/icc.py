@@ -4,7 +4,7 @@ C ABI (include/porla_gpu.h: porla_icc_encode_*).  Rows are in the reference's ow
 little-endian chunks in (utils.h:353-364), 64-byte little-endian values mod LCM out (utils.h:473-517)."""
 import ctypes
 
-from .loader import IccDecodeReq, ServerRebuildReq, UpdateReq, lib
+from .loader import IccDecodeReq, IccMacDecodeReq, ServerRebuildReq, UpdateReq, lib
 
 CURVE = {"bn254": 0, "secp256k1": 1}
 NUM_CHUNKS = 128  # config.hpp:22
@@ -267,3 +267,33 @@ def decode_host(rows, n_rows, n_cols, n_total, curve="bn254", form="exact", writ
     _check(lib.porla_icc_decode_host(bytes(rows), n_rows, n_cols, n_total, CURVE[curve], DECODE_FORM[form], steps,
                                      ctypes.cast(out, ctypes.c_void_p), ctypes.byref(bad) if want_bad else None))
     return out.raw, (bad.value if want_bad else None)
+
+
+# ---- the ICC MAC decode: the coded MAC rows of K levels back to their per-block MACs in one asynchronous call (include/porla_gpu.h:
+# porla_icc_mac_decode_batch_device) ----
+def mac_decode_requests(reqs):
+    """a ctypes array of porla_icc_mac_decode_req from per-level tuples (d_macs, d_out, d_write_steps or 0, d_sub or 0): device
+    addresses as integers"""
+    arr = (IccMacDecodeReq * max(len(reqs), 1))()
+    for i, r in enumerate(reqs):
+        if len(r) != 4:
+            raise ValueError("mac_decode_batch_device: request %d has %d fields, want 4" % (i, len(r)))
+        arr[i] = IccMacDecodeReq(*[(x or None) for x in r])
+    return arr
+
+
+def mac_decode_batch_device(reqs, n_rows, n_total, curve, stream=0):
+    """the inverse of the MAC network on len(reqs) levels of n_rows 64-byte affine points in ONE asynchronous call on `stream`: output
+    row i is input i of the network whose output is d_macs - d_sub; with d_write_steps position i is also multiplied by wt_i^-1 mod q.
+    `reqs`: tuples as mac_decode_requests takes them; curve: "bn254" or "secp256k1"."""
+    arr = mac_decode_requests(reqs)
+    _check(lib.porla_icc_mac_decode_batch_device(arr, len(reqs), n_rows, n_total, CURVE[curve], ctypes.c_void_p(stream)))
+
+
+def mac_decode_host(macs, n_rows, n_total, curve="bn254", write_steps=None, sub=None):
+    """one level from host memory: n_rows 64-byte affine points in (and optionally n_rows to subtract), n_rows out"""
+    out = ctypes.create_string_buffer(64 * n_rows)
+    steps = (ctypes.c_ulonglong * n_rows)(*write_steps) if write_steps is not None else None
+    _check(lib.porla_icc_mac_decode_host(bytes(macs), n_rows, n_total, CURVE[curve], steps, bytes(sub) if sub is not None else None,
+                                         ctypes.cast(out, ctypes.c_void_p)))
+    return out.raw

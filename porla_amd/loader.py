@@ -97,6 +97,16 @@ PORLA_ICC_DECODE_REQ_BYTES = 32
 assert ctypes.sizeof(IccDecodeReq) == PORLA_ICC_DECODE_REQ_BYTES
 
 
+class IccMacDecodeReq(ctypes.Structure):
+    """porla_icc_mac_decode_req, include/porla_gpu.h: one level of porla_icc_mac_decode_batch_device
+    (PORLA_ICC_MAC_DECODE_REQ_BYTES = 32)."""
+    _fields_ = [("d_macs", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("d_write_steps", ctypes.c_void_p), ("d_sub", ctypes.c_void_p)]
+
+
+PORLA_ICC_MAC_DECODE_REQ_BYTES = 32
+assert ctypes.sizeof(IccMacDecodeReq) == PORLA_ICC_MAC_DECODE_REQ_BYTES
+
+
 class PrfRun(ctypes.Structure):
     """porla_prf_run, include/porla_gpu.h: count triples (level, index0 + t, time0 + t * time_stride) of the MAC PRF
     (PORLA_PRF_RUN_BYTES = 32)."""
@@ -278,6 +288,10 @@ def _declare(L):
     L.porla_icc_decode_host.argtypes = [u8p, sz, sz, sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), vp,
                                         ctypes.POINTER(ctypes.c_uint)]
     L.porla_icc_decode_host.restype = ctypes.c_int
+    L.porla_icc_mac_decode_batch_device.argtypes = [ctypes.POINTER(IccMacDecodeReq), sz, sz, sz, ctypes.c_int, vp]
+    L.porla_icc_mac_decode_batch_device.restype = ctypes.c_int
+    L.porla_icc_mac_decode_host.argtypes = [u8p, sz, sz, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), u8p, vp]
+    L.porla_icc_mac_decode_host.restype = ctypes.c_int
     L.porla_mac_prf_batch_device.argtypes = [u8p, ctypes.POINTER(PrfRun), sz, vp, vp]; L.porla_mac_prf_batch_device.restype = ctypes.c_int
     L.porla_mac_prf_host.argtypes = [u8p, ctypes.POINTER(PrfRun), sz, vp]; L.porla_mac_prf_host.restype = ctypes.c_int
     L.porla_client_prf_runs.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, sz, ctypes.POINTER(PrfRun), sz,

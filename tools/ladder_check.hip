@@ -25,6 +25,13 @@
 //       ensure_mac_codes does, and append its n / 32 entries of MACQ_CODES_STRIDE 16-bit words.
 //         stage30, stage30_quad, stage30_oct                          per-butterfly scalars; total <= rows / 2 butterflies
 //         stage30_uniform, stage30_quad_uniform, stage30_oct_uniform  one table, total = n / 2, the launch rules of mac_stages
+//   inverse stage forms (icc_mac_decode.hip.h: k_imd_stage_quad, (A, B) -> (A + B, sc (A - B)) on the rows k, k + 2^(s-1)): the same
+//       file layout as the stage forms, the table IN PLACE OF THE INVERSE TWIDDLES; s >= 2 (stage 1 has no ladder)
+//         istage1_quad                                                k_imd_stage1_quad: (A, B) -> (A + B, A - B) on the rows 2 t, 2 t + 1;
+//                                                                     s = 1, total = rows / 2, the table is not read
+//         istage_quad                                                 per-butterfly scalars; total <= rows / 2 butterflies
+//         istage_quad_uniform                                         whole tables, total = rows / 2, n >> s >= 16; the digit codes of
+//                                                                     the table are made first and appended as for the stage forms
 //   by-value forms: out[i] = wt * in[i] for i < n; `rows` >= n input rows follow the header (32 words each: memory form; 16 words:
 //       64-byte big-endian affine), entries = 0.  Output: `rows` rows of 32 words, filled with 0xA5 bytes before the launch.  The
 //       launches of a file have a slice each of one input and one output buffer and go out over a few streams, waited for once.
@@ -32,6 +39,7 @@
 //         affine), load30_quad_work (k_mac_load30_quad<C, true>, memory form)
 // Every launch is checked against the rows and entries its file holds before it runs: a malformed file is refused, not launched.
 #include "mac_fft.hip.h"
+#include "icc_mac_decode.hip.h"
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -48,14 +56,16 @@ enum Op {
     OP_DIGIT, OP_WNAF, OP_SPLIT,
     OP_STAGE, OP_STAGE_U, OP_QUAD, OP_QUAD_U, OP_OCT, OP_OCT_U,
     OP_SCALE, OP_LOAD_WT, OP_LOAD_QUAD, OP_LOAD_QUAD_WORK,
+    OP_IQUAD, OP_IQUAD_U, OP_ISTAGE1,
     OP_COUNT
 };
 static const char* const OP_NAMES[OP_COUNT] = {
     "mac_signed_digit", "mac_wnaf5_step", "glv_split",
     "stage30", "stage30_uniform", "stage30_quad", "stage30_quad_uniform", "stage30_oct", "stage30_oct_uniform",
-    "scale30", "load30_wt", "load30_quad", "load30_quad_work"};
+    "scale30", "load30_wt", "load30_quad", "load30_quad_work",
+    "istage_quad", "istage_quad_uniform", "istage1_quad"};
 static bool op_is_recoder(int op) { return op <= OP_SPLIT; }
-static bool op_is_value(int op) { return op >= OP_SCALE; }
+static bool op_is_value(int op) { return op >= OP_SCALE && op <= OP_LOAD_QUAD_WORK; }
 static bool op_is_uniform_stage(int op) { return op == OP_STAGE_U || op == OP_QUAD_U || op == OP_OCT_U; }
 static bool op_affine_in(int op) { return op == OP_LOAD_WT || op == OP_LOAD_QUAD; }
 
@@ -161,6 +171,12 @@ static int parse_launches(int op, const std::vector<uint32_t>& in, std::vector<L
             if ((1u << logn) != l.n || l.s < 1 || (int)l.s > logn) return refuse("n must be a power of two and 1 <= s <= log2 n");
             if (l.rows % l.n != 0 || l.entries != l.n) return refuse("rows must be whole tables of n rows and entries = n");
             if (l.total == 0 || l.total > l.rows / 2) return refuse("total must be 1 .. rows / 2");
+            if (op == OP_IQUAD || op == OP_IQUAD_U) {
+                if (l.s < 2) return refuse("stage 1 of the decode has no ladder (istage1_quad)");
+                if (op == OP_IQUAD_U && (l.total != l.rows / 2 || !imd_stage_uniform(l.n, (int)l.s)))
+                    return refuse("the wave-uniform inverse stage runs on whole tables, total = rows / 2, n >> s >= 16");
+            }
+            if (op == OP_ISTAGE1 && (l.s != 1 || l.total != l.rows / 2)) return refuse("istage1_quad runs stage 1 on every pair: s = 1, total = rows / 2");
             if (op_is_uniform_stage(op)) {
                 // the launch rules of mac_stages for the wave-uniform forms
                 if (l.rows != l.n || l.total != l.n / 2 || l.n < 128) return refuse("a wave-uniform form runs on one table of n >= 128 rows, total = n / 2");
@@ -245,6 +261,7 @@ static int run_launches(int op, const std::vector<uint32_t>& in, std::vector<uin
     CK(hipMalloc(&d_tws, max_entries * 32));
     CK(hipMalloc(&d_codes, codes_bytes));
     mac_lds_attributes<C>();
+    imd_lds_attributes<C>();
     for (const Launch& l : ls) {
         XYZZ<M>* work = reinterpret_cast<XYZZ<M>*>(d_work);
         const uint32_t n = l.n, total = l.total;
@@ -254,13 +271,17 @@ static int run_launches(int op, const std::vector<uint32_t>& in, std::vector<uin
         CK(hipMemcpy(d_tws, in.data() + l.at_tws, (size_t)l.entries * 32, hipMemcpyHostToDevice));
         const uint32_t* tws = d_tws;
         const uint16_t* none = nullptr;
-        if (op_is_uniform_stage(op)) {                                 // the digit codes of the table, as ensure_mac_codes makes them
+        if (op_is_uniform_stage(op) || op == OP_IQUAD_U) {             // the digit codes of the table, as ensure_mac_codes makes them
             with_codes = true;
             const uint32_t entries = n >> MACQ_CODES_EXP_SHIFT;
             CK(hipMemset(d_codes, 0xA5, codes_bytes));
             hipLaunchKernelGGL((k_mac_wnaf_codes<C>), dim3((entries + 63) / 64), dim3(64), 0, 0, tws, entries, d_codes);
         }
-        if (op == OP_OCT_U)
+        if (op == OP_ISTAGE1)
+            hipLaunchKernelGGL((k_imd_stage1_quad<C>), dim3((total + 63) / 64), dim3(256), 0, 0, work, l.rows);
+        else if (op == OP_IQUAD || op == OP_IQUAD_U)
+            imd_launch_stage<C>(op == OP_IQUAD_U, work, tws, n, s, d_codes, total, 0);
+        else if (op == OP_OCT_U)
             hipLaunchKernelGGL((k_mac_stage30_oct_uniform<C>), dim3(total / MACO_BF), dim3(8 * MACO_BF), maco_lds_bytes<C>(), 0, work, tws, n, s, d_codes);
         else if (op == OP_QUAD_U)
             hipLaunchKernelGGL((k_mac_stage30_quad<C, true>), dim3((total + MACQ_BF - 1) / MACQ_BF), dim3(4 * MACQ_BF), macq_lds_bytes<C>(), 0, work, tws, n, s,
