@@ -937,6 +937,67 @@ int porla_icc_mac_decode_batch_device(const porla_icc_mac_decode_req *reqs, size
 int porla_icc_mac_decode_host(const uint8_t *macs, size_t n_rows, size_t n_total, int curve, const unsigned long long *write_steps,
                               const uint8_t *sub, uint8_t *out);
 
+/* ---- verified retrieval: the coded rows of a level checked against its stored MAC rows, then decoded, for K levels in ONE call ----
+ * "Give me this level back and tell me it is authentic" without the MAC decode.  The data network works mod LCM = p_icc q with integer
+ * multipliers vi < p_icc and the MAC network multiplies by the same vi reduced mod q, so coded row j of an exact half, reduced mod q,
+ * is the Z_q network of the chunks, and the half's MAC row j is alpha * Commit(row_j mod q) + s_j * h with s_j the PRF value of the
+ * complement the client currently holds for that row.  Every coded row is therefore checked against its stored MAC row directly -- KZG:
+ * one polynomial evaluation per row (the client knows tau) and a two-coefficient fixed-base commitment; IPA: one 128-coefficient
+ * commitment plus one multiple of the hiding base -- and no group-element network runs.  One altered symbol fails exactly its row, one
+ * altered MAC row exactly that row: the caller learns which stored row is damaged.  Request a is one half:
+ *   d_rows    n_rows x n_cols symbols of 64 bytes, little-endian, < LCM, row-major: ONE EXACT half (below)
+ *   d_macs    n_rows points, 64 bytes X||Y big-endian affine, 64 zero bytes = infinity: that half's MAC rows as stored, complements included
+ *   d_prf     n_rows PRF outputs of 16 raw bytes: row j's current complement, read as porla_client_update_req.d_prf is read (KZG: a
+ *             big-endian 128-bit integer; IPA: r.d[0], r.d[1] as little-endian words)
+ *   d_out     n_rows x n_cols x 32 bytes: the blocks, byte for byte what porla_icc_decode_batch_device writes for d_rows in the form
+ *             PORLA_ICC_DECODE_EXACT; NULL = check only.  The decode runs whatever the statuses are: the caller decides what to do with
+ *             a level that has failed rows
+ *   d_status  n_rows bytes: PORLA_RETRIEVE_ROW_OK iff the 64 bytes of d_macs row j EQUAL the bytes of the expected MAC in its canonical
+ *             affine form, otherwise 0.  A stored coordinate >= p is not OK; infinity is 64 zero bytes on both sides.  The expected MAC,
+ *             KZG: the bytes porla_kzg_mac_batch_device gives for the row's coefficients sym mod r and the PRF value left-padded to 32
+ *             bytes, i.e. alpha f(tau) G1[0] + prf h_MAC.  IPA: step 1 of porla_ipa_client_update_batch_device, sum_c (sym_c mod n)
+ *             alpha_generators[c] over the first 128 points of alpha_generators_fb plus prf h (h the one point of h_fb), formed by that
+ *             call's own addition
+ *   d_counts  two counters, or NULL; the call zeroes both: [0] the rows with status 0, [1] the data decode's *d_bad (0 when d_out is NULL)
+ * n_cols is the SRS size (KZG) or 128 (IPA), the rule of the client update batch.
+ * Which halves are valid input: an EXACT half, one where every symbol carries both residues -- the X half of every level, and both halves
+ * of the top level porla_server_rebuild_batch_device (CRebuild_Cached) leaves.  A half that holds residues mod p_icc only (the Y rows
+ * HAdd writes, the 32-byte aligned top level) needs its alignment store in the relation (M + alpha A, as in the batched verifier) and is
+ * out of scope: on such a half the call returns statuses that are all 0, and it CANNOT detect the misuse.
+ * n_rows: a power of two, 2 .. 2^16, <= n_total.  n_total: a power of two <= 2^16 (it selects the decode's resident table; no result
+ * depends on it).
+ * Contract: that of the other batches -- asynchronous on hip_stream, no host wait, no side stream; the launch sequence depends on
+ * n_rows, not on k (IPA: while k n_rows 128 x 32 bytes of coefficient rows fit 256 MiB; beyond that the rows go through in groups of
+ * 2^16); the ICC workspace's tables are used under its lock and fence, the KZG state's two-point table and evaluation scratch under
+ * their mutexes and fences, as porla_kzg_mac_batch_device uses them.  One host wait there is, as in that call: the KZG build's table
+ * of powers of tau is uploaded with a blocking copy on the first call and after a change of the key or the SRS size.
+ * PORLA_ERR_ARG (with a message, before the device is touched): NULL reqs with k > 0; NULL d_rows, d_macs, d_prf or d_status; d_rows,
+ * d_macs, d_prf or d_out not 16-byte aligned, d_counts not 4-byte aligned; n_rows not a power of two in 2 .. 2^16 or > n_total; n_total
+ * not a power of two <= 2^16; any output (d_out, d_status, d_counts) overlapping any input or output of any request of the call; more than
+ * 65535 requests; a byte size that overflows; IPA: a NULL base, and (where a base can exist: behind the device check) a BN254 base,
+ * alpha_generators_fb with fewer than 128 points, h_fb without exactly one point.  k = 0 returns 0; KZG without init_key + init_SRS:
+ * PORLA_ERR_STATE; valid arguments without a device: PORLA_ERR_NO_DEVICE.
+ * porla_*_retrieve_host is one level from host memory (upload, the same kernels, download; it waits): out and counts may be NULL.
+ * tools/bench_retrieve.py times the call with and without d_out beside the data decode, the MAC decode and the four-call sequence on
+ * the same level in the same run (DESIGN s4). */
+#define PORLA_RETRIEVE_REQ_BYTES 48    /* sizeof(porla_retrieve_req) on LP64; the library static_asserts it and each offset */
+#define PORLA_RETRIEVE_ROW_OK 1
+typedef struct {
+    const void    *d_rows;    /* 0 */
+    const void    *d_macs;    /* 8 */
+    const void    *d_prf;     /* 16 */
+    void          *d_out;     /* 24 */
+    unsigned char *d_status;  /* 32 */
+    unsigned int  *d_counts;  /* 40 */
+} porla_retrieve_req;
+int porla_kzg_retrieve_batch_device(const porla_retrieve_req *reqs, size_t k, size_t n_rows, size_t n_total, void *hip_stream);
+int porla_ipa_retrieve_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const porla_retrieve_req *reqs,
+                                    size_t k, size_t n_rows, size_t n_total, void *hip_stream);
+int porla_kzg_retrieve_host(const uint8_t *rows, const uint8_t *macs, const uint8_t *prf, size_t n_rows, size_t n_total, uint8_t *out,
+                            uint8_t *status, unsigned int *counts);
+int porla_ipa_retrieve_host(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t *rows, const uint8_t *macs,
+                            const uint8_t *prf, size_t n_rows, size_t n_total, uint8_t *out, uint8_t *status, unsigned int *counts);
+
 /* ---- AES on the device: the MAC PRF of the client writes, the audit challenge from its seed, the client's complement scalar ----
  * These calls PRODUCE the buffers the batches above consume (d_prf; d_idx* / d_coef* / d_mac_*; the 32-byte scalars of
  * porla_kzg_complement_batch_device or of a one-point fixed base) and change none of them.  Both uses are standard AES-128

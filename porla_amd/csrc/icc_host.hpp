@@ -2,6 +2,7 @@
 #pragma once
 #include "host_curve.hpp"
 #include "icc.hip.h"
+#include "../../include/porla_gpu.h"
 
 namespace porla {
 
@@ -58,5 +59,10 @@ inline int icc_pass_plan(int logn, size_t ncols, IccPass out[ICC_MAX_PASSES]) {
     }
     return passes;
 }
+
+// icc_decode.hip: porla_icc_decode_batch_device's body in the EXACT form for a caller that has made the refusals itself (the batched
+// retrieval): the decode's workspace under its lock and fence, every launch on `stream`
+int icc_decode_exact_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve,
+                             hipStream_t stream);
 
 }  // namespace porla

@@ -2,7 +2,7 @@
 // the client forms from the two, over many rows in one call (include/porla_gpu.h: porla_kzg_{digest,complement,mac}_batch_{device,host}).
 // The two evaluation kernels and their table of powers; the three batches on device pointers and on caller-owned host buffers.
 #include "kzg_state.hpp"
-#include "icc30.hip.h"
+#include "kzg_eval.hip.h"
 
 #include <cstring>
 #include <initializer_list>
@@ -13,46 +13,44 @@ using namespace porla;
 using Fp = Bn254Fp;
 using Fr = Bn254Fr;
 
-namespace {
-
-// compute_digest hoisted over rows (main.go:70-89): out[r] = big-endian bytes of alpha * f_r(tau) mod r, f_r given by n
-// coefficients of 32 big-endian bytes (fr.SetBytes: reduced mod r).
-// The evaluation with EIGHT lanes per row in the reduced-radix plain stream (rows longer than KZG_LAZY_MAX_COEFFS) of icc30.hip.h (modulus r = IccBn254Fr's q):
-//   f(tau) = sum_{j<8} tau^j g_j(tau^8),   g_j(x) = sum_k c_{8k+j} x^k
-// lane j runs Horner over its 16 coefficients with tau^8 in the 2^270 form -- acc * (tau^8 2^270) / 2^270 + c: the stream stays plain,
-// a raw 256-bit coefficient is added unreduced (SetBytes' reduction happens in the last step), ONE product per coefficient where
-// k_kzg_eval_rows spends two and a reduction -- then times tau^j, a butterfly sum over the eight lanes, and lane 0 multiplies by
-// alpha and reduces once.  The 8 lanes of a row read 8 consecutive coefficients (256 B) per step, a wave 8 such runs; a row is 16
-// dependent products deep instead of 128.  Bounds: acc < p + 2^248 + 2^256 < 2^258 at every step, the lane sum < 2^261.
-struct KzgEvalConsts {
-    uint32_t tj[8][8];   // tau^j * 2^270 mod r, canonical words, j < 8
-    uint32_t t8[8];      // tau^8 * 2^270 mod r
-    uint32_t alpha[8];   // alpha * 2^270 mod r
-};
-// The end both evaluation kernels share: the butterfly sum over a row's eight lanes (wave-wide, so idle lanes come this far), the
-// MAC batch's second scalar copied beside the result by lane 1 (out_stride = 64), and lane 0's product with alpha in the 2^270
-// form, the one reduction and the store.  Nothing follows it in either kernel: its returns are k_kzg_eval_rows30's returns and
-// k_kzg_eval_rows_lazy's continues.
-template <class Q>
-__device__ __forceinline__ void kzg_eval_finish(F30<Q> acc, bool live, uint32_t j, uint32_t r, const uint32_t (&alpha270)[8],
-                                                uint8_t* __restrict__ out, uint32_t out_stride, const uint8_t* __restrict__ second) {
-#pragma unroll
-    for (int m = 1; m < 8; m <<= 1) {
-        F30<Q> o;
-#pragma unroll
-        for (int l = 0; l < 9; l++) o.v[l] = (uint32_t)__shfl_xor((int)acc.v[l], m);
-        acc = icc30_add<Q>(acc, o);
-    }
-    if (!live) return;
-    if (j == 1 && second) {
-        const uint4* src = (const uint4*)(second + (size_t)r * 32);
-        uint4* dst = (uint4*)(out + (size_t)r * out_stride + 32);
-        dst[0] = src[0]; dst[1] = src[1];
-    }
-    if (j != 0) return;
-    const Fe<Q> res = icc30_canonical<Q>(icc30_reduce_top<Q>(icc30_mul<Q>(acc, f30_unpack<Q>(alpha270))));
-    store_be256(out + (size_t)r * out_stride, res.v);
+// a table of one or two points, rebuilt from `points` if it was built from an older state (g_kzg.mu held)
+int porla::kzg_small_table(FixedBase<Bn254G1>& fb, unsigned long long& built_version, std::initializer_list<Affine<Fp>> points) {
+    if (built_version == g_kzg.version) return PORLA_OK;
+    uint8_t be[128];
+    size_t n = 0;
+    for (const Affine<Fp>& p : points) h_affine_to_bytes<Fp>(be + 64 * n++, p);
+    std::lock_guard<std::mutex> lk(fb.mu);
+    int rc = fb.build_from_host_bytes(be, n, 0, engine_stream());
+    if (rc) return rc;
+    built_version = g_kzg.version;
+    return PORLA_OK;
 }
+
+// x * 2^270 mod r as canonical words, x in the Montgomery form: from_mont(x R * (2^270 R) / R)
+void porla::kzg_to270(const Fe<Fr>& xm, uint32_t dst[8]) {
+    static constexpr uint32_t C270[8] = {0x0ffead6fu, 0x36c69455u, 0x37577218u, 0xb1e9be3cu, 0xdf11f427u, 0x9e7d8ca3u, 0xed6d3304u, 0x279be39au};   // 2^270 mod r
+    Fe<Fr> c270;
+    for (int w = 0; w < 8; w++) c270.v[w] = C270[w];
+    const Fe<Fr> v = fe_from_mont<Fr>(fe_mul<Fr>(xm, fe_to_mont<Fr>(c270)));
+    for (int w = 0; w < 8; w++) dst[w] = v.v[w];
+}
+
+// the table of powers of the dot-product evaluations (g_kzg.mu held): per power i < n_coeffs, padded to a multiple of eight entries with
+// zeros, tau^i as 29-bit limbs in KZG_LAZY_ENTRY_WORDS words and, with `wide`, 2^256 tau^i mod r behind it (the Montgomery form of tau^i
+// read as a plain value is exactly that)
+std::vector<uint32_t> porla::kzg_tau29_table(uint32_t n_coeffs, bool wide) {
+    const size_t entry_words = (wide ? 2 : 1) * KZG_LAZY_ENTRY_WORDS;
+    std::vector<uint32_t> tab((size_t)((n_coeffs + 7) / 8 * 8) * entry_words, 0u);
+    Fe<Fr> pw = fe_one<Fr>();
+    for (uint32_t i = 0; i < n_coeffs; i++) {
+        kzg_unpack29(fe_from_mont<Fr>(pw).v, &tab[(size_t)i * entry_words]);
+        if (wide) kzg_unpack29(pw.v, &tab[(size_t)i * entry_words + KZG_LAZY_ENTRY_WORDS]);
+        pw = fe_mul<Fr>(pw, g_kzg.tau);
+    }
+    return tab;
+}
+
+namespace {
 
 __global__ void __launch_bounds__(256)
 k_kzg_eval_rows30(const uint8_t* __restrict__ rows, uint32_t n_rows, uint32_t n_coeffs, KzgEvalConsts K, uint8_t* __restrict__ out,
@@ -87,38 +85,7 @@ k_kzg_eval_rows30(const uint8_t* __restrict__ rows, uint32_t n_rows, uint32_t n_
     kzg_eval_finish<Q>(acc, live, j, r, K.alpha, out, out_stride, second);
 }
 
-// The evaluation as a DOT PRODUCT with the reduction left to the end: f(tau) = sum_i c_i tau^i with the powers of tau in a table
-// (9 limbs of 29 bits each, staged in LDS), lane j of a row's eight taking i = 8k + j.  A coefficient times a power is 81
-// multiply-adds into 17 64-bit columns and nothing else -- no reduction, no carries: limbs below 2^29 make a column's nine
-// products of one coefficient < 2^61.2, so SIX coefficients accumulate before the columns are rippled (6 * 9 * 2^58 + 2^29 <
-// 2^64) -- where the Horner form above pays a full modular product (81 + 90 multiply-adds and the carries) per coefficient.
-// The lane's sum (< steps * 2^510) is then three 256-bit pieces hi, mid, lo joined by two products with 2^256 in the 2^270 form,
-// and from there the lanes are summed, multiplied by alpha and reduced exactly as in k_kzg_eval_rows30.
-constexpr int KZG_LAZY_ENTRY_WORDS = 12;      // 9 limbs + 3 words of padding: three 16-byte LDS reads per power
-constexpr uint32_t KZG_LAZY_MAX_COEFFS = 1024;
-constexpr uint32_t KZG_M29 = (1u << 29) - 1u;
-constexpr int KZG_LAZY_GROUP = 6;              // coefficients accumulated between two ripples of the columns
-// (reading all six coefficients of a group ahead of their products: 142 registers, 0.51 ms against 0.46 at 2^19 rows; one step
-// ahead, as below: 0.44)
-// a 256-bit value as 9 limbs of 29 bits (the kernel's coefficients; on the host, the table's powers of tau)
-__host__ __device__ __forceinline__ void kzg_unpack29(const uint32_t w[8], uint32_t out[9]) {
-#pragma unroll
-    for (int l = 0; l < 9; l++) {
-        const int bit = 29 * l, i = bit >> 5, sft = bit & 31;
-        const uint64_t two = (uint64_t)w[i] | (i + 1 < 8 ? (uint64_t)w[i + 1] << 32 : 0ull);
-        out[l] = (uint32_t)(two >> sft) & KZG_M29;
-    }
-}
-__device__ __forceinline__ void kzg_ripple29(uint64_t (&col)[19]) {
-    uint64_t carry = 0;
-#pragma unroll
-    for (int k = 0; k < 19; k++) {
-        const uint64_t t = col[k] + carry;
-        col[k] = t & KZG_M29;
-        carry = t >> 29;
-    }
-}
-struct KzgAlpha270 { uint32_t w[8]; };       // alpha * 2^270 mod r
+// the dot-product form (kzg_eval.hip.h) on 32-byte big-endian coefficients
 __global__ void __launch_bounds__(256)
 k_kzg_eval_rows_lazy(const uint8_t* __restrict__ rows, uint32_t n_rows, uint32_t n_coeffs, const uint32_t* __restrict__ tau29,
                      KzgAlpha270 A, uint8_t* __restrict__ out, uint32_t out_stride, const uint8_t* __restrict__ second) {
@@ -129,7 +96,6 @@ k_kzg_eval_rows_lazy(const uint8_t* __restrict__ rows, uint32_t n_rows, uint32_t
         kzg_lds_tau[i] = reinterpret_cast<const uint4*>(tau29)[i];
     __syncthreads();
     const uint32_t j = threadIdx.x & 7u;
-    const F30<Q> C526 = f30_const<Q>(Icc30Const<Q>::C526);
     // a block takes 32 rows at a time, grid-strided: the table above is staged once per block, not once per 32 rows
     for (uint32_t r0 = blockIdx.x * (blockDim.x >> 3); r0 < n_rows; r0 += gridDim.x * (blockDim.x >> 3)) {
         const uint32_t rr = r0 + (threadIdx.x >> 3);
@@ -164,45 +130,9 @@ k_kzg_eval_rows_lazy(const uint8_t* __restrict__ rows, uint32_t n_rows, uint32_t
             if (++since == KZG_LAZY_GROUP) { kzg_ripple29(col); since = 0; }
         }
         kzg_ripple29(col);
-        // 19 limbs of 29 bits -> 17 words of 32: lo = words 0..7, mid = 8..15, hi = word 16 (the sum is below 2^517 for 1024 coefficients)
-        uint32_t W[17];
-#pragma unroll
-        for (int w = 0; w < 17; w++) {
-            const int bit = 32 * w, l = bit / 29, sft = bit % 29;
-            uint64_t v = col[l] >> sft;
-            if (l + 1 < 19) v |= col[l + 1] << (29 - sft);
-            if (l + 2 < 19 && 58 - sft < 32) v |= col[l + 2] << (58 - sft);
-            W[w] = (uint32_t)v;
-        }
-        uint32_t hi[8];
-#pragma unroll
-        for (int w = 0; w < 8; w++) hi[w] = w == 0 ? W[16] : 0u;
-        F30<Q> acc = icc30_add<Q>(icc30_mul<Q>(f30_unpack<Q>(hi), C526), f30_unpack<Q>(W + 8));
-        acc = icc30_add<Q>(icc30_mul<Q>(acc, C526), f30_unpack<Q>(W));
+        const F30<Q> acc = kzg_columns_join<Q>(col);          // (the sum is below 2^517 for 1024 coefficients)
         kzg_eval_finish<Q>(acc, live, j, r, A.w, out, out_stride, second);
     }
-}
-
-// a table of one or two points, rebuilt from `points` if it was built from an older state (g_kzg.mu held)
-int small_table(FixedBase<Bn254G1>& fb, unsigned long long& built_version, std::initializer_list<Affine<Fp>> points) {
-    if (built_version == g_kzg.version) return PORLA_OK;
-    uint8_t be[128];
-    size_t n = 0;
-    for (const Affine<Fp>& p : points) h_affine_to_bytes<Fp>(be + 64 * n++, p);
-    std::lock_guard<std::mutex> lk(fb.mu);
-    int rc = fb.build_from_host_bytes(be, n, 0, engine_stream());
-    if (rc) return rc;
-    built_version = g_kzg.version;
-    return PORLA_OK;
-}
-
-// x * 2^270 mod r as canonical words, x in the Montgomery form: from_mont(x R * (2^270 R) / R)
-void kzg_to270(const Fe<Fr>& xm, uint32_t dst[8]) {
-    static constexpr uint32_t C270[8] = {0x0ffead6fu, 0x36c69455u, 0x37577218u, 0xb1e9be3cu, 0xdf11f427u, 0x9e7d8ca3u, 0xed6d3304u, 0x279be39au};   // 2^270 mod r
-    Fe<Fr> c270;
-    for (int w = 0; w < 8; w++) c270.v[w] = C270[w];
-    const Fe<Fr> v = fe_from_mont<Fr>(fe_mul<Fr>(xm, fe_to_mont<Fr>(c270)));
-    for (int w = 0; w < 8; w++) dst[w] = v.v[w];
 }
 
 // alpha * f_r(tau) of n_rows rows into kd->d_eval at out_stride bytes per row (32, or 64 with a second scalar copied beside it).
@@ -218,12 +148,7 @@ int kzg_eval_rows_launch(KzgDev* kd, const void* d_rows, size_t n_rows, uint32_t
     if (n_coeffs <= KZG_LAZY_MAX_COEFFS) {
         const uint32_t entries = (n_coeffs + 7) / 8 * 8;
         if (!kd->d_tau29.p || kd->tau29_n != n_coeffs || memcmp(kd->tau29_tau.v, g_kzg.tau.v, sizeof(g_kzg.tau.v)) != 0) {
-            std::vector<uint32_t> tab((size_t)entries * KZG_LAZY_ENTRY_WORDS, 0u);
-            Fe<Fr> pw = fe_one<Fr>();
-            for (uint32_t i = 0; i < n_coeffs; i++) {
-                kzg_unpack29(fe_from_mont<Fr>(pw).v, &tab[(size_t)i * KZG_LAZY_ENTRY_WORDS]);
-                pw = fe_mul<Fr>(pw, g_kzg.tau);
-            }
+            const std::vector<uint32_t> tab = kzg_tau29_table(n_coeffs, false);
             kd->d_tau29.release();                                // the hipFree waits for the evaluations that still read the old table
             kd->tau29_n = 0;
             if ((rc = kd->d_tau29.ensure(tab.size() * 4))) return rc;
@@ -270,9 +195,9 @@ int client_batch_device(int kind /* 0 digest, 1 complement, 2 MAC */, const void
     KzgDev* kd;
     if ((rc = current_dev(&kd))) return rc;
     FixedBase<Bn254G1>& fb = kind == 0 ? kd->fb_g : kind == 1 ? kd->fb_h : kd->fb_gh;
-    if (kind == 0) rc = small_table(fb, kd->g_version, {g_kzg.srs[0]});
-    else if (kind == 1) rc = small_table(fb, kd->h_version, {g_kzg.h_mac});
-    else rc = small_table(fb, kd->gh_version, {g_kzg.srs[0], g_kzg.h_mac});
+    if (kind == 0) rc = kzg_small_table(fb, kd->g_version, {g_kzg.srs[0]});
+    else if (kind == 1) rc = kzg_small_table(fb, kd->h_version, {g_kzg.h_mac});
+    else rc = kzg_small_table(fb, kd->gh_version, {g_kzg.srs[0], g_kzg.h_mac});
     if (rc) return rc;
     std::lock_guard<std::mutex> lk2(fb.mu);
     if (kind == 1) return fb.commit_device((const uint8_t*)d_scalars, n, 1, 32, (uint8_t*)d_out, stream);

@@ -367,6 +367,8 @@ int porla_kzg_release_device_memory(void) {
         kd->d_eval.release();
         kd->d_tau29.release();
         kd->tau29_n = 0;
+        kd->d_tau29w.release();
+        kd->tau29w_n = 0;
         kd->srs_version = kd->g_version = kd->h_version = kd->gh_version = 0;
     }
     (void)hipSetDevice(cur);

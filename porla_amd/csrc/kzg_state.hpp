@@ -21,6 +21,9 @@ struct KzgDev {
     Buf d_tau29;                  // powers of tau in 29-bit limbs (k_kzg_eval_rows_lazy), for the key and row length below
     Fe<Bn254Fr> tau29_tau;
     uint32_t tau29_n = 0;
+    Buf d_tau29w;                 // per power two entries, tau^i and 2^256 tau^i (retrieve_batch.hip: k_rt_eval_lazy), kept as d_tau29 is
+    Fe<Bn254Fr> tau29w_tau;
+    uint32_t tau29w_n = 0;
 };
 
 struct KzgState {
@@ -84,6 +87,12 @@ int kzg_commit_rows(const uint8_t* rows, bool device_ptrs, size_t n_rows, size_t
 int kzg_commit_coalesced(const uint8_t* row, uint8_t out[64]);
 // kzg_abi.hip: y = f(z) and the quotient h = (f - y)/(X - z) of create_proof (main.go:153-175), on the host
 void kzg_open_rows(const uint8_t* d, size_t n, unsigned long long random_point, uint8_t* h_row, uint8_t point[32], uint8_t claim[32]);
+// kzg_client_batch.hip: a table of one or two points, rebuilt from `points` if it was built from an older state (g_kzg.mu held); x *
+// 2^270 mod r as canonical words, x in the Montgomery form
+int kzg_small_table(FixedBase<Bn254G1>& fb, unsigned long long& built_version, std::initializer_list<Affine<Bn254Fp>> points);
+void kzg_to270(const Fe<Bn254Fr>& xm, uint32_t dst[8]);
+// kzg_client_batch.hip: the dot-product evaluations' table of powers of tau, one entry per power or (wide) two (g_kzg.mu held)
+std::vector<uint32_t> kzg_tau29_table(uint32_t n_coeffs, bool wide);
 // kzg_client_batch.hip: frees the host batches' staging buffers (takes their mutexes: call it outside g_kzg.mu)
 void kzg_client_staging_release();
 

@@ -350,6 +350,47 @@ def kzg_client_rebuild_batch_device(reqs, n_total, stream=0):
     _check(lib.porla_kzg_client_rebuild_batch_device(arr, len(reqs), n_total, ctypes.c_void_p(stream)))
 
 
+# ---- verified retrieval: a level's coded rows checked against its MAC rows, then decoded (include/porla_gpu.h: porla_*_retrieve_*) ----
+def retrieve_requests(reqs):
+    """a ctypes array of porla_retrieve_req from per-half tuples (d_rows, d_macs, d_prf, d_out or 0, d_status, d_counts or 0): device
+    addresses as integers"""
+    from .loader import RetrieveReq
+    arr = (RetrieveReq * max(len(reqs), 1))()
+    for i, r in enumerate(reqs):
+        if len(r) != 6:
+            raise ValueError("retrieve_batch_device: request %d has %d fields, want 6" % (i, len(r)))
+        arr[i] = RetrieveReq(*(x or None for x in r))
+    return arr
+
+
+def _retrieve_host(call, rows, macs, prf, n_rows, n_cols, want_blocks):
+    """(status bytes, [failed rows, the decode's bad count], blocks or None) of one level from host memory"""
+    for name, buf, want in (("rows", rows, 64 * n_rows * n_cols), ("macs", macs, 64 * n_rows), ("prf", prf, 16 * n_rows)):
+        if n_cols and len(buf) != want:                     # the library reads exactly these sizes (no SRS yet: it refuses the call)
+            raise ValueError("retrieve_host: %s holds %d bytes, the call reads %d" % (name, len(buf), want))
+    out = ctypes.create_string_buffer(32 * n_rows * n_cols) if want_blocks else None
+    status = ctypes.create_string_buffer(n_rows)
+    counts = (ctypes.c_uint * 2)()
+    _check(call(bytes(rows), bytes(macs), bytes(prf), out, status, counts))
+    return status.raw, [counts[0], counts[1]], out.raw if want_blocks else None
+
+
+def kzg_retrieve_batch_device(reqs, n_rows, n_total, stream=0):
+    """The coded rows of len(reqs) exact halves checked row by row against their stored MAC rows in the coded domain (status byte 1 iff
+    the stored MAC row equals alpha f(tau) G1[0] + prf h_MAC of the row's symbols mod r), then decoded (d_out; 0 = check only), in ONE
+    asynchronous call on `stream`, KZG build; n_cols is the SRS size.  `reqs`: tuples as retrieve_requests takes them."""
+    arr = retrieve_requests(reqs)
+    _check(lib.porla_kzg_retrieve_batch_device(arr, len(reqs), n_rows, n_total, ctypes.c_void_p(stream)))
+
+
+def kzg_retrieve_host(rows, macs, prf, n_rows, n_total, want_blocks=True):
+    """one level from host memory (porla_kzg_retrieve_host; it waits) -> (status bytes, [failed rows, the decode's bad count], blocks
+    or None)"""
+    n_cols = kzg_row_coefficients()                        # the resident SRS size: what the library reads per row
+    return _retrieve_host(lambda r, m, p, out, st, cn: lib.porla_kzg_retrieve_host(r, m, p, n_rows, n_total, out, st, cn),
+                          rows, macs, prf, n_rows, n_cols, want_blocks)
+
+
 # ---- batched fixed-base commitments (include/porla_gpu.h) ------------------------------------------
 CURVES = {"bn254": 0, "secp256k1": 1}
 
@@ -419,6 +460,20 @@ class FixedBase:
         arr = client_update_requests(reqs)
         _check(lib.porla_ipa_client_update_batch_device(self.h, h_fb.h if h_fb is not None else None, arr, len(reqs), n_total,
                                                         ctypes.c_void_p(stream)))
+
+    def ipa_retrieve_batch_device(self, h_fb, reqs, n_rows, n_total, stream=0):
+        """kzg_retrieve_batch_device for the IPA build (porla_ipa_retrieve_batch_device: 128 columns; the expected MAC of a row is
+        sum_c (sym_c mod n) alpha_generators[c] + prf h); self and h_fb as for ipa_client_update_batch_device.  `reqs`: tuples as
+        retrieve_requests takes them."""
+        arr = retrieve_requests(reqs)
+        _check(lib.porla_ipa_retrieve_batch_device(self.h, h_fb.h if h_fb is not None else None, arr, len(reqs), n_rows, n_total,
+                                                   ctypes.c_void_p(stream)))
+
+    def ipa_retrieve_host(self, h_fb, rows, macs, prf, n_rows, n_total, want_blocks=True):
+        """one level from host memory (porla_ipa_retrieve_host; it waits) -> what kzg_retrieve_host returns"""
+        hh = h_fb.h if h_fb is not None else None
+        return _retrieve_host(lambda r, m, p, out, st, cn: lib.porla_ipa_retrieve_host(self.h, hh, r, m, p, n_rows, n_total, out, st, cn),
+                              rows, macs, prf, n_rows, 128, want_blocks)
 
     def ipa_client_rebuild_batch_device(self, h_fb, reqs, n_total, stream=0):
         """The client's rebuild write (Client::CRebuild's step) of len(reqs) independent writes in ONE asynchronous call on `stream`, IPA
