@@ -962,8 +962,9 @@ int porla_icc_mac_decode_host(const uint8_t *macs, size_t n_rows, size_t n_total
  * n_cols is the SRS size (KZG) or 128 (IPA), the rule of the client update batch.
  * Which halves are valid input: an EXACT half, one where every symbol carries both residues -- the X half of every level, and both halves
  * of the top level porla_server_rebuild_batch_device (CRebuild_Cached) leaves.  A half that holds residues mod p_icc only (the Y rows
- * HAdd writes, the 32-byte aligned top level) needs its alignment store in the relation (M + alpha A, as in the batched verifier) and is
- * out of scope: on such a half the call returns statuses that are all 0, and it CANNOT detect the misuse.
+ * HAdd writes, the 32-byte aligned top level) needs its alignment store in the relation (M + alpha A, as in the batched verifier):
+ * that is porla_*_retrieve_aligned_batch_device below, which covers every half of every level.  THIS call has no alignment store to
+ * look at, so on such a half its statuses are 0 on every row whose alignment is finite.
  * n_rows: a power of two, 2 .. 2^16, <= n_total.  n_total: a power of two <= 2^16 (it selects the decode's resident table; no result
  * depends on it).
  * Contract: that of the other batches -- asynchronous on hip_stream, no host wait, no side stream; the launch sequence depends on
@@ -997,6 +998,66 @@ int porla_kzg_retrieve_host(const uint8_t *rows, const uint8_t *macs, const uint
                             uint8_t *status, unsigned int *counts);
 int porla_ipa_retrieve_host(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t *rows, const uint8_t *macs,
                             const uint8_t *prf, size_t n_rows, size_t n_total, uint8_t *out, uint8_t *status, unsigned int *counts);
+
+/* ---- verified retrieval of ANY half: the alignment store joins the relation ----
+ * Every row of every non-empty level, X and Y, keeps MAC[j] + alpha * align[j] == alpha * Commit(row[j] mod q) (+ s_j h with the
+ * complements), row[j] being the STORED symbol reduced mod the group order q: the rows mix mod LCM and both point stores mix by the
+ * same multipliers mod q (tests/test_update_batch_cpu.py), and the aligned top level has it by construction (c = (A mod p_icc - A) mod
+ * q, alignment = Commit(c)).  So for every half
+ *     status_j = (bytes of d_macs row j == canonical affine bytes of E_j - alpha * A_j)
+ * with E_j the expected MAC of porla_*_retrieve_batch_device above and A_j row j of the half's alignment store; with every A_j at
+ * infinity this IS that call.  Request a is one half; d_rows, d_macs, d_prf, d_status, d_counts as in porla_retrieve_req, and
+ *   d_align        n_rows points, 64 bytes X||Y big-endian affine, 64 zero bytes = infinity: the half's alignment rows, read the way the
+ *                  MAC stores are read everywhere (coordinates reduced mod p; NOT checked to be on the curve: a garbage A_j gives a
+ *                  defined, fault-free result, which will be status 0).  NULL = every alignment at infinity
+ *   d_write_steps  n_rows values or NULL; residue forms only: the data decode's unscale of a Y half (porla_icc_decode_req)
+ *   d_out          n_rows x n_cols x 32 bytes, byte for byte what porla_icc_decode_batch_device writes for the same rows, form and write
+ *                  steps; NULL = check only
+ *   d_counts[1]    that call's *d_bad for PORLA_ICC_DECODE_EXACT, 0 for the residue forms
+ * form, one of the decode's constants, fixes the row width the check reads AND the decode that runs when d_out is given:
+ * PORLA_ICC_DECODE_EXACT and PORLA_ICC_DECODE_RESIDUE64 read 64-byte little-endian symbols below LCM, PORLA_ICC_DECODE_RESIDUE32 reads
+ * 32-byte little-endian symbols below p_icc (the d_rows32 store of porla_*_server_rebuild_aligned_batch_device).
+ * Which call on which store: a cached top level or an X half -- either call (form EXACT); a Y half of 64-byte rows -- this call with
+ * RESIDUE64, the half's alignment store and the blocks' write steps; the aligned top level -- this call with RESIDUE32.
+ * alpha.  KZG: the state's key, the value the expected MACs are made with.  IPA: alpha_be, 32 big-endian bytes, reduced mod n; it must be
+ * the scalar with alpha_generators[c] = alpha * generators[c].  The call CANNOT check that: a wrong alpha fails every row whose
+ * alignment is finite (and no other).
+ * Infinity on both sides is 64 zero bytes; a stored coordinate >= p in d_macs is not OK.
+ * Launches: those of porla_*_retrieve_batch_device; when a request of the call has a d_align, k_rt_compare_aligned (a quad of lanes per
+ * row, alpha * A_j by the four-lane uniform ladder of the MAC network) stands in for k_rt_compare, and a block of 64 rows without a
+ * nonzero alignment byte runs k_rt_compare's body instead of the ladder; then the data decode of `form`.  Contract, locks and fences:
+ * as porla_*_retrieve_batch_device -- asynchronous on hip_stream, no side stream, no host wait beyond that call's, the launch sequence
+ * depends on n_rows and not on k.
+ * PORLA_ERR_ARG (with a message, before the device is touched): everything porla_*_retrieve_batch_device refuses, the byte sizes being
+ * computed from the form's row width; a form that is none of the three; d_align not 16-byte aligned; d_write_steps not 8-byte aligned,
+ * or given with PORLA_ICC_DECODE_EXACT; NULL alpha_be (IPA); an output overlapping any input (d_align and d_write_steps included) or any
+ * output of any request.  k = 0 returns 0; KZG without init_key + init_SRS: PORLA_ERR_STATE; valid arguments without a device:
+ * PORLA_ERR_NO_DEVICE.
+ * porla_*_retrieve_aligned_host is one level from host memory (it waits): align, write_steps, out and counts may be NULL.
+ * tools/bench_retrieve_aligned.py times the call beside porla_*_retrieve_batch_device on the same level (DESIGN s4). */
+#define PORLA_RETRIEVE_ALIGNED_REQ_BYTES 64   /* sizeof(porla_retrieve_aligned_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    const void               *d_rows;         /*  0 */
+    const void               *d_macs;         /*  8 */
+    const void               *d_prf;          /* 16 */
+    const void               *d_align;        /* 24 */
+    const unsigned long long *d_write_steps;  /* 32 */
+    void                     *d_out;          /* 40 */
+    unsigned char            *d_status;       /* 48 */
+    unsigned int             *d_counts;       /* 56 */
+} porla_retrieve_aligned_req;
+int porla_kzg_retrieve_aligned_batch_device(const porla_retrieve_aligned_req *reqs, size_t k, size_t n_rows, size_t n_total, int form,
+                                            void *hip_stream);
+int porla_ipa_retrieve_aligned_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t alpha_be[32],
+                                            const porla_retrieve_aligned_req *reqs, size_t k, size_t n_rows, size_t n_total, int form,
+                                            void *hip_stream);
+int porla_kzg_retrieve_aligned_host(const uint8_t *rows, const uint8_t *macs, const uint8_t *prf, const uint8_t *align,
+                                    const unsigned long long *write_steps, size_t n_rows, size_t n_total, int form, uint8_t *out,
+                                    uint8_t *status, unsigned int *counts);
+int porla_ipa_retrieve_aligned_host(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t alpha_be[32],
+                                    const uint8_t *rows, const uint8_t *macs, const uint8_t *prf, const uint8_t *align,
+                                    const unsigned long long *write_steps, size_t n_rows, size_t n_total, int form, uint8_t *out,
+                                    uint8_t *status, unsigned int *counts);
 
 /* ---- AES on the device: the MAC PRF of the client writes, the audit challenge from its seed, the client's complement scalar ----
  * These calls PRODUCE the buffers the batches above consume (d_prf; d_idx* / d_coef* / d_mac_*; the 32-byte scalars of

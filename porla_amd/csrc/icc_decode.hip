@@ -169,11 +169,15 @@ static int icd_run(IccDecodeWs* ws, const porla_icc_decode_req* reqs, size_t k, 
                       : icd_enqueue<IccSecp256k1Fn>(ws, 1, reqs, k, n_rows, n_cols, n_total, form, stream);
 }
 
-int icc_decode_exact_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve,
-                             hipStream_t stream) {
+int icc_decode_form_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form,
+                            hipStream_t stream) {
     IccDecodeWs* ws = nullptr;
     if (int rc = g_icd_ws.get(&ws)) return rc;
-    return FencedCall(ws, stream).run([&] { return icd_run(ws, reqs, k, n_rows, n_cols, n_total, curve, PORLA_ICC_DECODE_EXACT, stream); });
+    return FencedCall(ws, stream).run([&] { return icd_run(ws, reqs, k, n_rows, n_cols, n_total, curve, form, stream); });
+}
+int icc_decode_exact_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve,
+                             hipStream_t stream) {
+    return icc_decode_form_enqueue(reqs, k, n_rows, n_cols, n_total, curve, PORLA_ICC_DECODE_EXACT, stream);
 }
 
 }  // namespace porla

@@ -64,5 +64,8 @@ inline int icc_pass_plan(int logn, size_t ncols, IccPass out[ICC_MAX_PASSES]) {
 // retrieval): the decode's workspace under its lock and fence, every launch on `stream`
 int icc_decode_exact_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve,
                              hipStream_t stream);
+// ... and in any of the three forms (the aligned retrieval: the residue forms carry the requests' d_write_steps through)
+int icc_decode_form_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form,
+                            hipStream_t stream);
 
 }  // namespace porla

@@ -119,6 +119,17 @@ PORLA_RETRIEVE_ROW_OK = 1
 assert ctypes.sizeof(RetrieveReq) == PORLA_RETRIEVE_REQ_BYTES
 
 
+class RetrieveAlignedReq(ctypes.Structure):
+    """porla_retrieve_aligned_req, include/porla_gpu.h: one half of porla_kzg_retrieve_aligned_batch_device /
+    porla_ipa_retrieve_aligned_batch_device (PORLA_RETRIEVE_ALIGNED_REQ_BYTES = 64)."""
+    _fields_ = [("d_rows", ctypes.c_void_p), ("d_macs", ctypes.c_void_p), ("d_prf", ctypes.c_void_p), ("d_align", ctypes.c_void_p),
+                ("d_write_steps", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("d_status", ctypes.c_void_p), ("d_counts", ctypes.c_void_p)]
+
+
+PORLA_RETRIEVE_ALIGNED_REQ_BYTES = 64
+assert ctypes.sizeof(RetrieveAlignedReq) == PORLA_RETRIEVE_ALIGNED_REQ_BYTES
+
+
 class PrfRun(ctypes.Structure):
     """porla_prf_run, include/porla_gpu.h: count triples (level, index0 + t, time0 + t * time_stride) of the MAC PRF
     (PORLA_PRF_RUN_BYTES = 32)."""
@@ -312,6 +323,15 @@ def _declare(L):
     L.porla_kzg_retrieve_host.restype = ctypes.c_int
     L.porla_ipa_retrieve_host.argtypes = [vp, vp, u8p, u8p, u8p, sz, sz, vp, vp, ctypes.POINTER(ctypes.c_uint)]
     L.porla_ipa_retrieve_host.restype = ctypes.c_int
+    L.porla_kzg_retrieve_aligned_batch_device.argtypes = [ctypes.POINTER(RetrieveAlignedReq), sz, sz, sz, ctypes.c_int, vp]
+    L.porla_kzg_retrieve_aligned_batch_device.restype = ctypes.c_int
+    L.porla_ipa_retrieve_aligned_batch_device.argtypes = [vp, vp, u8p, ctypes.POINTER(RetrieveAlignedReq), sz, sz, sz, ctypes.c_int, vp]
+    L.porla_ipa_retrieve_aligned_batch_device.restype = ctypes.c_int
+    L.porla_kzg_retrieve_aligned_host.argtypes = [u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp, ctypes.POINTER(ctypes.c_uint)]
+    L.porla_kzg_retrieve_aligned_host.restype = ctypes.c_int
+    L.porla_ipa_retrieve_aligned_host.argtypes = [vp, vp, u8p, u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp,
+                                                  ctypes.POINTER(ctypes.c_uint)]
+    L.porla_ipa_retrieve_aligned_host.restype = ctypes.c_int
     L.porla_mac_prf_batch_device.argtypes = [u8p, ctypes.POINTER(PrfRun), sz, vp, vp]; L.porla_mac_prf_batch_device.restype = ctypes.c_int
     L.porla_mac_prf_host.argtypes = [u8p, ctypes.POINTER(PrfRun), sz, vp]; L.porla_mac_prf_host.restype = ctypes.c_int
     L.porla_client_prf_runs.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, sz, ctypes.POINTER(PrfRun), sz,

@@ -391,8 +391,68 @@ def kzg_retrieve_host(rows, macs, prf, n_rows, n_total, want_blocks=True):
                           rows, macs, prf, n_rows, n_cols, want_blocks)
 
 
+# ---- verified retrieval of any half: the alignment store joins the relation (include/porla_gpu.h: porla_*_retrieve_aligned_*) ----
+RETRIEVE_FORM = {"exact": 0, "residue64": 1, "residue32": 2}        # icc.DECODE_FORM: the decode's constants
+RETRIEVE_SYMBOL_BYTES = {"exact": 64, "residue64": 64, "residue32": 32}
+
+
+def retrieve_aligned_requests(reqs):
+    """a ctypes array of porla_retrieve_aligned_req from per-half tuples (d_rows, d_macs, d_prf, d_align or 0, d_write_steps or 0, d_out
+    or 0, d_status, d_counts or 0): device addresses as integers"""
+    from .loader import RetrieveAlignedReq
+    arr = (RetrieveAlignedReq * max(len(reqs), 1))()
+    for i, r in enumerate(reqs):
+        if len(r) != 8:
+            raise ValueError("retrieve_aligned_batch_device: request %d has %d fields, want 8" % (i, len(r)))
+        arr[i] = RetrieveAlignedReq(*(x or None for x in r))
+    return arr
+
+
+def _retrieve_aligned_host(call, rows, macs, prf, align, write_steps, n_rows, n_cols, form, want_blocks):
+    """(status bytes, [failed rows, the decode's bad count], blocks or None) of one level from host memory"""
+    sizes = [("rows", rows, RETRIEVE_SYMBOL_BYTES[form] * n_rows * n_cols), ("macs", macs, 64 * n_rows), ("prf", prf, 16 * n_rows)]
+    if align is not None:
+        sizes.append(("align", align, 64 * n_rows))
+    for name, buf, want in sizes:
+        if n_cols and len(buf) != want:                     # the library reads exactly these sizes (no SRS yet: it refuses the call)
+            raise ValueError("retrieve_aligned_host: %s holds %d bytes, the call reads %d" % (name, len(buf), want))
+    if write_steps is not None and len(write_steps) != n_rows:
+        raise ValueError("retrieve_aligned_host: %d write steps, want %d" % (len(write_steps), n_rows))
+    steps = (ctypes.c_ulonglong * n_rows)(*write_steps) if write_steps is not None else None
+    out = ctypes.create_string_buffer(32 * n_rows * n_cols) if want_blocks else None
+    status = ctypes.create_string_buffer(n_rows)
+    counts = (ctypes.c_uint * 2)()
+    _check(call(bytes(rows), bytes(macs), bytes(prf), bytes(align) if align is not None else None, steps, out, status, counts))
+    return status.raw, [counts[0], counts[1]], out.raw if want_blocks else None
+
+
+def kzg_retrieve_aligned_batch_device(reqs, n_rows, n_total, form, stream=0):
+    """kzg_retrieve_batch_device for ANY half: status byte 1 iff the stored MAC row equals E_j - alpha A_j, E_j that call's expected MAC
+    and A_j the half's alignment row (d_align; 0 = all at infinity, which is that call).  form: "exact" / "residue64" (64-byte rows) or
+    "residue32" (32-byte rows below p_icc): the row width the check reads and the decode that fills d_out (with d_write_steps, the
+    residue forms' unscale of a Y half).  `reqs`: tuples as retrieve_aligned_requests takes them."""
+    arr = retrieve_aligned_requests(reqs)
+    _check(lib.porla_kzg_retrieve_aligned_batch_device(arr, len(reqs), n_rows, n_total, RETRIEVE_FORM[form], ctypes.c_void_p(stream)))
+
+
+def kzg_retrieve_aligned_host(rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None, want_blocks=True):
+    """one level from host memory (porla_kzg_retrieve_aligned_host; it waits) -> what kzg_retrieve_host returns"""
+    n_cols = kzg_row_coefficients()
+    f = RETRIEVE_FORM[form]
+    return _retrieve_aligned_host(lambda r, m, p, a, ws, out, st, cn: lib.porla_kzg_retrieve_aligned_host(r, m, p, a, ws, n_rows, n_total, f,
+                                                                                                        out, st, cn),
+                                  rows, macs, prf, align, write_steps, n_rows, n_cols, form, want_blocks)
+
+
 # ---- batched fixed-base commitments (include/porla_gpu.h) ------------------------------------------
 CURVES = {"bn254": 0, "secp256k1": 1}
+
+
+def _alpha_be(alpha):
+    """an integer or 32 bytes -> the 32 big-endian bytes the aligned retrieval takes; None stays None (the library refuses it)"""
+    if alpha is None:
+        return None
+    return alpha.to_bytes(32, "big") if isinstance(alpha, int) else bytes(alpha)
 
 
 class FixedBase:
@@ -474,6 +534,23 @@ class FixedBase:
         hh = h_fb.h if h_fb is not None else None
         return _retrieve_host(lambda r, m, p, out, st, cn: lib.porla_ipa_retrieve_host(self.h, hh, r, m, p, n_rows, n_total, out, st, cn),
                               rows, macs, prf, n_rows, 128, want_blocks)
+
+    def ipa_retrieve_aligned_batch_device(self, h_fb, alpha, reqs, n_rows, n_total, form, stream=0):
+        """kzg_retrieve_aligned_batch_device for the IPA build (porla_ipa_retrieve_aligned_batch_device); self and h_fb as for
+        ipa_retrieve_batch_device.  alpha: the scalar with alpha_generators[c] = alpha * generators[c], an integer or 32 big-endian
+        bytes -- the call cannot check it: a wrong alpha fails every row whose alignment is finite."""
+        arr = retrieve_aligned_requests(reqs)
+        _check(lib.porla_ipa_retrieve_aligned_batch_device(self.h, h_fb.h if h_fb is not None else None, _alpha_be(alpha), arr, len(reqs),
+                                                           n_rows, n_total, RETRIEVE_FORM[form], ctypes.c_void_p(stream)))
+
+    def ipa_retrieve_aligned_host(self, h_fb, alpha, rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None,
+                                  want_blocks=True):
+        """one level from host memory (porla_ipa_retrieve_aligned_host; it waits) -> what kzg_retrieve_host returns"""
+        hh = h_fb.h if h_fb is not None else None
+        f, ab = RETRIEVE_FORM[form], _alpha_be(alpha)
+        return _retrieve_aligned_host(lambda r, m, p, a, ws, out, st, cn: lib.porla_ipa_retrieve_aligned_host(self.h, hh, ab, r, m, p, a, ws,
+                                                                                                            n_rows, n_total, f, out, st, cn),
+                                      rows, macs, prf, align, write_steps, n_rows, 128, form, want_blocks)
 
     def ipa_client_rebuild_batch_device(self, h_fb, reqs, n_total, stream=0):
         """The client's rebuild write (Client::CRebuild's step) of len(reqs) independent writes in ONE asynchronous call on `stream`, IPA
