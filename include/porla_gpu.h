@@ -1059,6 +1059,74 @@ int porla_ipa_retrieve_aligned_host(porla_fixed_base *alpha_generators_fb, porla
                                     const unsigned long long *write_steps, size_t n_rows, size_t n_total, int form, uint8_t *out,
                                     uint8_t *status, unsigned int *counts);
 
+/* ---- verified file extraction: every resident level of K files checked, decoded and merged, newest authentic copy wins ----
+ * The retrieval calls above give ONE level back; a proof of retrievability promises the FILE.  This call takes K files with their
+ * hierarchies as they lie in HBM, checks every resident row, decodes every resident X half and merges the decoded blocks into the
+ * file's block store.  What the hierarchy gives (Server::HAdd / HRebuildX / HRebuildY, Server.hpp:1330-1477; tests/update_model.py):
+ * with t = write_step % n_total, level i < log2 n_total is resident iff bit i of t is set and its X half holds the blocks of the epoch
+ * write steps hi_i - 2^i + 1 .. hi_i, hi_i = t with the bits below i cleared, decoded in write order, oldest first; lower levels are
+ * newer; the top level holds U as of the last rebuild, block b at position b, older than everything below it; with t == 0 only the top
+ * level is resident.  The X half of a lower level is exact (64-byte symbols below LCM; level 0's one row is the chunks zero-extended);
+ * the top level's X half is exact after porla_server_rebuild_batch_device, or 32-byte residues mod p_icc with an alignment store
+ * after porla_*_server_rebuild_aligned_batch_device: top_form, PORLA_ICC_DECODE_EXACT or PORLA_ICC_DECODE_RESIDUE32, for the whole call.
+ * A block names its slot: the low 8 bytes of chunk 0, a little-endian 64-bit integer, are the block index counted from 1 (the
+ * reference's wire format, Client.hpp:367-372 / Server.hpp:404-414); chunk 0 is under the row check like the rest.
+ * Request a is one file (the fields below).  n_cols is the SRS size (KZG) or 128 (IPA); n_total a power of two, 2 .. 2^16.
+ *   1. Row check.  Every resident row gets the status of porla_*_retrieve_aligned_batch_device, byte for byte: PORLA_RETRIEVE_ROW_OK
+ *      iff the stored MAC bytes equal the canonical bytes of E_j - alpha A_j, the lower levels without an alignment store, the top
+ *      level with d_top_align.  Level 0's single row is checked by the same relation.
+ *   2. Failed levels.  A level with a status-0 row is failed, the top level included; a decoded block depends on every row of its
+ *      level, so no block of a failed level is ever taken.
+ *   3. Merge.  A block of a clean lower level whose index id is in 1 .. n_total is a candidate for slot id - 1 with its epoch write
+ *      step as rank; block b of a clean top level is a candidate for slot b with rank 0.  The highest rank wins; ranks are distinct.
+ *   4. Per slot: d_blocks = the winner's n_cols x 32 bytes, or zeros; d_steps = the winner's rank, or 0xffffffff; d_flags = FOUND iff
+ *      there is a winner, RESIDUE iff the winner is a top-level block and top_form is RESIDUE32, UNSURE iff some failed level's
+ *      highest write step (hi_i; 0 for the top level) is greater than the winner's rank, a slot without a winner having rank -1.
+ *   5. A block of a clean lower level whose index is 0 or above n_total is counted and dropped.
+ *   6. d_counts: [0] the rows with status 0, [1] the sum of the exact decodes' bad-symbol counts (level 0: symbols with a nonzero
+ *      upper half), [2] the blocks dropped under 5, [3] the slots that are not FOUND or are UNSURE.
+ * Launches: one upload; one clear; the aligned retrieval's check launches ONCE over all 64-byte rows of all files and levels and once
+ * more over the RESIDUE32 top levels (the rows find their half by a binary search in the halves' start rows; IPA in its coefficient
+ * workspace groups) -- their number depends on the symbol widths present, not on K and not on which levels are resident; the data
+ * decode once per level size present (top level straight into d_blocks, lower levels into d_work, level 0 by a copy kernel); three
+ * merge kernels.  Contract: that of the other batches -- asynchronous on hip_stream, no side stream, no host wait beyond the retrieval
+ * calls' first-use upload of the tau table; workspaces under their locks and fences.
+ * PORLA_ERR_ARG (with a message, before the device is touched): NULL reqs with k > 0; NULL d_blocks, d_steps or d_flags; NULL d_prf or
+ * d_row_status with a resident row; NULL d_top_macs beside d_top_rows; NULL data_x, mac_x or d_work with t > 0 (they may be NULL only when
+ * t == 0); a resident level with a NULL pointer; a level pointer, d_top_rows, d_top_macs, d_top_align, d_prf, d_work or d_blocks not
+ * 16-byte aligned, d_steps or d_counts not 4-byte aligned; n_total not a power of two in 2 .. 2^16; a top_form that is neither of the
+ * two; NULL alpha_be or bases (IPA); more than 65535 requests; a byte size that overflows; any output (d_work counts as one)
+ * overlapping any input or output of the call.  k = 0 returns 0; KZG without init_key + init_SRS: PORLA_ERR_STATE; valid arguments
+ * without a device: PORLA_ERR_NO_DEVICE.
+ * Not in this call: a level's Y half when its X half fails (the row statuses say which half to try with the aligned retrieval); a
+ * host-memory form; n_total > 2^16.  tools/bench_extract.py times the call beside one aligned retrieval call per resident level size
+ * on the same stores (profiles/r23_a_extract.jsonl, DESIGN s4: one file of 2^15 blocks x 128, every level resident, in 4.4 ms (KZG) /
+ * 11.8 ms (IPA) against 8.1 / 19.6 ms for the fifteen calls, which merge nothing and skip level 0; one run, wide spread). */
+#define PORLA_EXTRACT_REQ_BYTES 104   /* sizeof(porla_extract_req) on LP64; the library static_asserts it and each offset */
+#define PORLA_EXTRACT_FOUND    1   /* the slot holds a copy taken from a level whose rows all checked OK */
+#define PORLA_EXTRACT_UNSURE   2   /* a level with a failed row could hold a newer copy of this slot */
+#define PORLA_EXTRACT_RESIDUE  4   /* the copy comes from a RESIDUE32 top level: chunks mod p_icc */
+typedef struct {
+    unsigned long long  write_step;   /*  0: the server's counter; t = write_step % n_total */
+    void *const        *data_x;       /*  8: HOST array of log2(n_total) DEVICE pointers: level i's data store as porla_update_req lays it
+                                             out; the first 2^i rows (the resident X half) are read.  Entries of non-resident levels are ignored */
+    void *const        *mac_x;        /* 16: the same for the MAC stores */
+    const void         *d_top_rows;   /* 24: the top level's X half, n_total rows in top_form; NULL = no top level */
+    const void         *d_top_macs;   /* 32 */
+    const void         *d_top_align;  /* 40: NULL = every alignment at infinity */
+    const void         *d_prf;        /* 48: 16 raw bytes per resident row, read as porla_retrieve_req.d_prf is read: resident levels in
+                                             ascending order, 2^i values each, then n_total values for the top level if there is one */
+    void               *d_work;       /* 56: t x n_cols x 32 bytes of scratch for the decoded lower levels */
+    void               *d_blocks;     /* 64: n_total x n_cols x 32 bytes: slot b = block index b + 1 */
+    unsigned int       *d_steps;      /* 72: n_total words: the epoch write step of the copy taken, 0 = top level, 0xffffffff = none */
+    unsigned char      *d_flags;      /* 80: n_total bytes of the PORLA_EXTRACT_* bits */
+    unsigned char      *d_row_status; /* 88: one byte per resident row, laid out like d_prf: PORLA_RETRIEVE_ROW_OK or 0 */
+    unsigned int       *d_counts;     /* 96: four words or NULL, zeroed by the call */
+} porla_extract_req;
+int porla_kzg_extract_batch_device(const porla_extract_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
+int porla_ipa_extract_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t alpha_be[32],
+                                   const porla_extract_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
+
 /* ---- AES on the device: the MAC PRF of the client writes, the audit challenge from its seed, the client's complement scalar ----
  * These calls PRODUCE the buffers the batches above consume (d_prf; d_idx* / d_coef* / d_mac_*; the 32-byte scalars of
  * porla_kzg_complement_batch_device or of a one-point fixed base) and change none of them.  Both uses are standard AES-128

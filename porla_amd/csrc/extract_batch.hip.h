@@ -1,0 +1,141 @@
+// Kernels of the verified file extraction (extract_batch.hip: porla_{kzg,ipa}_extract_batch_device): every resident level of K files
+// is checked row by row, its X half decoded, and the decoded blocks merged per slot by "newest authentic copy wins".
+//
+// The row check is the aligned retrieval's (retrieve_batch.hip.h) with another row -> request map: a request is ONE HALF (one level of
+// one file), the halves differ in size, and RtMapStarts finds a row's half by a binary search in the halves' start rows.  The check's
+// kernels are k_rt_eval_lazy, k_rt_eval_horner, k_rt_pack, k_rt_compare and k_rt_compare_aligned instantiated with that map
+// (retrieve_batch.hip launches them), so a status byte is what the retrieval calls write for the same row.
+//
+// The layout the merge works in, per file, t = write_step % n_total: the resident lower levels are the set bits of t, in ascending
+// order, level i at offset o_i = t & (2^i - 1) with 2^i entries -- the row statuses (then the top level's n_total rows at offset t), the
+// PRF values, and the decoded blocks in d_work all lie that way.  Entry o_i + p of level i is the block of epoch write step
+// (t with bits 0 .. i cleared) + 1 + p, and the level's highest step is hi_i = t with the bits below i cleared.  The other way round
+// step s, 1 .. t, lies in level i = the highest bit in which s - 1 and t differ, at p = (s - 1) & (2^i - 1).
+// Ranks travel as rank + 1 in d_steps (0 = no candidate; a clean top level's blocks are candidates of rank 0), so that one atomicMax per
+// decoded block picks the winner; k_ex_gather writes the documented values at the end.
+#pragma once
+#include "retrieve_batch.hip.h"
+#include "../../include/porla_gpu.h"
+
+namespace porla {
+
+// ---- the merge.  One file as its kernels see it
+struct ExFile {
+    const uint8_t* level0;     // level 0's one row of 64-byte symbols, or nullptr: not resident
+    const uint8_t* status;     // d_row_status
+    uint8_t* work;             // d_work
+    uint8_t* blocks;           // d_blocks: a clean top level has been decoded into it
+    uint32_t* steps;           // d_steps
+    uint8_t* flags;            // d_flags
+    uint32_t* counts;          // d_counts or nullptr
+    uint32_t* scratch;         // EX_SCRATCH_WORDS words of the call's workspace: [0] the failed-level mask (bit i = level i, bit log2
+                               // n_total = the top level), [1 + s] the bad-symbol count of the decode of 2^s rows
+    uint32_t t;                // write_step % n_total
+    uint32_t has_top;
+};
+constexpr int EX_SCRATCH_WORDS = 20;
+static_assert(sizeof(ExFile) == 72, "ExFile: eight pointers and two words");
+
+// the level of entry r < t of a file's ascending layout, and the entry's place in the level
+__device__ __forceinline__ uint32_t ex_level_of_entry(uint32_t t, uint32_t r, uint32_t& p) {
+    uint32_t rest = t, off = 0;
+    for (;;) {
+        const uint32_t i = (uint32_t)__ffs((int)rest) - 1u;
+        if (r < off + (1u << i) || (rest & (rest - 1u)) == 0u) { p = r - off; return i; }
+        off += 1u << i;
+        rest &= rest - 1u;
+    }
+}
+
+// counters, failed-level mask, decode counters and the ranks of every slot: zero
+__global__ void __launch_bounds__(256)
+k_ex_clear(const ExFile* __restrict__ files, uint32_t n_total) {
+    const ExFile& F = files[blockIdx.y];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_total) F.steps[i] = 0;
+    if (i < (uint32_t)EX_SCRATCH_WORDS) F.scratch[i] = 0;
+    if (i < 4u && F.counts) F.counts[i] = 0;
+}
+
+// level 0: one row, the decode is the identity on the low 32 bytes of each symbol; a nonzero upper half is a bad symbol
+__global__ void __launch_bounds__(256)
+k_ex_level0(const ExFile* __restrict__ files, uint32_t ncols) {
+    const ExFile& F = files[blockIdx.y];
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (!F.level0 || c >= ncols) return;
+    const uint4* s = reinterpret_cast<const uint4*>(F.level0 + 64 * (size_t)c);
+    uint4* d = reinterpret_cast<uint4*>(F.work + 32 * (size_t)c);
+    const uint4 a = s[0], b = s[1], x = s[2], y = s[3];
+    d[0] = a;
+    d[1] = b;
+    if ((x.x | x.y | x.z | x.w | y.x | y.y | y.z | y.w) != 0u) atomicAdd(F.scratch + 1, 1u);
+}
+
+// the verdict: a lane per resident row; a row with status 0 fails its level
+__global__ void __launch_bounds__(256)
+k_ex_verdict(const ExFile* __restrict__ files, uint32_t n_total, uint32_t top_bit) {
+    const ExFile& F = files[blockIdx.y];
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t rows = F.t + (F.has_top ? n_total : 0u);
+    if (r == 0u && F.counts) {                                            // the decodes' bad symbols, summed
+        uint32_t bad = 0;
+        for (int s = 1; s < EX_SCRATCH_WORDS; s++) bad += F.scratch[s];
+        F.counts[1] = bad;
+    }
+    if (r >= rows || F.status[r] != 0) return;
+    uint32_t p;
+    atomicOr(F.scratch, 1u << (r < F.t ? ex_level_of_entry(F.t, r, p) : top_bit));
+}
+
+// rank: a lane per decoded block of a lower level; a clean level's block bids for the slot its first eight bytes name
+__global__ void __launch_bounds__(256)
+k_ex_rank(const ExFile* __restrict__ files, uint32_t n_total, uint32_t ncols) {
+    const ExFile& F = files[blockIdx.y];
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= F.t) return;
+    uint32_t p;
+    const uint32_t i = ex_level_of_entry(F.t, r, p);
+    if (F.scratch[0] >> i & 1u) return;
+    const uint2 id = *reinterpret_cast<const uint2*>(F.work + (size_t)r * ncols * 32);
+    if (id.y != 0u || id.x == 0u || id.x > n_total) {
+        if (F.counts) atomicAdd(F.counts + 2, 1u);
+        return;
+    }
+    const uint32_t step = (F.t & ~((2u << i) - 1u)) + 1u + p;
+    atomicMax(F.steps + (id.x - 1u), step + 1u);
+}
+
+// gather: a block per slot.  The winner's bytes (a top-level winner lies in d_blocks already), or zeros; step, flags, counts[3]
+__global__ void __launch_bounds__(64)
+k_ex_gather(const ExFile* __restrict__ files, uint32_t ncols, uint32_t top_bit, uint32_t residue) {
+    const ExFile& F = files[blockIdx.y];
+    const uint32_t slot = blockIdx.x, t = F.t;
+    const uint32_t failed = F.scratch[0];
+    uint32_t enc = F.steps[slot];
+    __syncthreads();                                                      // (lane 0 rewrites the word below)
+    if (enc == 0u && F.has_top && !(failed >> top_bit & 1u)) enc = 1u;
+    bool unsure = enc == 0u && F.has_top && (failed >> top_bit & 1u);     // the top level's highest step is 0 > -1 only
+    for (uint32_t rest = failed & t; rest; rest &= rest - 1u) {
+        const uint32_t i = (uint32_t)__ffs((int)rest) - 1u;
+        unsure = unsure || (uint64_t)(t & ~((1u << i) - 1u)) + 1u > enc;  // hi_i > rank
+    }
+    const size_t u4 = (size_t)ncols * 2;                                  // 16-byte words of a block
+    uint4* dst = reinterpret_cast<uint4*>(F.blocks) + (size_t)slot * u4;
+    if (enc > 1u) {
+        const uint32_t s1 = enc - 2u;                                     // step - 1
+        const uint32_t i = 31u - (uint32_t)__clz((int)(s1 ^ t));
+        const size_t entry = (size_t)(t & ((1u << i) - 1u)) + (s1 & ((1u << i) - 1u));
+        const uint4* src = reinterpret_cast<const uint4*>(F.work) + entry * u4;
+        for (size_t w = threadIdx.x; w < u4; w += blockDim.x) dst[w] = src[w];
+    } else if (enc == 0u) {
+        for (size_t w = threadIdx.x; w < u4; w += blockDim.x) dst[w] = make_uint4(0, 0, 0, 0);
+    }
+    if (threadIdx.x == 0u) {
+        F.steps[slot] = enc ? enc - 1u : 0xffffffffu;
+        F.flags[slot] = (uint8_t)((enc ? PORLA_EXTRACT_FOUND : 0) | (unsure ? PORLA_EXTRACT_UNSURE : 0) |
+                                  (enc == 1u && residue ? PORLA_EXTRACT_RESIDUE : 0));
+        if ((enc == 0u || unsure) && F.counts) atomicAdd(F.counts + 3, 1u);
+    }
+}
+
+}  // namespace porla

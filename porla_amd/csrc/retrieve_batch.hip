@@ -15,6 +15,8 @@
 //     or k_rt_compare_aligned   when a request of the call has a d_align: ... minus alpha * A_j first (a quad of lanes per row)
 //   the data decode in the call's form (icc_decode.hip: icc_decode_form_enqueue) of the requests that have a d_out; EXACT: d_bad =
 //   d_counts + 1
+// The check between k_rt_clear and the decode is rt_check_rows, written over the kernels' row -> request map: the retrieval calls run
+// it with RtMapShift, the file extraction (extract_batch.hip) through rt_check_starts_{kzg,ipa} with RtMapStarts on halves of unequal sizes.
 #include "retrieve_batch.hip.h"
 #include "write_batch_host.hpp"
 #include "../../include/porla_gpu.h"
@@ -124,7 +126,8 @@ static int rt_check(const char* who, const RtReqs& reqs, size_t k, size_t n_rows
 // the table of (G1[0], h_MAC), under the state's and the table's mutexes and the tables' fences as client_batch_device takes them
 // symb: the symbol width of the rows.  alpha_sc (or nullptr): the key as the plain scalar of the aligned compare's ladder, read under
 // the same lock as the evaluation's
-static int rt_kzg_expected(const RtDesc* d_desc, int n_rows_log, size_t rows, size_t n_coeffs, size_t symb, uint8_t* d_exp, uint32_t* alpha_sc,
+template <class Map>
+static int rt_kzg_expected(const RtDesc* d_desc, const Map& map, size_t rows, size_t n_coeffs, size_t symb, uint8_t* d_exp, uint32_t* alpha_sc,
                            hipStream_t stream) {
     using Fr = Bn254Fr;
     int rc;
@@ -157,17 +160,17 @@ static int rt_kzg_expected(const RtDesc* d_desc, int n_rows_log, size_t rows, si
         KzgAlpha270 A;
         kzg_to270(g_kzg.alpha, A.w);
         static LdsOnce once;                                         // dynamic LDS above 64 KiB (more than 682 coefficients): told once per device
-        once.set({lds_kernel(&k_rt_eval_lazy<64>, (size_t)KZG_LAZY_MAX_COEFFS * entry_words * 4),
-                  lds_kernel(&k_rt_eval_lazy<32>, (size_t)KZG_LAZY_MAX_COEFFS * entry_words * 2)});
+        once.set({lds_kernel(&k_rt_eval_lazy<64, Map>, (size_t)KZG_LAZY_MAX_COEFFS * entry_words * 4),
+                  lds_kernel(&k_rt_eval_lazy<32, Map>, (size_t)KZG_LAZY_MAX_COEFFS * entry_words * 2)});
         ProfScope ps("retrieve_eval", stream);
         constexpr size_t lazy_grid = 2048;                           // k_kzg_eval_rows_lazy's
         const size_t groups = (rows + 31) / 32;
         const dim3 grid((unsigned)std::min(groups, lazy_grid));
         if (symb == 64)
-            hipLaunchKernelGGL(k_rt_eval_lazy<64>, grid, dim3(256), (size_t)entries * entry_words * 4, stream, d_desc, (uint32_t)n_rows_log,
+            hipLaunchKernelGGL((k_rt_eval_lazy<64, Map>), grid, dim3(256), (size_t)entries * entry_words * 4, stream, d_desc, map,
                                (uint32_t)rows, nc, (const uint32_t*)kd->d_tau29w.p, A, (uint8_t*)kd->d_eval.p);
         else                                                         // (the tau^i half of every entry of the same table)
-            hipLaunchKernelGGL(k_rt_eval_lazy<32>, grid, dim3(256), (size_t)entries * entry_words * 2, stream, d_desc, (uint32_t)n_rows_log,
+            hipLaunchKernelGGL((k_rt_eval_lazy<32, Map>), grid, dim3(256), (size_t)entries * entry_words * 2, stream, d_desc, map,
                                (uint32_t)rows, nc, (const uint32_t*)kd->d_tau29w.p, A, (uint8_t*)kd->d_eval.p);
     } else {
         KzgEvalConsts K;
@@ -178,10 +181,10 @@ static int rt_kzg_expected(const RtDesc* d_desc, int n_rows_log, size_t rows, si
         ProfScope ps("retrieve_eval", stream);
         const dim3 grid((unsigned)((8 * rows + 255) / 256));
         if (symb == 64)
-            hipLaunchKernelGGL(k_rt_eval_horner<64>, grid, dim3(256), 0, stream, d_desc, (uint32_t)n_rows_log, (uint32_t)rows, nc, K,
+            hipLaunchKernelGGL((k_rt_eval_horner<64, Map>), grid, dim3(256), 0, stream, d_desc, map, (uint32_t)rows, nc, K,
                                (uint8_t*)kd->d_eval.p);
         else
-            hipLaunchKernelGGL(k_rt_eval_horner<32>, grid, dim3(256), 0, stream, d_desc, (uint32_t)n_rows_log, (uint32_t)rows, nc, K,
+            hipLaunchKernelGGL((k_rt_eval_horner<32, Map>), grid, dim3(256), 0, stream, d_desc, map, (uint32_t)rows, nc, K,
                                (uint8_t*)kd->d_eval.p);
     }
     PORLA_HIP(hipGetLastError());
@@ -189,13 +192,73 @@ static int rt_kzg_expected(const RtDesc* d_desc, int n_rows_log, size_t rows, si
 }
 
 // the aligned compare: its dynamic LDS is the quad ladder's, told once per device
-template <class C, bool ADD>
-static void rt_compare_aligned_launch(const RtDesc* d_desc, int logn, size_t g0, size_t m, uint8_t* d_exp, const uint8_t* d_hpts,
+template <class C, bool ADD, class Map>
+static void rt_compare_aligned_launch(const RtDesc* d_desc, const Map& map, size_t g0, size_t m, uint8_t* d_exp, const uint8_t* d_hpts,
                                       const MacScalar& alpha, hipStream_t stream) {
     static LdsOnce once;
-    once.set({lds_kernel(&k_rt_compare_aligned<C, ADD>, macq_lds_bytes<C>())});
-    hipLaunchKernelGGL((k_rt_compare_aligned<C, ADD>), dim3((unsigned)((m + RT_ALIGNED_ROWS - 1) / RT_ALIGNED_ROWS)), dim3(4 * MACQ_BF),
-                       macq_lds_bytes<C>(), stream, d_desc, (uint32_t)logn, (uint32_t)g0, (uint32_t)m, d_exp, d_hpts, alpha);
+    once.set({lds_kernel(&k_rt_compare_aligned<C, ADD, Map>, macq_lds_bytes<C>())});
+    hipLaunchKernelGGL((k_rt_compare_aligned<C, ADD, Map>), dim3((unsigned)((m + RT_ALIGNED_ROWS - 1) / RT_ALIGNED_ROWS)), dim3(4 * MACQ_BF),
+                       macq_lds_bytes<C>(), stream, d_desc, map, (uint32_t)g0, (uint32_t)m, d_exp, d_hpts, alpha);
+}
+
+// the IPA build's rows of one group (all of them while their coefficient rows fit the bound); the KZG build takes all rows at once
+template <class C>
+static size_t rt_group_rows(size_t rows, size_t ncols) {
+    return std::is_same<C, Bn254G1>::value ? rows : std::min(rows, std::max<size_t>(RT_COEFF_BYTES / (ncols * 32), 1));
+}
+// the workspace of a check of `rows` rows
+template <class C>
+static int rt_ensure(RetrieveWs* ws, size_t rows, size_t ncols) {
+    int rc;
+    const size_t group = rt_group_rows<C>(rows, ncols);
+    if ((rc = ws->exp.ensure(group * 64))) return rc;
+    if (!std::is_same<C, Bn254G1>::value) {
+        if ((rc = ws->coeffs.ensure(group * ncols * 32))) return rc;
+        if ((rc = ws->scalars.ensure(group * 32))) return rc;
+        if ((rc = ws->hpts.ensure(group * 64))) return rc;
+    }
+    return PORLA_OK;
+}
+
+// The check of the rows 0 .. rows - 1 of the requests at d_desc under `map`: expected MACs, then the compare -> status bytes, failures
+// counted.  ws->mu held, ws->fence entered, rt_ensure done.  alpha: the IPA build's, for the aligned compare (the KZG build reads its key)
+template <class C, class Map>
+static int rt_check_rows(RetrieveWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* fb_h, MacScalar alpha, bool aligned, const RtDesc* d_desc,
+                         const Map& map, size_t rows, size_t ncols, size_t symb, hipStream_t stream) {
+    using Q = typename IccCurve<C>::Q;
+    constexpr bool kzg = std::is_same<C, Bn254G1>::value;
+    int rc;
+    const size_t group = rt_group_rows<C>(rows, ncols);
+    uint8_t* d_exp = (uint8_t*)ws->exp.p;
+    for (size_t g0 = 0; g0 < rows; g0 += group) {
+        const size_t m = std::min(group, rows - g0);
+        if constexpr (kzg) {
+            if ((rc = rt_kzg_expected(d_desc, map, rows, ncols, symb, d_exp, aligned ? alpha.v : nullptr, stream))) return rc;
+        } else {
+            {
+                ProfScope ps("retrieve_pack", stream);
+                const size_t items = m * ncols + m;
+                const dim3 grid((unsigned)((items + 255) / 256));
+                if (symb == 64)
+                    hipLaunchKernelGGL((k_rt_pack<Q, 64, Map>), grid, dim3(256), 0, stream, d_desc, map, (uint32_t)g0, (uint32_t)m,
+                                       (uint32_t)ncols, (uint8_t*)ws->coeffs.p, (uint8_t*)ws->scalars.p);
+                else
+                    hipLaunchKernelGGL((k_rt_pack<Q, 32, Map>), grid, dim3(256), 0, stream, d_desc, map, (uint32_t)g0, (uint32_t)m,
+                                       (uint32_t)ncols, (uint8_t*)ws->coeffs.p, (uint8_t*)ws->scalars.p);
+                PORLA_HIP(hipGetLastError());
+            }
+            if ((rc = client_block_pass<C>(fb_alpha, (const uint8_t*)ws->coeffs.p, m, ncols, d_exp, stream))) return rc;
+            if ((rc = client_h_pass<C>(fb_h, (const uint8_t*)ws->scalars.p, m, (uint8_t*)ws->hpts.p, stream))) return rc;
+        }
+        ProfScope ps("retrieve_compare", stream);
+        if (aligned)
+            rt_compare_aligned_launch<C, !kzg>(d_desc, map, g0, m, d_exp, (const uint8_t*)ws->hpts.p, alpha, stream);
+        else
+            hipLaunchKernelGGL((k_rt_compare<C, !kzg, Map>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, stream, d_desc, map,
+                               (uint32_t)g0, (uint32_t)m, d_exp, (const uint8_t*)ws->hpts.p);
+        PORLA_HIP(hipGetLastError());
+    }
+    return PORLA_OK;
 }
 
 // ws->mu held, ws->fence entered; arguments checked.  fb_alpha == nullptr: the KZG build (the resident key, SRS and hiding base).
@@ -203,7 +266,6 @@ static void rt_compare_aligned_launch(const RtDesc* d_desc, int logn, size_t g0,
 template <class C>
 static int rt_enqueue(RetrieveWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* fb_h, const uint32_t* alpha_ipa, const RtReqs& reqs, size_t k,
                       size_t n_rows, size_t ncols, size_t n_total, int form, hipStream_t stream) {
-    using Q = typename IccCurve<C>::Q;
     constexpr bool kzg = std::is_same<C, Bn254G1>::value;
     int rc;
     const int logn = ilog2u(n_rows);
@@ -211,16 +273,9 @@ static int rt_enqueue(RetrieveWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* fb_h
     static_assert(sizeof(RtDesc) == sizeof(porla_retrieve_aligned_req), "the requests are uploaded in the aligned call's layout");
     const size_t symb = rt_symbol_bytes(form);
     bool aligned = false;                                                // a request with an alignment store: the quad compare
-    // IPA: the rows of one group (all of them while their coefficient rows fit the bound)
-    const size_t group = kzg ? rows : std::min(rows, std::max<size_t>(RT_COEFF_BYTES / (ncols * 32), 1));
     if ((rc = ws->h_list.stage(desc_b))) return rc;
     if ((rc = ws->list.ensure(desc_b))) return rc;
-    if ((rc = ws->exp.ensure(group * 64))) return rc;
-    if (!kzg) {
-        if ((rc = ws->coeffs.ensure(group * ncols * 32))) return rc;
-        if ((rc = ws->scalars.ensure(group * 32))) return rc;
-        if ((rc = ws->hpts.ensure(group * 64))) return rc;
-    }
+    if ((rc = rt_ensure<C>(ws, rows, ncols))) return rc;
     for (size_t a = 0; a < k; a++) {
         const porla_retrieve_aligned_req R = reqs.at(a);
         aligned = aligned || R.d_align;
@@ -230,37 +285,9 @@ static int rt_enqueue(RetrieveWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* fb_h
     MacScalar alpha{};
     if (!kzg && aligned) memcpy(alpha.v, alpha_ipa, sizeof(alpha.v));
     const RtDesc* d_desc = (const RtDesc*)ws->list.p;
-    uint8_t* d_exp = (uint8_t*)ws->exp.p;
     hipLaunchKernelGGL(k_rt_clear, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, stream, d_desc, (uint32_t)k);
     PORLA_HIP(hipGetLastError());
-    for (size_t g0 = 0; g0 < rows; g0 += group) {
-        const size_t m = std::min(group, rows - g0);
-        if constexpr (kzg) {
-            if ((rc = rt_kzg_expected(d_desc, logn, rows, ncols, symb, d_exp, aligned ? alpha.v : nullptr, stream))) return rc;
-        } else {
-            {
-                ProfScope ps("retrieve_pack", stream);
-                const size_t items = m * ncols + m;
-                const dim3 grid((unsigned)((items + 255) / 256));
-                if (symb == 64)
-                    hipLaunchKernelGGL((k_rt_pack<Q, 64>), grid, dim3(256), 0, stream, d_desc, (uint32_t)logn, (uint32_t)g0, (uint32_t)m,
-                                       (uint32_t)ncols, (uint8_t*)ws->coeffs.p, (uint8_t*)ws->scalars.p);
-                else
-                    hipLaunchKernelGGL((k_rt_pack<Q, 32>), grid, dim3(256), 0, stream, d_desc, (uint32_t)logn, (uint32_t)g0, (uint32_t)m,
-                                       (uint32_t)ncols, (uint8_t*)ws->coeffs.p, (uint8_t*)ws->scalars.p);
-                PORLA_HIP(hipGetLastError());
-            }
-            if ((rc = client_block_pass<C>(fb_alpha, (const uint8_t*)ws->coeffs.p, m, ncols, d_exp, stream))) return rc;
-            if ((rc = client_h_pass<C>(fb_h, (const uint8_t*)ws->scalars.p, m, (uint8_t*)ws->hpts.p, stream))) return rc;
-        }
-        ProfScope ps("retrieve_compare", stream);
-        if (aligned)
-            rt_compare_aligned_launch<C, !kzg>(d_desc, logn, g0, m, d_exp, (const uint8_t*)ws->hpts.p, alpha, stream);
-        else
-            hipLaunchKernelGGL((k_rt_compare<C, !kzg>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, stream, d_desc, (uint32_t)logn,
-                               (uint32_t)g0, (uint32_t)m, d_exp, (const uint8_t*)ws->hpts.p);
-        PORLA_HIP(hipGetLastError());
-    }
+    if ((rc = rt_check_rows<C>(ws, fb_alpha, fb_h, alpha, aligned, d_desc, RtMapShift{(uint32_t)logn}, rows, ncols, symb, stream))) return rc;
     // the data decode of the requests that want their blocks, whatever the statuses are
     std::vector<porla_icc_decode_req> dec;
     dec.reserve(k);
@@ -271,6 +298,29 @@ static int rt_enqueue(RetrieveWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* fb_h
     }
     if (dec.empty()) return PORLA_OK;
     return icc_decode_form_enqueue(dec.data(), dec.size(), n_rows, ncols, n_total, IccCurve<C>::id, form, stream);
+}
+
+// The same check for halves of unequal sizes (the extraction, extract_batch.hip): the requests at d_desc, row numbering by `map`,
+// `rows` rows of `symb`-byte symbols; under this file's workspace, its lock and fence
+template <class C>
+static int rt_check_starts(FixedBase<C>* fb_alpha, FixedBase<C>* fb_h, const uint32_t* alpha_ipa, bool aligned, const RtDesc* d_desc,
+                           const RtMapStarts& map, size_t rows, size_t ncols, size_t symb, hipStream_t stream) {
+    RetrieveWs* ws = nullptr;
+    int rc;
+    if ((rc = g_rt_ws.get(&ws))) return rc;
+    MacScalar alpha{};
+    if (alpha_ipa && aligned) memcpy(alpha.v, alpha_ipa, sizeof(alpha.v));
+    return FencedCall(ws, stream).run([&] {
+        if (int r = rt_ensure<C>(ws, rows, ncols)) return r;
+        return rt_check_rows<C>(ws, fb_alpha, fb_h, alpha, aligned, d_desc, map, rows, ncols, symb, stream);
+    });
+}
+int rt_check_starts_kzg(bool aligned, const RtDesc* d_desc, const RtMapStarts& map, size_t rows, size_t ncols, size_t symb, hipStream_t stream) {
+    return rt_check_starts<Bn254G1>(nullptr, nullptr, nullptr, aligned, d_desc, map, rows, ncols, symb, stream);
+}
+int rt_check_starts_ipa(porla_fixed_base* alpha_generators_fb, porla_fixed_base* h_fb, const uint32_t alpha[8], bool aligned, const RtDesc* d_desc,
+                        const RtMapStarts& map, size_t rows, size_t symb, hipStream_t stream) {
+    return rt_check_starts<Secp256k1G>(&alpha_generators_fb->secp, &h_fb->secp, alpha, aligned, d_desc, map, rows, IPA_COLS, symb, stream);
 }
 
 // one level from host memory: upload, the batch of one request on the engine's stream, download; `run` enqueues that batch

@@ -9,7 +9,8 @@
 // k_rt_eval_horner for a long SRS) and the expected MAC a two-coefficient commitment against (G1[0], h_MAC).  IPA: the row's 128
 // symbols reduced mod n are one commitment row against the alpha generators (k_rt_pack), the PRF value one row of the hiding base.
 // k_rt_compare sets the status bytes from the expected MACs' canonical affine bytes.  The rows of all K requests are numbered through,
-// g = request * n_rows + row, and a kernel finds its request by a shift.
+// g = request * n_rows + row, and a kernel finds its request by a shift (RtMapShift below; the file extraction's instances of the same
+// kernels, whose requests differ in size, search for it: RtMapStarts).
 //
 // The aligned call: a half that holds residues mod p_icc only (the Y rows of HAdd / HRebuildY, the 32-byte aligned top level) keeps
 // MAC[j] + alpha * align[j] == alpha * Commit(row_j mod q), with row_j the STORED symbol reduced mod q, so its MAC row j is
@@ -39,12 +40,37 @@ struct RtDesc {
 };
 static_assert(sizeof(RtDesc) == 64, "RtDesc: eight pointers");
 
-// the call zeroes both counters of every request that has them
-__global__ void __launch_bounds__(256)
+// the call zeroes both counters of every request that has them (static: the header is read by more than one file)
+static __global__ void __launch_bounds__(256)
 k_rt_clear(const RtDesc* __restrict__ desc, uint32_t k) {
     const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a < k && desc[a].counts) { desc[a].counts[0] = 0; desc[a].counts[1] = 0; }
 }
+
+// The row -> request map of a launch, a template parameter of the kernels below.  The rows of a call are numbered through; find(g, jr)
+// gives the request of row g and sets jr to its row there.  RtMapShift (the default): every request has 2^n_rows_log rows -- the
+// retrieval calls, whose kernels these instances are.  RtMapStarts: request a starts at row starts[a] (ascending from 0, n of them) and
+// the requests may differ in size -- a binary search; the instances of the extraction (extract_batch.hip).
+struct RtMapShift {
+    uint32_t n_rows_log;
+    __device__ __forceinline__ uint32_t find(uint32_t g, uint32_t& jr) const {
+        jr = g & ((1u << n_rows_log) - 1u);
+        return g >> n_rows_log;
+    }
+};
+struct RtMapStarts {
+    const uint32_t* starts;
+    uint32_t n;
+    __device__ __forceinline__ uint32_t find(uint32_t g, uint32_t& jr) const {
+        uint32_t lo = 0, hi = n;
+        while (hi - lo > 1u) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (starts[mid] <= g) lo = mid; else hi = mid;
+        }
+        jr = g - starts[lo];
+        return lo;
+    }
+};
 
 // 64-byte little-endian symbol -> its residue mod q in the plain stream, unreduced: hi * (2^256 in the 2^270 form) -- below q + 2^242
 // -- plus the raw lower half, below 2^258 (icc30_load_symbol's q part)
@@ -77,9 +103,9 @@ template <int SYMB> constexpr int rt_lazy_group() { return SYMB == 64 ? 3 : 6; }
 constexpr int RT_LAZY_ENTRY_U4 = 2 * KZG_LAZY_ENTRY_WORDS / 4;                          // an entry of the resident table: both powers
 template <int SYMB> constexpr int rt_lazy_lds_u4() { return SYMB / 32 * KZG_LAZY_ENTRY_WORDS / 4; }   // ... and what of it is staged
 
-template <int SYMB>
+template <int SYMB, class Map = RtMapShift>
 __global__ void __launch_bounds__(256)
-k_rt_eval_lazy(const RtDesc* __restrict__ desc, uint32_t n_rows_log, uint32_t total_rows, uint32_t n_coeffs,
+k_rt_eval_lazy(const RtDesc* __restrict__ desc, const Map map, uint32_t total_rows, uint32_t n_coeffs,
                const uint32_t* __restrict__ tau29w, KzgAlpha270 A, uint8_t* __restrict__ out) {
     using Q = IccBn254Fr;
     extern __shared__ uint4 rt_lds_tau[];
@@ -96,8 +122,8 @@ k_rt_eval_lazy(const RtDesc* __restrict__ desc, uint32_t n_rows_log, uint32_t to
         const size_t rr = r0 + (threadIdx.x >> 3);
         const bool live = rr < total_rows;
         const uint32_t g = live ? (uint32_t)rr : total_rows - 1;        // idle lanes redo the last row (the lane sum below is wave-wide)
-        const RtDesc& D = desc[g >> n_rows_log];
-        const uint32_t jr = g & ((1u << n_rows_log) - 1u);
+        uint32_t jr;
+        const RtDesc& D = desc[map.find(g, jr)];
         const uint8_t* row = D.rows + (size_t)jr * n_coeffs * SYMB;
         uint64_t col[19];
 #pragma unroll
@@ -143,17 +169,17 @@ k_rt_eval_lazy(const RtDesc* __restrict__ desc, uint32_t n_rows_log, uint32_t to
 // The same for an SRS longer than KZG_LAZY_MAX_COEFFS: the Horner form of k_kzg_eval_rows30 with the symbol reduced to the plain stream
 // on load (one product).  Bounds: the symbol is below 2^258, acc = acc tau^8 + symbol < r + 2^250 + 2^258 < 2^259 at every step, the
 // lane sum of the eight products with tau^j below 2^258.  SYMB == 32: the symbol is loaded as it is, below 2^256: the same bounds.
-template <int SYMB>
+template <int SYMB, class Map = RtMapShift>
 __global__ void __launch_bounds__(256)
-k_rt_eval_horner(const RtDesc* __restrict__ desc, uint32_t n_rows_log, uint32_t total_rows, uint32_t n_coeffs, KzgEvalConsts K,
+k_rt_eval_horner(const RtDesc* __restrict__ desc, const Map map, uint32_t total_rows, uint32_t n_coeffs, KzgEvalConsts K,
                  uint8_t* __restrict__ out) {
     using Q = IccBn254Fr;
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;       // (eight lanes per row: 2^29 rows and more pass 32 bits)
     const uint32_t j = (uint32_t)t & 7u;
     const bool live = (t >> 3) < total_rows;
     const uint32_t g = live ? (uint32_t)(t >> 3) : total_rows - 1;      // idle lanes redo the last row (the lane sum is wave-wide)
-    const RtDesc& D = desc[g >> n_rows_log];
-    const uint32_t jr = g & ((1u << n_rows_log) - 1u);
+    uint32_t jr;
+    const RtDesc& D = desc[map.find(g, jr)];
     const uint8_t* row = D.rows + (size_t)jr * n_coeffs * SYMB;
     const F30<Q> T8 = f30_unpack<Q>(K.t8);
     F30<Q> acc;
@@ -182,22 +208,22 @@ k_rt_eval_horner(const RtDesc* __restrict__ desc, uint32_t n_rows_log, uint32_t 
 // big-endian coefficient client_block_pass takes; then a lane per row: its PRF value as the scalar row of the h pass (cr_prf /
 // cr_store_row: the client rebuild's reading of d_prf for the IPA build, r.d[0], r.d[1] as little-endian words).  SYMB == 32: a symbol
 // below p_icc is still reduced mod n -- two different 256-bit moduli.
-template <class Q, int SYMB>
+template <class Q, int SYMB, class Map = RtMapShift>
 __global__ void __launch_bounds__(256)
-k_rt_pack(const RtDesc* __restrict__ desc, uint32_t n_rows_log, uint32_t g0, uint32_t rows, uint32_t ncols, uint8_t* __restrict__ coeffs,
+k_rt_pack(const RtDesc* __restrict__ desc, const Map map, uint32_t g0, uint32_t rows, uint32_t ncols, uint8_t* __restrict__ coeffs,
           uint8_t* __restrict__ scalars) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t symbols = (size_t)rows * ncols;
-    const uint32_t mask = (1u << n_rows_log) - 1u;
+    uint32_t jr;
     if (t < symbols) {
         const uint32_t gl = (uint32_t)(t / ncols), c = (uint32_t)(t - (size_t)gl * ncols), g = g0 + gl;
-        const RtDesc& D = desc[g >> n_rows_log];
-        const F30<Q> v = rt_symbol_mod_q<Q, SYMB>(D.rows + (size_t)SYMB * ((size_t)(g & mask) * ncols + c));
+        const RtDesc& D = desc[map.find(g, jr)];
+        const F30<Q> v = rt_symbol_mod_q<Q, SYMB>(D.rows + (size_t)SYMB * ((size_t)jr * ncols + c));
         cr_store_row<Q>(coeffs + 32 * t, icc30_canonical<Q>(icc30_reduce_top<Q>(v)));
     } else if (t - symbols < rows) {
         const uint32_t gl = (uint32_t)(t - symbols), g = g0 + gl;
-        const RtDesc& D = desc[g >> n_rows_log];
-        cr_store_row<Q>(scalars + 32 * (size_t)gl, cr_prf<Q, true>(D.prf, g & mask));
+        const RtDesc& D = desc[map.find(g, jr)];
+        cr_store_row<Q>(scalars + 32 * (size_t)gl, cr_prf<Q, true>(D.prf, jr));
     }
 }
 
@@ -219,12 +245,12 @@ __device__ __forceinline__ void rt_compare_bytes(const RtDesc& D, uint32_t jr, c
     if (diff && D.counts) atomicAdd(D.counts, 1u);
 }
 // row g0 + gl on the calling lane
-template <class C, bool ADD>
-__device__ __forceinline__ void rt_compare_row(const RtDesc* __restrict__ desc, uint32_t n_rows_log, uint32_t g0, uint32_t gl,
+template <class C, bool ADD, class Map>
+__device__ __forceinline__ void rt_compare_row(const RtDesc* __restrict__ desc, const Map map, uint32_t g0, uint32_t gl,
                                                uint8_t* __restrict__ exp, const uint8_t* __restrict__ hpts) {
     using M = typename C::Fp;
-    const uint32_t g = g0 + gl, jr = g & ((1u << n_rows_log) - 1u);
-    const RtDesc& D = desc[g >> n_rows_log];
+    uint32_t jr;
+    const RtDesc& D = desc[map.find(g0 + gl, jr)];
     uint8_t* mine = exp + 64 * (size_t)gl;
     if constexpr (ADD) {
         XYZZ<M> a = load_affine_be_lazy<M>(mine);
@@ -234,13 +260,13 @@ __device__ __forceinline__ void rt_compare_row(const RtDesc* __restrict__ desc, 
     }
     rt_compare_bytes(D, jr, mine);
 }
-template <class C, bool ADD>
+template <class C, bool ADD, class Map = RtMapShift>
 __global__ void __launch_bounds__(64)
-k_rt_compare(const RtDesc* __restrict__ desc, uint32_t n_rows_log, uint32_t g0, uint32_t rows, uint8_t* __restrict__ exp,
+k_rt_compare(const RtDesc* __restrict__ desc, const Map map, uint32_t g0, uint32_t rows, uint8_t* __restrict__ exp,
              const uint8_t* __restrict__ hpts) {
     const size_t gl64 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gl64 >= rows) return;
-    rt_compare_row<C, ADD>(desc, n_rows_log, g0, (uint32_t)gl64, exp, hpts);
+    rt_compare_row<C, ADD>(desc, map, g0, (uint32_t)gl64, exp, hpts);
 }
 
 // ---- the aligned compare: a QUAD per row, RT_ALIGNED_ROWS = MACQ_BF rows per block of 256 lanes.  The stored MAC row must equal
@@ -256,17 +282,18 @@ k_rt_compare(const RtDesc* __restrict__ desc, uint32_t n_rows_log, uint32_t g0, 
 // ladder's path and gets the same answer there.)  Padding quads (rows beyond the last) hold infinity on both sides -- row 0's expected
 // bytes may be in the middle of being rewritten by that row's own quad -- so they leave the ladder at once, and store nothing.
 constexpr int RT_ALIGNED_ROWS = MACQ_BF;
-template <class C, bool ADD>
+template <class C, bool ADD, class Map = RtMapShift>
 __global__ void __launch_bounds__(4 * MACQ_BF) MACQ_GUEST_ATTR
-k_rt_compare_aligned(const RtDesc* __restrict__ desc, uint32_t n_rows_log, uint32_t g0, uint32_t rows, uint8_t* __restrict__ exp,
+k_rt_compare_aligned(const RtDesc* __restrict__ desc, const Map map, uint32_t g0, uint32_t rows, uint8_t* __restrict__ exp,
                      const uint8_t* __restrict__ hpts, MacScalar alpha) {
     using M = typename C::Fp;
     MACQ_LDS(L);
     const uint32_t q = threadIdx.x >> 2, r = threadIdx.x & 3u, lane = threadIdx.x & 63u;
     const size_t gl64 = (size_t)blockIdx.x * MACQ_BF + q;
     const bool valid = gl64 < rows;
-    const uint32_t gl = valid ? (uint32_t)gl64 : 0u, g = g0 + gl, jr = g & ((1u << n_rows_log) - 1u);
-    const RtDesc& D = desc[g >> n_rows_log];
+    const uint32_t gl = valid ? (uint32_t)gl64 : 0u;
+    uint32_t jr;
+    const RtDesc& D = desc[map.find(g0 + gl, jr)];
     const uint8_t* ap = D.align ? D.align + 64 * (size_t)jr : nullptr;
     bool finite = false;
     if (valid && ap) {                                                     // lane r looks at its quarter of the row
@@ -275,7 +302,7 @@ k_rt_compare_aligned(const RtDesc* __restrict__ desc, uint32_t n_rows_log, uint3
     }
     if (!__syncthreads_or(finite)) {
         const size_t mine64 = (size_t)blockIdx.x * MACQ_BF + threadIdx.x;
-        if (threadIdx.x < (uint32_t)MACQ_BF && mine64 < rows) rt_compare_row<C, ADD>(desc, n_rows_log, g0, (uint32_t)mine64, exp, hpts);
+        if (threadIdx.x < (uint32_t)MACQ_BF && mine64 < rows) rt_compare_row<C, ADD>(desc, map, g0, (uint32_t)mine64, exp, hpts);
         return;
     }
     uint8_t* mine = exp + 64 * (size_t)gl;

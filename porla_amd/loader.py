@@ -130,6 +130,20 @@ PORLA_RETRIEVE_ALIGNED_REQ_BYTES = 64
 assert ctypes.sizeof(RetrieveAlignedReq) == PORLA_RETRIEVE_ALIGNED_REQ_BYTES
 
 
+class ExtractReq(ctypes.Structure):
+    """porla_extract_req, include/porla_gpu.h: one file of porla_kzg_extract_batch_device / porla_ipa_extract_batch_device
+    (PORLA_EXTRACT_REQ_BYTES = 104).  data_x and mac_x are HOST arrays of device pointers."""
+    _fields_ = [("write_step", ctypes.c_ulonglong), ("data_x", ctypes.c_void_p), ("mac_x", ctypes.c_void_p), ("d_top_rows", ctypes.c_void_p),
+                ("d_top_macs", ctypes.c_void_p), ("d_top_align", ctypes.c_void_p), ("d_prf", ctypes.c_void_p), ("d_work", ctypes.c_void_p),
+                ("d_blocks", ctypes.c_void_p), ("d_steps", ctypes.c_void_p), ("d_flags", ctypes.c_void_p), ("d_row_status", ctypes.c_void_p),
+                ("d_counts", ctypes.c_void_p)]
+
+
+PORLA_EXTRACT_REQ_BYTES = 104
+PORLA_EXTRACT_FOUND, PORLA_EXTRACT_UNSURE, PORLA_EXTRACT_RESIDUE = 1, 2, 4
+assert ctypes.sizeof(ExtractReq) == PORLA_EXTRACT_REQ_BYTES
+
+
 class PrfRun(ctypes.Structure):
     """porla_prf_run, include/porla_gpu.h: count triples (level, index0 + t, time0 + t * time_stride) of the MAC PRF
     (PORLA_PRF_RUN_BYTES = 32)."""
@@ -327,6 +341,10 @@ def _declare(L):
     L.porla_kzg_retrieve_aligned_batch_device.restype = ctypes.c_int
     L.porla_ipa_retrieve_aligned_batch_device.argtypes = [vp, vp, u8p, ctypes.POINTER(RetrieveAlignedReq), sz, sz, sz, ctypes.c_int, vp]
     L.porla_ipa_retrieve_aligned_batch_device.restype = ctypes.c_int
+    L.porla_kzg_extract_batch_device.argtypes = [ctypes.POINTER(ExtractReq), sz, sz, ctypes.c_int, vp]
+    L.porla_kzg_extract_batch_device.restype = ctypes.c_int
+    L.porla_ipa_extract_batch_device.argtypes = [vp, vp, u8p, ctypes.POINTER(ExtractReq), sz, sz, ctypes.c_int, vp]
+    L.porla_ipa_extract_batch_device.restype = ctypes.c_int
     L.porla_kzg_retrieve_aligned_host.argtypes = [u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp, ctypes.POINTER(ctypes.c_uint)]
     L.porla_kzg_retrieve_aligned_host.restype = ctypes.c_int
     L.porla_ipa_retrieve_aligned_host.argtypes = [vp, vp, u8p, u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp,

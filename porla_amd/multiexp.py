@@ -435,6 +435,38 @@ def kzg_retrieve_aligned_batch_device(reqs, n_rows, n_total, form, stream=0):
     _check(lib.porla_kzg_retrieve_aligned_batch_device(arr, len(reqs), n_rows, n_total, RETRIEVE_FORM[form], ctypes.c_void_p(stream)))
 
 
+def extract_requests(reqs):
+    """(a ctypes array of porla_extract_req, what must stay alive beside it) from per-file tuples (write_step, data_x, mac_x, d_top_rows or
+    0, d_top_macs or 0, d_top_align or 0, d_prf, d_work or 0, d_blocks, d_steps, d_flags, d_row_status, d_counts or 0): device addresses as
+    integers; data_x and mac_x are sequences of the levels' device addresses (entries of non-resident levels may be 0), or None"""
+    from .loader import ExtractReq
+    arr = (ExtractReq * max(len(reqs), 1))()
+    keep = []
+    for i, r in enumerate(reqs):
+        if len(r) != 13:
+            raise ValueError("extract_batch_device: request %d has %d fields, want 13" % (i, len(r)))
+        fams = []
+        for fam in r[1:3]:
+            if fam is None:
+                fams.append(None)
+                continue
+            host = (ctypes.c_void_p * max(len(fam), 1))(*[p or None for p in fam])
+            keep.append(host)
+            fams.append(ctypes.cast(host, ctypes.c_void_p))
+        arr[i] = ExtractReq(r[0], fams[0], fams[1], *(x or None for x in r[3:]))
+    return arr, keep
+
+
+def kzg_extract_batch_device(reqs, n_total, top_form, stream=0):
+    """The verified file extraction of len(reqs) files in ONE asynchronous call on `stream` (porla_kzg_extract_batch_device): every
+    resident level checked row by row as kzg_retrieve_aligned_batch_device checks it, the X halves decoded, the decoded blocks merged
+    per slot by "newest authentic copy wins" -- d_blocks, d_steps, d_flags (PORLA_EXTRACT_*), d_row_status, d_counts.  top_form: "exact"
+    or "residue32", the form of the top level's X half.  `reqs`: tuples as extract_requests takes them."""
+    arr, keep = extract_requests(reqs)
+    _check(lib.porla_kzg_extract_batch_device(arr, len(reqs), n_total, RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
+    del keep
+
+
 def kzg_retrieve_aligned_host(rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None, want_blocks=True):
     """one level from host memory (porla_kzg_retrieve_aligned_host; it waits) -> what kzg_retrieve_host returns"""
     n_cols = kzg_row_coefficients()
@@ -542,6 +574,14 @@ class FixedBase:
         arr = retrieve_aligned_requests(reqs)
         _check(lib.porla_ipa_retrieve_aligned_batch_device(self.h, h_fb.h if h_fb is not None else None, _alpha_be(alpha), arr, len(reqs),
                                                            n_rows, n_total, RETRIEVE_FORM[form], ctypes.c_void_p(stream)))
+
+    def ipa_extract_batch_device(self, h_fb, alpha, reqs, n_total, top_form, stream=0):
+        """kzg_extract_batch_device for the IPA build (porla_ipa_extract_batch_device: 128 columns); self, h_fb and alpha as for
+        ipa_retrieve_aligned_batch_device."""
+        arr, keep = extract_requests(reqs)
+        _check(lib.porla_ipa_extract_batch_device(self.h, h_fb.h if h_fb is not None else None, _alpha_be(alpha), arr, len(reqs), n_total,
+                                                  RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
+        del keep
 
     def ipa_retrieve_aligned_host(self, h_fb, alpha, rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None,
                                   want_blocks=True):
