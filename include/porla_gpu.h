@@ -1098,8 +1098,8 @@ int porla_ipa_retrieve_aligned_host(porla_fixed_base *alpha_generators_fb, porla
  * two; NULL alpha_be or bases (IPA); more than 65535 requests; a byte size that overflows; any output (d_work counts as one)
  * overlapping any input or output of the call.  k = 0 returns 0; KZG without init_key + init_SRS: PORLA_ERR_STATE; valid arguments
  * without a device: PORLA_ERR_NO_DEVICE.
- * Not in this call: a level's Y half when its X half fails (the row statuses say which half to try with the aligned retrieval); a
- * host-memory form; n_total > 2^16.  tools/bench_extract.py times the call beside one aligned retrieval call per resident level size
+ * A level's Y half when its X half fails: porla_*_extract_xy_batch_device below.  Not in this call: a host-memory form; n_total >
+ * 2^16.  tools/bench_extract.py times the call beside one aligned retrieval call per resident level size
  * on the same stores (profiles/r23_a_extract.jsonl, DESIGN s4: one file of 2^15 blocks x 128, every level resident, in 4.4 ms (KZG) /
  * 11.8 ms (IPA) against 8.1 / 19.6 ms for the fifteen calls, which merge nothing and skip level 0; one run, wide spread). */
 #define PORLA_EXTRACT_REQ_BYTES 104   /* sizeof(porla_extract_req) on LP64; the library static_asserts it and each offset */
@@ -1126,6 +1126,78 @@ typedef struct {
 int porla_kzg_extract_batch_device(const porla_extract_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
 int porla_ipa_extract_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t alpha_be[32],
                                    const porla_extract_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
+
+/* ---- verified file extraction with the Y halves: a lower level whose X half fails is recovered from its second copy ----
+ * The hierarchy stores every lower level twice: the X half holds the exact symbols, the Y half chunk * wt mod p_icc with an alignment
+ * store (Server::HAdd).  The call above drops all 2^i blocks of a level with one damaged X row; this one takes the arguments of that
+ * call over porla_extract_xy_req -- porla_extract_req field for field in its first 104 bytes, then the Y stores -- and falls back to
+ * the Y half of the levels the caller names in y_levels.  The mask is the caller's because the launch shapes are fixed on the host:
+ * pass the levels an earlier extraction reported as failed, or all ones for a full scrub of both halves (which also reports damaged Y
+ * rows).  With y_levels & t == 0 every output of the call above comes back byte for byte and the Y pointers may be NULL.
+ * Steps 1 and 2 of the call above hold for the X halves and the top level.  Beside them:
+ *   1y. Y row check.  Every row of every tried Y half gets the status of porla_*_retrieve_aligned_batch_device on that half with form
+ *       PORLA_ICC_DECODE_RESIDUE64, its align_y store and its slice of d_prf_y, in d_row_status_y; the rows of untried levels get
+ *       PORLA_EXTRACT_ROW_NOT_TRIED.  Level 0's single Y row is checked by the same relation.  The tried Y halves are further halves of
+ *       the ONE pass over the 64-byte rows: the check's launch count does not grow.
+ *   2y. Source of a level: X if its X half is clean; else Y if the level was tried and its Y half is clean; else the level is failed.
+ *       The top level has no Y fall-back here.
+ *   3y. Y decode.  Every tried Y half goes through the RESIDUE64 decode into d_work_y with the write steps of its blocks (entry p of
+ *       level i: write_step - t + (t with bits 0 .. i cleared) + 1 + p, written on the device); level 0's one row is unscaled by
+ *       wt^-1 = w^(N - reverse_bits(step % N)) mod p_icc.  Outputs are canonical, below p_icc.
+ *   4y. Merge.  A block of an X-sourced level bids as in the call above.  A block of a Y-sourced level is known mod p_icc only; its
+ *       rank is its epoch write step; if it wins, the slot gets its n_cols x 32 bytes (chunks mod p_icc) and the flags FOUND | RESIDUE
+ *       | FROM_Y.
+ *   5y. Ambiguous index.  r0 = the decoded chunk 0 of a Y-sourced block, D = 2^256 - p_icc = 49 * 2^248 - 1.  The true chunk 0 is r0 or
+ *       r0 + p_icc, the second iff r0 < D; p_icc = 1 mod 2^64, so the two name the indices a = low64(r0) and a + 1 mod 2^64.  r0 >= D:
+ *       the index is a; in 1 .. n_total the block is a candidate, otherwise it is counted and dropped (rule 5).  r0 < D and neither
+ *       index in 1 .. n_total: counted and dropped (rule 5).  r0 < D otherwise: the block is set aside -- NEVER taken, the wrong slot
+ *       would be a silent error -- counted in d_counts[5], and each candidate slot in range records the block's step as a doubt.  With
+ *       random 256-bit chunks about 38 % of the Y blocks are ambiguous (r0 < D for a chunk below D and for one at or above p_icc: 2 D / 2^256): a caller
+ *       who wants the full fall-back keeps chunk 0 of every block in [D, p_icc).
+ *   6y. UNSURE iff some failed level (2y; the top level as above) has hi_i greater than the winner's rank, or the slot's doubt is
+ *       greater than the winner's rank; a slot without a winner has rank -1.
+ *   7y. d_counts, SIX words: [0] the X and top rows with status 0, [1] as above, [2] the blocks dropped for their index, from either
+ *       source, [3] the slots that are not FOUND or are UNSURE, [4] the tried Y rows with status 0, [5] the blocks set aside as ambiguous.
+ * Launches: those of the call above, plus the step-array kernel, the RESIDUE64 decode once per level size present among the tried Y
+ * halves, and the level-0 Y kernel.  The sequence depends on the symbol widths and on the level sizes present among the X halves and
+ * among the tried Y halves, never on K.  Contract: as the call above.
+ * PORLA_ERR_ARG (with a message, before the device is touched): everything the call above refuses (d_counts is 24 bytes here); with
+ * y_levels & t != 0 a NULL data_y, mac_y, align_y (the array itself), d_prf_y, d_work_y or d_row_status_y, and a tried level with a NULL
+ * entry in data_y or mac_y; whenever the pointer is given, a tried level's pointer of the three Y families, d_prf_y or d_work_y not
+ * 16-byte aligned, and a byte size that wraps; d_work_y and d_row_status_y are outputs in the overlap walk, the Y inputs may be shared
+ * between requests.  k = 0, PORLA_ERR_STATE and PORLA_ERR_NO_DEVICE as in the call above.
+ * Not in this call: the top level's Y half (a failed top level behaves as above); a host-memory form; n_total > 2^16; a cross-check
+ * of a Y decode against a clean X decode of the same level.  tools/bench_extract_xy.py times it (profiles/r24_a_extract_xy.jsonl). */
+#define PORLA_EXTRACT_XY_REQ_BYTES 160   /* sizeof(porla_extract_xy_req) on LP64; the library static_asserts it and each offset */
+#define PORLA_EXTRACT_FROM_Y        8    /* d_flags: the copy comes from a level's Y half: chunks mod p_icc (RESIDUE is set too) */
+#define PORLA_EXTRACT_ROW_NOT_TRIED 2    /* d_row_status_y: the row's level is not in y_levels */
+typedef struct {
+    unsigned long long  write_step;     /*   0: the fields of porla_extract_req, at its offsets */
+    void *const        *data_x;         /*   8 */
+    void *const        *mac_x;          /*  16 */
+    const void         *d_top_rows;     /*  24 */
+    const void         *d_top_macs;     /*  32 */
+    const void         *d_top_align;    /*  40 */
+    const void         *d_prf;          /*  48 */
+    void               *d_work;         /*  56 */
+    void               *d_blocks;       /*  64 */
+    unsigned int       *d_steps;        /*  72 */
+    unsigned char      *d_flags;        /*  80 */
+    unsigned char      *d_row_status;   /*  88 */
+    unsigned int       *d_counts;       /*  96: SIX words or NULL, zeroed by the call */
+    void *const        *data_y;         /* 104: HOST array of log2(n_total) DEVICE pointers: level i's Y data store as porla_update_req
+                                                lays it out; the first 2^i rows (the resident half) are read.  Entries of untried levels are ignored */
+    void *const        *mac_y;          /* 112: the same for the Y MAC stores */
+    void *const        *align_y;        /* 120: the same for the Y alignment stores; an entry may be 0: every alignment of that half at infinity */
+    const void         *d_prf_y;        /* 128: 16 raw bytes per lower-level row, laid out like the lower-level part of d_prf (t entries);
+                                                only the entries of tried levels are read */
+    void               *d_work_y;       /* 136: t x n_cols x 32 bytes of scratch for the decoded Y halves, laid out like d_work */
+    unsigned char      *d_row_status_y; /* 144: t bytes, laid out like the lower-level part of d_row_status */
+    unsigned long long  y_levels;       /* 152: bit i = try level i's Y half; only the bits of y_levels & t count */
+} porla_extract_xy_req;
+int porla_kzg_extract_xy_batch_device(const porla_extract_xy_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
+int porla_ipa_extract_xy_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t alpha_be[32],
+                                      const porla_extract_xy_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
 
 /* ---- AES on the device: the MAC PRF of the client writes, the audit challenge from its seed, the client's complement scalar ----
  * These calls PRODUCE the buffers the batches above consume (d_prf; d_idx* / d_coef* / d_mac_*; the 32-byte scalars of

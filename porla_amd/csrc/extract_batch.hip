@@ -1,15 +1,20 @@
-// The verified file extraction (include/porla_gpu.h: porla_kzg_extract_batch_device / porla_ipa_extract_batch_device): every resident
-// level of K files checked row by row against its stored MAC rows, the X halves decoded, and the decoded blocks merged into each file's
-// block store by "newest authentic copy wins", in ONE asynchronous call.  Kernels and the layout of a file's rows: extract_batch.hip.h.
-// Every step is on the caller's stream.  The launch sequence depends on the symbol widths and the level sizes present in the call,
-// never on K and -- the row check -- never on which levels are resident:
+// The verified file extraction (include/porla_gpu.h: porla_{kzg,ipa}_extract_batch_device and, with the lower levels' Y halves as a
+// second source, porla_{kzg,ipa}_extract_xy_batch_device): every resident level of K files checked row by row against its stored MAC
+// rows, the halves decoded, and the decoded blocks merged into each file's block store by "newest authentic copy wins", in ONE
+// asynchronous call.  Kernels and the layout of a file's rows: extract_batch.hip.h.  Both pairs of entry points go through ex_check and
+// ex_enqueue; a request of the first pair is one of the second without Y stores.  Every step is on the caller's stream.  The launch
+// sequence depends on the symbol widths and the level sizes present in the call (among the X halves, among the tried Y halves), never
+// on K and -- the row check -- never on which levels are resident:
 //
 //   upload                the files (ExFile), the halves as requests of the row check (RtDesc) and their start rows, one copy
-//   k_ex_clear            counters, failed-level masks, decode counters, the ranks of all slots
+//   k_ex_clear            counters, failed-level masks, decode counters, the ranks and doubts of all slots, the untried Y statuses
+//   k_ex_ysteps           a Y half tried: the write steps of the lower-level entries, for the unscale
 //   the row check         retrieve_batch.hip: rt_check_starts_{kzg,ipa}, the aligned retrieval's launches with the search map -- one
-//                         pass over ALL halves of 64-byte symbols (the lower levels, an exact top level), one over the RESIDUE32 top levels
+//                         pass over ALL halves of 64-byte symbols (the lower levels' X and tried Y halves, an exact top level), one
+//                         over the RESIDUE32 top levels
 //   the decodes           icc_decode_form_enqueue once per level size present: lower levels into d_work, the top level into d_blocks;
-//                         k_ex_level0 for the one-row level
+//                         k_ex_level0 for the one-row level; the tried Y halves in the form RESIDUE64 into d_work_y, once per level
+//                         size present among them, icc_decode_row0_enqueue for level 0's Y row
 //   k_ex_verdict, k_ex_rank, k_ex_gather       the merge
 #include "extract_batch.hip.h"
 #include "write_batch_host.hpp"
@@ -31,25 +36,41 @@ int rt_check_starts_ipa(porla_fixed_base* alpha_generators_fb, porla_fixed_base*
 struct ExtractWs {
     std::mutex mu;
     int device = -1;
-    Buf list, scratch;
+    Buf list, scratch, doubt, ysteps;
     PinnedList h_list;
     UseFence fence;
 };
 static PerDevice<ExtractWs> g_ex_ws;
 
-static inline uint32_t ex_t(const porla_extract_req& R, size_t n_total) { return (uint32_t)(R.write_step % n_total); }
+// the requests of a call: an array of porla_extract_req, or of porla_extract_xy_req (xy), read as the latter -- the first has no Y stores
+struct ExReqs {
+    const void* p;
+    bool xy;
+    porla_extract_xy_req at(size_t a) const {
+        porla_extract_xy_req R;
+        memset(&R, 0, sizeof R);
+        if (xy) memcpy(&R, (const uint8_t*)p + a * sizeof(porla_extract_xy_req), sizeof(porla_extract_xy_req));
+        else memcpy(&R, (const uint8_t*)p + a * sizeof(porla_extract_req), sizeof(porla_extract_req));
+        return R;
+    }
+    size_t counts_bytes() const { return xy ? 24 : 16; }
+};
+
+static inline uint32_t ex_t(const porla_extract_xy_req& R, size_t n_total) { return (uint32_t)(R.write_step % n_total); }
+static inline uint32_t ex_tried(const porla_extract_xy_req& R, size_t n_total) { return (uint32_t)(R.y_levels & ex_t(R, n_total)); }
 
 // the checks made before the device is touched; n_cols: the row width the buffers are sized by
-static int ex_check(const char* who, const porla_extract_req* reqs, size_t k, size_t n_cols, size_t n_total, int top_form) {
+static int ex_check(const char* who, const ExReqs& reqs, size_t k, size_t n_cols, size_t n_total, int top_form) {
     auto bad = [&](const std::string& what) { return bad_arg(who, what); };
-    if (k && !reqs) return bad("reqs is NULL");
+    if (k && !reqs.p) return bad("reqs is NULL");
     if (int rc = check_n_total(who, n_total, 16)) return rc;
     if (top_form != PORLA_ICC_DECODE_EXACT && top_form != PORLA_ICC_DECODE_RESIDUE32)
         return bad("top_form must be PORLA_ICC_DECODE_EXACT or PORLA_ICC_DECODE_RESIDUE32");
     if (int rc = check_request_count(who, k)) return rc;
     size_t bb, top_b, blocks_b, rows_all;
     // (the kernels number the rows of the call through in 32 bits)
-    if (!mul_ok(n_cols, 64, &bb) || !mul_ok(bb, n_total, &top_b) || (k && (!mul_ok(2 * n_total, k, &rows_all) || rows_all > 0xffffffffull)))
+    if (!mul_ok(n_cols, 64, &bb) || !mul_ok(bb, n_total, &top_b) ||
+        (k && (!mul_ok((reqs.xy ? 3 : 2) * n_total, k, &rows_all) || rows_all > 0xffffffffull)))
         return bad("a byte size overflows: the rows of the call do not fit a buffer");
     bb /= 2;                                                                 // a decoded block
     blocks_b = top_b / 2;
@@ -64,17 +85,20 @@ static int ex_check(const char* who, const porla_extract_req* reqs, size_t k, si
         ranges.push_back(Range{lo, lo + bytes, out});
     };
     for (size_t a = 0; a < k; a++) {
-        const porla_extract_req& R = reqs[a];
+        const porla_extract_xy_req R = reqs.at(a);
         const std::string at = "request " + std::to_string(a) + ": ";
-        const uint32_t t = ex_t(R, n_total);
+        const uint32_t t = ex_t(R, n_total), ym = ex_tried(R, n_total);
         const size_t rows = t + (R.d_top_rows ? n_total : 0);
         if (!R.d_blocks || !R.d_steps || !R.d_flags) return bad(at + "a NULL d_blocks, d_steps or d_flags");
         if (rows && (!R.d_prf || !R.d_row_status)) return bad(at + "a NULL d_prf or d_row_status");
         if (R.d_top_rows && !R.d_top_macs) return bad(at + "a NULL d_top_macs");
         if (t && (!R.data_x || !R.mac_x || !R.d_work)) return bad(at + "a NULL data_x, mac_x or d_work with resident lower levels");
+        if (ym && (!R.data_y || !R.mac_y || !R.align_y || !R.d_prf_y || !R.d_work_y || !R.d_row_status_y))
+            return bad(at + "a NULL data_y, mac_y, align_y, d_prf_y, d_work_y or d_row_status_y with a Y half to try");
         if (((uintptr_t)R.d_top_rows | (uintptr_t)R.d_top_macs | (uintptr_t)R.d_top_align | (uintptr_t)R.d_prf | (uintptr_t)R.d_work |
              (uintptr_t)R.d_blocks) & 15u)
             return bad(at + "d_top_rows, d_top_macs, d_top_align, d_prf, d_work or d_blocks is not 16-byte aligned");
+        if (((uintptr_t)R.d_prf_y | (uintptr_t)R.d_work_y) & 15u) return bad(at + "d_prf_y or d_work_y is not 16-byte aligned");
         if (((uintptr_t)R.d_steps | (uintptr_t)R.d_counts) & 3u) return bad(at + "d_steps or d_counts is not 4-byte aligned");
         for (int i = 0; i < logn; i++) {
             if (!(t >> i & 1u)) continue;
@@ -83,6 +107,14 @@ static int ex_check(const char* who, const porla_extract_req* reqs, size_t k, si
             if (((uintptr_t)dx | (uintptr_t)mx) & 15u) return bad(at + "a level pointer of data_x or mac_x is not 16-byte aligned");
             add(dx, ((size_t)2 * bb) << i, false);
             add(mx, (size_t)64 << i, false);
+            if (!(ym >> i & 1u)) continue;
+            const void *dy = R.data_y[i], *my = R.mac_y[i], *ay = R.align_y[i];
+            if (!dy || !my) return bad(at + "tried level " + std::to_string(i) + " has a NULL pointer in data_y or mac_y");
+            if (((uintptr_t)dy | (uintptr_t)my | (uintptr_t)ay) & 15u)
+                return bad(at + "a level pointer of data_y, mac_y or align_y is not 16-byte aligned");
+            add(dy, ((size_t)2 * bb) << i, false);
+            add(my, (size_t)64 << i, false);
+            if (ay) add(ay, (size_t)64 << i, false);
         }
         if (R.d_top_rows) {
             add(R.d_top_rows, top_b, false);
@@ -94,10 +126,13 @@ static int ex_check(const char* who, const porla_extract_req* reqs, size_t k, si
             add(R.d_row_status, rows, true);
         }
         if (t) add(R.d_work, (size_t)t * bb, true);
+        if (t && R.d_prf_y) add(R.d_prf_y, (size_t)16 * t, false);
+        if (t && R.d_work_y) add(R.d_work_y, (size_t)t * bb, true);
+        if (t && R.d_row_status_y) add(R.d_row_status_y, t, true);
         add(R.d_blocks, blocks_b, true);
         add(R.d_steps, 4 * n_total, true);
         add(R.d_flags, n_total, true);
-        if (R.d_counts) add(R.d_counts, 16, true);
+        if (R.d_counts) add(R.d_counts, reqs.counts_bytes(), true);
         if (wraps) return bad(at + "a byte size overflows: a buffer wraps around the address space");
     }
     // an output may overlap nothing, inputs may be shared (retrieve_batch.hip: the same walk)
@@ -105,8 +140,8 @@ static int ex_check(const char* who, const porla_extract_req* reqs, size_t k, si
     uintptr_t end_any = 0, end_out = 0;
     for (const Range& r : ranges) {
         if (r.lo < (r.out ? end_any : end_out))
-            return bad("an output (d_work, d_blocks, d_steps, d_flags, d_row_status or d_counts) overlaps an input or output of this call: "
-                       "outputs must be disjoint from everything");
+            return bad(std::string("an output (d_work, d_blocks, d_steps, d_flags, d_row_status") + (reqs.xy ? ", d_work_y, d_row_status_y" : "") +
+                       " or d_counts) overlaps an input or output of this call: outputs must be disjoint from everything");
         end_any = std::max(end_any, r.hi);
         if (r.out) end_out = std::max(end_out, r.hi);
     }
@@ -114,8 +149,8 @@ static int ex_check(const char* who, const porla_extract_req* reqs, size_t k, si
 }
 
 // ws->mu held, ws->fence entered; arguments checked.  fb_alpha == nullptr: the KZG build
-static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_base* fb_h, const uint32_t* alpha_ipa, const porla_extract_req* reqs,
-                      size_t k, size_t ncols, size_t n_total, int top_form, hipStream_t stream) {
+static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_base* fb_h, const uint32_t* alpha_ipa, const ExReqs& reqs, size_t k,
+                      size_t ncols, size_t n_total, int top_form, hipStream_t stream) {
     int rc;
     const bool kzg = fb_alpha == nullptr, residue = top_form == PORLA_ICC_DECODE_RESIDUE32;
     const int logn = ilog2u(n_total), curve = kzg ? 0 : 1;
@@ -126,14 +161,17 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
     uint32_t rows_of[2] = {0, 0};
     bool aligned[2] = {false, false};
     std::vector<ExFile> files(k);
-    std::vector<std::vector<porla_icc_decode_req>> dec(logn + 1);
+    std::vector<std::vector<porla_icc_decode_req>> dec(logn + 1), dec_y(logn);
     uint32_t t_max = 0, rows_max = 0;
-    bool level0 = false;
+    bool level0 = false, any_y = false;
+    for (size_t a = 0; a < k && !any_y; a++) any_y = ex_tried(reqs.at(a), n_total) != 0;
     if ((rc = ws->scratch.ensure(k * EX_SCRATCH_WORDS * 4))) return rc;
+    if (any_y && ((rc = ws->doubt.ensure(k * n_total * 4)) || (rc = ws->ysteps.ensure(k * n_total * 8)))) return rc;
     for (size_t a = 0; a < k; a++) {
-        const porla_extract_req& R = reqs[a];
-        const uint32_t t = ex_t(R, n_total);
+        const porla_extract_xy_req R = reqs.at(a);
+        const uint32_t t = ex_t(R, n_total), ym = ex_tried(R, n_total);
         uint32_t* scratch = (uint32_t*)ws->scratch.p + a * EX_SCRATCH_WORDS;
+        unsigned long long* ysteps = ym ? (unsigned long long*)ws->ysteps.p + a * n_total : nullptr;
         ExFile& F = files[a];
         F.level0 = (t & 1u) ? (const uint8_t*)R.data_x[0] : nullptr;
         F.status = R.d_row_status;
@@ -143,26 +181,44 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
         F.flags = R.d_flags;
         F.counts = R.d_counts;
         F.scratch = scratch;
+        F.status_y = t ? R.d_row_status_y : nullptr;
+        F.work_y = (const uint8_t*)R.d_work_y;
+        F.doubt = ym ? (uint32_t*)ws->doubt.p + a * n_total : nullptr;
+        F.ysteps = ysteps;
+        F.epoch = R.write_step - t;
         F.t = t;
         F.has_top = R.d_top_rows != nullptr;
+        F.y_tried = ym;
+        F.n_counts = (uint32_t)(reqs.counts_bytes() / 4);
         level0 = level0 || (t & 1u);
         t_max = std::max(t_max, t);
         rows_max = std::max(rows_max, t + (F.has_top ? (uint32_t)n_total : 0u));
-        auto half = [&](int w, const void* rows, const void* macs, const void* align, size_t off, size_t n) {
-            desc[w].push_back(RtDesc{(const uint8_t*)rows, (const uint8_t*)macs, (const uint8_t*)R.d_prf + 16 * off, (const uint8_t*)align, nullptr,
-                                     nullptr, R.d_row_status + off, R.d_counts});
+        auto half = [&](int w, const RtDesc& D, size_t n) {
+            desc[w].push_back(D);
             starts[w].push_back(rows_of[w]);
             rows_of[w] += (uint32_t)n;
-            aligned[w] = aligned[w] || align;
+            aligned[w] = aligned[w] || D.align;
+        };
+        auto half_x = [&](int w, const void* rows, const void* macs, const void* align, size_t off, size_t n) {
+            half(w, RtDesc{(const uint8_t*)rows, (const uint8_t*)macs, (const uint8_t*)R.d_prf + 16 * off, (const uint8_t*)align, nullptr, nullptr,
+                           R.d_row_status + off, R.d_counts}, n);
         };
         for (int i = 0; i < logn; i++) {
             if (!(t >> i & 1u)) continue;
             const size_t off = t & ((1u << i) - 1u);
-            half(0, R.data_x[i], R.mac_x[i], nullptr, off, (size_t)1 << i);
+            half_x(0, R.data_x[i], R.mac_x[i], nullptr, off, (size_t)1 << i);
             if (i) dec[i].push_back(porla_icc_decode_req{R.data_x[i], (uint8_t*)R.d_work + off * bb, nullptr, scratch + 1 + i});
         }
+        // the tried Y halves: further halves of the 64-byte pass, their failures counted in d_counts[4]
+        for (int i = 0; i < logn; i++) {
+            if (!(ym >> i & 1u)) continue;
+            const size_t off = t & ((1u << i) - 1u);
+            half(0, RtDesc{(const uint8_t*)R.data_y[i], (const uint8_t*)R.mac_y[i], (const uint8_t*)R.d_prf_y + 16 * off, (const uint8_t*)R.align_y[i],
+                           nullptr, nullptr, R.d_row_status_y + off, R.d_counts ? R.d_counts + 4 : nullptr}, (size_t)1 << i);
+            dec_y[i].push_back(porla_icc_decode_req{R.data_y[i], (uint8_t*)R.d_work_y + off * bb, ysteps + off, nullptr});
+        }
         if (F.has_top) {
-            half(residue ? 1 : 0, R.d_top_rows, R.d_top_macs, R.d_top_align, t, n_total);
+            half_x(residue ? 1 : 0, R.d_top_rows, R.d_top_macs, R.d_top_align, t, n_total);
             dec[logn].push_back(porla_icc_decode_req{R.d_top_rows, R.d_blocks, nullptr, residue ? nullptr : scratch + 1 + logn});
         }
     }
@@ -189,6 +245,11 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
         hipLaunchKernelGGL(k_ex_clear, dim3(blocks_of(n_total), ky), dim3(256), 0, stream, d_files, (uint32_t)n_total);
         PORLA_HIP(hipGetLastError());
     }
+    if (any_y) {
+        ProfScope ps("extract_ysteps", stream);
+        hipLaunchKernelGGL(k_ex_ysteps, dim3(blocks_of(t_max), ky), dim3(256), 0, stream, d_files);
+        PORLA_HIP(hipGetLastError());
+    }
     // the row check: one pass per symbol width present
     for (int w = 0; w < 2; w++) {
         if (!rows_of[w]) continue;
@@ -209,6 +270,13 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
         const int form = i == logn ? top_form : PORLA_ICC_DECODE_EXACT;
         if ((rc = icc_decode_form_enqueue(dec[i].data(), dec[i].size(), (size_t)1 << i, ncols, n_total, curve, form, stream))) return rc;
     }
+    // ... and per level size present among the tried Y halves
+    if (any_y && !dec_y[0].empty() && (rc = icc_decode_row0_enqueue(dec_y[0].data(), dec_y[0].size(), ncols, n_total, curve, stream))) return rc;
+    for (int i = 1; i < logn; i++) {
+        if (dec_y[i].empty()) continue;
+        if ((rc = icc_decode_form_enqueue(dec_y[i].data(), dec_y[i].size(), (size_t)1 << i, ncols, n_total, curve, PORLA_ICC_DECODE_RESIDUE64, stream)))
+            return rc;
+    }
     // the merge
     ProfScope ps("extract_merge", stream);
     hipLaunchKernelGGL(k_ex_verdict, dim3(blocks_of(rows_max), ky), dim3(256), 0, stream, d_files, (uint32_t)n_total, (uint32_t)logn);
@@ -219,21 +287,7 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
     return PORLA_OK;
 }
 
-}  // namespace porla
-
-using namespace porla;
-
-static_assert(sizeof(porla_extract_req) == PORLA_EXTRACT_REQ_BYTES, "porla_extract_req size");
-static_assert(offsetof(porla_extract_req, write_step) == 0 && offsetof(porla_extract_req, data_x) == 8 && offsetof(porla_extract_req, mac_x) == 16 &&
-              offsetof(porla_extract_req, d_top_rows) == 24 && offsetof(porla_extract_req, d_top_macs) == 32 &&
-              offsetof(porla_extract_req, d_top_align) == 40 && offsetof(porla_extract_req, d_prf) == 48 &&
-              offsetof(porla_extract_req, d_work) == 56 && offsetof(porla_extract_req, d_blocks) == 64 &&
-              offsetof(porla_extract_req, d_steps) == 72 && offsetof(porla_extract_req, d_flags) == 80 &&
-              offsetof(porla_extract_req, d_row_status) == 88 && offsetof(porla_extract_req, d_counts) == 96,
-              "porla_extract_req offsets (include/porla_gpu.h)");
-
-extern "C" int porla_kzg_extract_batch_device(const porla_extract_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
-    const char* who = "porla_kzg_extract_batch_device";
+static int ex_kzg(const char* who, const ExReqs& reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
     // the row width for the refusals: the SRS size, or one column while there is no SRS (the call then ends in PORLA_ERR_STATE or
     // PORLA_ERR_NO_DEVICE, and the refusals that do not depend on the width have been made)
     const size_t width = std::max<size_t>(kzg_n_samples(), 1);
@@ -250,9 +304,8 @@ extern "C" int porla_kzg_extract_batch_device(const porla_extract_req* reqs, siz
     return FencedCall(ws, stream).run([&] { return ex_enqueue(ws, nullptr, nullptr, nullptr, reqs, k, n, n_total, top_form, stream); });
 }
 
-extern "C" int porla_ipa_extract_batch_device(porla_fixed_base* alpha_generators_fb, porla_fixed_base* h_fb, const uint8_t alpha_be[32],
-                                              const porla_extract_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
-    const char* who = "porla_ipa_extract_batch_device";
+static int ex_ipa(const char* who, porla_fixed_base* alpha_generators_fb, porla_fixed_base* h_fb, const uint8_t alpha_be[32], const ExReqs& reqs,
+                  size_t k, size_t n_total, int top_form, void* hip_stream) {
     int rc = ex_check(who, reqs, k, IPA_COLS, n_total, top_form);
     if (rc) return rc;
     if (!alpha_be) return bad_arg(who, "alpha_be is NULL");
@@ -269,4 +322,48 @@ extern "C" int porla_ipa_extract_batch_device(porla_fixed_base* alpha_generators
     hipStream_t stream = (hipStream_t)hip_stream;
     return FencedCall(ws, stream).run(
         [&] { return ex_enqueue(ws, alpha_generators_fb, h_fb, alpha, reqs, k, IPA_COLS, n_total, top_form, stream); });
+}
+
+}  // namespace porla
+
+using namespace porla;
+
+static_assert(sizeof(porla_extract_req) == PORLA_EXTRACT_REQ_BYTES, "porla_extract_req size");
+static_assert(offsetof(porla_extract_req, write_step) == 0 && offsetof(porla_extract_req, data_x) == 8 && offsetof(porla_extract_req, mac_x) == 16 &&
+              offsetof(porla_extract_req, d_top_rows) == 24 && offsetof(porla_extract_req, d_top_macs) == 32 &&
+              offsetof(porla_extract_req, d_top_align) == 40 && offsetof(porla_extract_req, d_prf) == 48 &&
+              offsetof(porla_extract_req, d_work) == 56 && offsetof(porla_extract_req, d_blocks) == 64 &&
+              offsetof(porla_extract_req, d_steps) == 72 && offsetof(porla_extract_req, d_flags) == 80 &&
+              offsetof(porla_extract_req, d_row_status) == 88 && offsetof(porla_extract_req, d_counts) == 96,
+              "porla_extract_req offsets (include/porla_gpu.h)");
+static_assert(sizeof(porla_extract_xy_req) == PORLA_EXTRACT_XY_REQ_BYTES, "porla_extract_xy_req size");
+static_assert(offsetof(porla_extract_xy_req, write_step) == 0 && offsetof(porla_extract_xy_req, data_x) == 8 &&
+              offsetof(porla_extract_xy_req, mac_x) == 16 && offsetof(porla_extract_xy_req, d_top_rows) == 24 &&
+              offsetof(porla_extract_xy_req, d_top_macs) == 32 && offsetof(porla_extract_xy_req, d_top_align) == 40 &&
+              offsetof(porla_extract_xy_req, d_prf) == 48 && offsetof(porla_extract_xy_req, d_work) == 56 &&
+              offsetof(porla_extract_xy_req, d_blocks) == 64 && offsetof(porla_extract_xy_req, d_steps) == 72 &&
+              offsetof(porla_extract_xy_req, d_flags) == 80 && offsetof(porla_extract_xy_req, d_row_status) == 88 &&
+              offsetof(porla_extract_xy_req, d_counts) == 96 && offsetof(porla_extract_xy_req, data_y) == 104 &&
+              offsetof(porla_extract_xy_req, mac_y) == 112 && offsetof(porla_extract_xy_req, align_y) == 120 &&
+              offsetof(porla_extract_xy_req, d_prf_y) == 128 && offsetof(porla_extract_xy_req, d_work_y) == 136 &&
+              offsetof(porla_extract_xy_req, d_row_status_y) == 144 && offsetof(porla_extract_xy_req, y_levels) == 152,
+              "porla_extract_xy_req offsets (include/porla_gpu.h): porla_extract_req field for field, then the Y stores");
+
+extern "C" int porla_kzg_extract_batch_device(const porla_extract_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
+    return ex_kzg("porla_kzg_extract_batch_device", ExReqs{reqs, false}, k, n_total, top_form, hip_stream);
+}
+
+extern "C" int porla_ipa_extract_batch_device(porla_fixed_base* alpha_generators_fb, porla_fixed_base* h_fb, const uint8_t alpha_be[32],
+                                              const porla_extract_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
+    return ex_ipa("porla_ipa_extract_batch_device", alpha_generators_fb, h_fb, alpha_be, ExReqs{reqs, false}, k, n_total, top_form, hip_stream);
+}
+
+extern "C" int porla_kzg_extract_xy_batch_device(const porla_extract_xy_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
+    return ex_kzg("porla_kzg_extract_xy_batch_device", ExReqs{reqs, true}, k, n_total, top_form, hip_stream);
+}
+
+extern "C" int porla_ipa_extract_xy_batch_device(porla_fixed_base* alpha_generators_fb, porla_fixed_base* h_fb, const uint8_t alpha_be[32],
+                                                 const porla_extract_xy_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
+    return ex_ipa("porla_ipa_extract_xy_batch_device", alpha_generators_fb, h_fb, alpha_be, ExReqs{reqs, true}, k, n_total, top_form,
+                  hip_stream);
 }

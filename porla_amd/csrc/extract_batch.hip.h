@@ -13,13 +13,19 @@
 // step s, 1 .. t, lies in level i = the highest bit in which s - 1 and t differ, at p = (s - 1) & (2^i - 1).
 // Ranks travel as rank + 1 in d_steps (0 = no candidate; a clean top level's blocks are candidates of rank 0), so that one atomicMax per
 // decoded block picks the winner; k_ex_gather writes the documented values at the end.
+//
+// The second source (porla_*_extract_xy_batch_device): the tried Y halves lie in d_row_status_y, d_prf_y and d_work_y at the same
+// offsets o_i, decoded mod p_icc.  A level whose X half failed and whose tried Y half is clean is Y-sourced: its blocks bid with the
+// same ranks when chunk 0 mod p_icc names ONE index, and are set aside with a doubt (step + 1, a per-slot maximum) on the slots they
+// may name when it names two -- r0 < D = 2^256 - p_icc: the chunk may be r0 + p_icc, whose low 64 bits are one more.
 #pragma once
 #include "retrieve_batch.hip.h"
 #include "../../include/porla_gpu.h"
 
 namespace porla {
 
-// ---- the merge.  One file as its kernels see it
+// ---- the merge.  One file as its kernels see it.  The Y members are those of porla_*_extract_xy_batch_device: y_tried == 0 (the call
+// without Y halves, or none tried) leaves every kernel below on the X path alone.
 struct ExFile {
     const uint8_t* level0;     // level 0's one row of 64-byte symbols, or nullptr: not resident
     const uint8_t* status;     // d_row_status
@@ -28,13 +34,23 @@ struct ExFile {
     uint32_t* steps;           // d_steps
     uint8_t* flags;            // d_flags
     uint32_t* counts;          // d_counts or nullptr
-    uint32_t* scratch;         // EX_SCRATCH_WORDS words of the call's workspace: [0] the failed-level mask (bit i = level i, bit log2
-                               // n_total = the top level), [1 + s] the bad-symbol count of the decode of 2^s rows
+    uint32_t* scratch;         // EX_SCRATCH_WORDS words of the call's workspace: [0] the failed-level mask of the X halves (bit i = level
+                               // i, bit log2 n_total = the top level), [1 + s] the bad-symbol count of the decode of 2^s rows,
+                               // [EX_SCRATCH_FAILED_Y] the failed-level mask of the tried Y halves
+    uint8_t* status_y;         // d_row_status_y or nullptr
+    const uint8_t* work_y;     // d_work_y: the decoded Y halves, chunks mod p_icc
+    uint32_t* doubt;           // n_total words of the call's workspace, or nullptr (no Y half tried): per slot the highest step + 1 of
+                               // a Y block set aside as ambiguous that may belong there
+    unsigned long long* ysteps;// t words of the call's workspace: the write steps of the file's lower-level entries (the Y unscale)
+    unsigned long long epoch;  // write_step - t
     uint32_t t;                // write_step % n_total
     uint32_t has_top;
+    uint32_t y_tried;          // y_levels & t
+    uint32_t n_counts;         // 4, or 6 in the call with Y halves
 };
 constexpr int EX_SCRATCH_WORDS = 20;
-static_assert(sizeof(ExFile) == 72, "ExFile: eight pointers and two words");
+constexpr int EX_SCRATCH_FAILED_Y = 18;
+static_assert(sizeof(ExFile) == 120, "ExFile: twelve pointers, the epoch and four words");
 
 // the level of entry r < t of a file's ascending layout, and the entry's place in the level
 __device__ __forceinline__ uint32_t ex_level_of_entry(uint32_t t, uint32_t r, uint32_t& p) {
@@ -46,15 +62,35 @@ __device__ __forceinline__ uint32_t ex_level_of_entry(uint32_t t, uint32_t r, ui
         rest &= rest - 1u;
     }
 }
+// the epoch write step of entry p of level i
+__device__ __forceinline__ uint32_t ex_step_of(uint32_t t, uint32_t i, uint32_t p) { return (t & ~((2u << i) - 1u)) + 1u + p; }
+// the levels whose source is the Y half: X failed, Y tried and clean
+__device__ __forceinline__ uint32_t ex_y_sourced(const ExFile& F) { return F.scratch[0] & F.y_tried & ~F.scratch[EX_SCRATCH_FAILED_Y]; }
 
-// counters, failed-level mask, decode counters and the ranks of every slot: zero
+// counters, failed-level masks, decode counters, the ranks and doubts of every slot: zero; the Y statuses of untried levels
 __global__ void __launch_bounds__(256)
 k_ex_clear(const ExFile* __restrict__ files, uint32_t n_total) {
     const ExFile& F = files[blockIdx.y];
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_total) F.steps[i] = 0;
+    if (i < n_total && F.doubt) F.doubt[i] = 0;
     if (i < (uint32_t)EX_SCRATCH_WORDS) F.scratch[i] = 0;
-    if (i < 4u && F.counts) F.counts[i] = 0;
+    if (i < F.n_counts && F.counts) F.counts[i] = 0;
+    if (i < F.t && F.status_y) {
+        uint32_t p;
+        if (!(F.y_tried >> ex_level_of_entry(F.t, i, p) & 1u)) F.status_y[i] = PORLA_EXTRACT_ROW_NOT_TRIED;
+    }
+}
+
+// the write steps of a file's lower-level entries, for the unscale of the Y decodes: a lane per entry
+__global__ void __launch_bounds__(256)
+k_ex_ysteps(const ExFile* __restrict__ files) {
+    const ExFile& F = files[blockIdx.y];
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= F.t || !F.y_tried) return;
+    uint32_t p;
+    const uint32_t i = ex_level_of_entry(F.t, r, p);
+    F.ysteps[r] = F.epoch + ex_step_of(F.t, i, p);
 }
 
 // level 0: one row, the decode is the identity on the low 32 bytes of each symbol; a nonzero upper half is a bad symbol
@@ -71,7 +107,7 @@ k_ex_level0(const ExFile* __restrict__ files, uint32_t ncols) {
     if ((x.x | x.y | x.z | x.w | y.x | y.y | y.z | y.w) != 0u) atomicAdd(F.scratch + 1, 1u);
 }
 
-// the verdict: a lane per resident row; a row with status 0 fails its level
+// the verdict: a lane per resident row; a row with status 0 fails its level -- an X or top row in word 0, a tried Y row in the Y word
 __global__ void __launch_bounds__(256)
 k_ex_verdict(const ExFile* __restrict__ files, uint32_t n_total, uint32_t top_bit) {
     const ExFile& F = files[blockIdx.y];
@@ -79,15 +115,23 @@ k_ex_verdict(const ExFile* __restrict__ files, uint32_t n_total, uint32_t top_bi
     const uint32_t rows = F.t + (F.has_top ? n_total : 0u);
     if (r == 0u && F.counts) {                                            // the decodes' bad symbols, summed
         uint32_t bad = 0;
-        for (int s = 1; s < EX_SCRATCH_WORDS; s++) bad += F.scratch[s];
+        for (int s = 1; s < EX_SCRATCH_FAILED_Y; s++) bad += F.scratch[s];
         F.counts[1] = bad;
     }
-    if (r >= rows || F.status[r] != 0) return;
+    if (r >= rows) return;
     uint32_t p;
-    atomicOr(F.scratch, 1u << (r < F.t ? ex_level_of_entry(F.t, r, p) : top_bit));
+    if (F.status[r] == 0) atomicOr(F.scratch, 1u << (r < F.t ? ex_level_of_entry(F.t, r, p) : top_bit));
+    if (r < F.t && F.y_tried && F.status_y[r] == 0) atomicOr(F.scratch + EX_SCRATCH_FAILED_Y, 1u << ex_level_of_entry(F.t, r, p));
 }
 
-// rank: a lane per decoded block of a lower level; a clean level's block bids for the slot its first eight bytes name
+// r0 < D = 2^256 - p_icc = 49 * 2^248 - 1, r0 as eight little-endian words: then r0 + p_icc is a 256-bit chunk too
+__device__ __forceinline__ bool ex_below_d(const uint4& lo, const uint4& hi) {
+    if (hi.w != 0x30ffffffu) return hi.w < 0x30ffffffu;
+    return (lo.x & lo.y & lo.z & lo.w & hi.x & hi.y & hi.z) != 0xffffffffu;                   // (all ones: r0 = D)
+}
+
+// rank: a lane per decoded block of a lower level; a clean level's block bids for the slot its first eight bytes name.  A block of a
+// Y-sourced level is known mod p_icc: it bids when its index is certain, and is set aside with a doubt on the slots it may name when not
 __global__ void __launch_bounds__(256)
 k_ex_rank(const ExFile* __restrict__ files, uint32_t n_total, uint32_t ncols) {
     const ExFile& F = files[blockIdx.y];
@@ -95,14 +139,31 @@ k_ex_rank(const ExFile* __restrict__ files, uint32_t n_total, uint32_t ncols) {
     if (r >= F.t) return;
     uint32_t p;
     const uint32_t i = ex_level_of_entry(F.t, r, p);
-    if (F.scratch[0] >> i & 1u) return;
-    const uint2 id = *reinterpret_cast<const uint2*>(F.work + (size_t)r * ncols * 32);
-    if (id.y != 0u || id.x == 0u || id.x > n_total) {
-        if (F.counts) atomicAdd(F.counts + 2, 1u);
+    const uint32_t step = ex_step_of(F.t, i, p);
+    if (!(F.scratch[0] >> i & 1u)) {
+        const uint2 id = *reinterpret_cast<const uint2*>(F.work + (size_t)r * ncols * 32);
+        if (id.y != 0u || id.x == 0u || id.x > n_total) {
+            if (F.counts) atomicAdd(F.counts + 2, 1u);
+            return;
+        }
+        atomicMax(F.steps + (id.x - 1u), step + 1u);
         return;
     }
-    const uint32_t step = (F.t & ~((2u << i) - 1u)) + 1u + p;
-    atomicMax(F.steps + (id.x - 1u), step + 1u);
+    if (!(ex_y_sourced(F) >> i & 1u)) return;
+    const uint4* c0 = reinterpret_cast<const uint4*>(F.work_y + (size_t)r * ncols * 32);
+    const uint4 lo = c0[0], hi = c0[1];
+    const uint64_t a = (uint64_t)lo.y << 32 | lo.x, b = a + 1u;           // (b wraps to 0: out of range)
+    const bool in_a = a >= 1u && a <= n_total, in_b = b >= 1u && b <= n_total;
+    if (!ex_below_d(lo, hi)) {
+        if (in_a) atomicMax(F.steps + ((uint32_t)a - 1u), step + 1u);
+        else if (F.counts) atomicAdd(F.counts + 2, 1u);
+    } else if (!in_a && !in_b) {
+        if (F.counts) atomicAdd(F.counts + 2, 1u);
+    } else {
+        if (F.counts) atomicAdd(F.counts + 5, 1u);
+        if (in_a) atomicMax(F.doubt + ((uint32_t)a - 1u), step + 1u);
+        if (in_b) atomicMax(F.doubt + ((uint32_t)b - 1u), step + 1u);
+    }
 }
 
 // gather: a block per slot.  The winner's bytes (a top-level winner lies in d_blocks already), or zeros; step, flags, counts[3]
@@ -110,7 +171,7 @@ __global__ void __launch_bounds__(64)
 k_ex_gather(const ExFile* __restrict__ files, uint32_t ncols, uint32_t top_bit, uint32_t residue) {
     const ExFile& F = files[blockIdx.y];
     const uint32_t slot = blockIdx.x, t = F.t;
-    const uint32_t failed = F.scratch[0];
+    const uint32_t from_y = ex_y_sourced(F), failed = F.scratch[0] & ~from_y;
     uint32_t enc = F.steps[slot];
     __syncthreads();                                                      // (lane 0 rewrites the word below)
     if (enc == 0u && F.has_top && !(failed >> top_bit & 1u)) enc = 1u;
@@ -119,13 +180,16 @@ k_ex_gather(const ExFile* __restrict__ files, uint32_t ncols, uint32_t top_bit, 
         const uint32_t i = (uint32_t)__ffs((int)rest) - 1u;
         unsure = unsure || (uint64_t)(t & ~((1u << i) - 1u)) + 1u > enc;  // hi_i > rank
     }
+    if (F.doubt) unsure = unsure || F.doubt[slot] > enc;                  // an ambiguous block's step > rank
     const size_t u4 = (size_t)ncols * 2;                                  // 16-byte words of a block
     uint4* dst = reinterpret_cast<uint4*>(F.blocks) + (size_t)slot * u4;
+    bool y = false;
     if (enc > 1u) {
         const uint32_t s1 = enc - 2u;                                     // step - 1
         const uint32_t i = 31u - (uint32_t)__clz((int)(s1 ^ t));
         const size_t entry = (size_t)(t & ((1u << i) - 1u)) + (s1 & ((1u << i) - 1u));
-        const uint4* src = reinterpret_cast<const uint4*>(F.work) + entry * u4;
+        y = from_y >> i & 1u;
+        const uint4* src = reinterpret_cast<const uint4*>(y ? F.work_y : F.work) + entry * u4;
         for (size_t w = threadIdx.x; w < u4; w += blockDim.x) dst[w] = src[w];
     } else if (enc == 0u) {
         for (size_t w = threadIdx.x; w < u4; w += blockDim.x) dst[w] = make_uint4(0, 0, 0, 0);
@@ -133,7 +197,7 @@ k_ex_gather(const ExFile* __restrict__ files, uint32_t ncols, uint32_t top_bit, 
     if (threadIdx.x == 0u) {
         F.steps[slot] = enc ? enc - 1u : 0xffffffffu;
         F.flags[slot] = (uint8_t)((enc ? PORLA_EXTRACT_FOUND : 0) | (unsure ? PORLA_EXTRACT_UNSURE : 0) |
-                                  (enc == 1u && residue ? PORLA_EXTRACT_RESIDUE : 0));
+                                  (enc == 1u && residue ? PORLA_EXTRACT_RESIDUE : 0) | (y ? PORLA_EXTRACT_RESIDUE | PORLA_EXTRACT_FROM_Y : 0));
         if ((enc == 0u || unsure) && F.counts) atomicAdd(F.counts + 3, 1u);
     }
 }

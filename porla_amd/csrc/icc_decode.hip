@@ -175,6 +175,29 @@ int icc_decode_form_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t n
     if (int rc = g_icd_ws.get(&ws)) return rc;
     return FencedCall(ws, stream).run([&] { return icd_run(ws, reqs, k, n_rows, n_cols, n_total, curve, form, stream); });
 }
+// levels of ONE row in the form RESIDUE64: k_icd_row0 under the workspace's lock and fence and the data side's table lease
+int icc_decode_row0_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t n_cols, size_t n_total, int curve, hipStream_t stream) {
+    IccDecodeWs* ws = nullptr;
+    if (int rc = g_icd_ws.get(&ws)) return rc;
+    return FencedCall(ws, stream).run([&] {
+        int rc;
+        const size_t desc_b = k * sizeof(IcdDesc);
+        if ((rc = ws->h_list.stage(desc_b))) return rc;
+        if ((rc = ws->list.ensure(desc_b))) return rc;
+        memcpy(ws->h_list.h, reqs, desc_b);
+        if ((rc = ws->h_list.send(ws->list.p, desc_b, stream))) return rc;
+        const uint32_t *twp = nullptr, *twqi = nullptr;
+        if ((rc = icc_decode_tables_acquire(curve, n_total, false, stream, &twp, &twqi))) return rc;
+        {
+            ProfScope ps("icc_decode_row0", stream);
+            hipLaunchKernelGGL(k_icd_row0, dim3((unsigned)((n_cols + 255) / 256), (unsigned)k), dim3(256), 0, stream, (const IcdDesc*)ws->list.p,
+                               twp, (uint32_t)n_total, ilog2u(n_total), (uint32_t)n_cols);
+        }
+        if (hipGetLastError() != hipSuccess) { set_last_error("porla: ICC decode of one-row levels: a launch failed"); rc = PORLA_ERR_HIP; }
+        const int r1 = icc_mix_tables_release(stream);
+        return rc ? rc : r1;
+    });
+}
 int icc_decode_exact_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve,
                              hipStream_t stream) {
     return icc_decode_form_enqueue(reqs, k, n_rows, n_cols, n_total, curve, PORLA_ICC_DECODE_EXACT, stream);

@@ -77,15 +77,19 @@ __device__ __forceinline__ void icd_bfly(F30<M>& a, F30<M>& b, const F30<M>& w) 
     b = icc30_mul<M>(w, d);
 }
 
+// a 64-byte little-endian symbol mod the modulus of M, below 2 p (the load step of BOUNDS)
+template <class M>
+__device__ __forceinline__ F30<M> icd_load64(const uint8_t* __restrict__ sym) {
+    const Fe<IccFp> lo = ld_fe<IccFp>(reinterpret_cast<const uint32_t*>(sym));
+    const Fe<IccFp> hi = ld_fe<IccFp>(reinterpret_cast<const uint32_t*>(sym + 32));
+    return icc30_reduce_top<M>(icc30_add<M>(icc30_mul<M>(f30_unpack<M>(hi.v), f30_const<M>(Icc30Const<M>::C526)), f30_unpack<M>(lo.v)));
+}
+
 // a tile symbol from where the pass finds it, below 2 p
 template <class M, int SRC>
 __device__ __forceinline__ F30<M> icd_fetch(const IccTile& T, uint32_t e, const uint8_t* __restrict__ rows, const uint32_t* __restrict__ work) {
     const size_t gi = icc30_symbol_index(T, e);
-    if (SRC == ICD_ROWS64) {
-        const Fe<IccFp> lo = ld_fe<IccFp>(reinterpret_cast<const uint32_t*>(rows + 64 * gi));
-        const Fe<IccFp> hi = ld_fe<IccFp>(reinterpret_cast<const uint32_t*>(rows + 64 * gi + 32));
-        return icc30_reduce_top<M>(icc30_add<M>(icc30_mul<M>(f30_unpack<M>(hi.v), f30_const<M>(Icc30Const<M>::C526)), f30_unpack<M>(lo.v)));
-    }
+    if (SRC == ICD_ROWS64) return icd_load64<M>(rows + 64 * gi);
     if (SRC == ICD_ROWS32) return f30_unpack<M>(ld_fe<IccFp>(reinterpret_cast<const uint32_t*>(rows + 32 * gi)).v);
     return icc30_ld_work<M>(work + gi * ICC30_PLANE_WORDS);
 }
@@ -284,6 +288,20 @@ k_icd_residue(const IcdDesc* __restrict__ desc, uint32_t* __restrict__ work, siz
             }
         }
     }
+}
+
+// ---- a level of ONE row in the form RESIDUE64 (level 0's Y row): no stage runs, the symbol is chunk * wt mod p_icc and the decode is
+// the unscale alone, a lane per symbol of request blockIdx.y: wt^-1 = w^(N - e), e = reverse_bits(step % N, log2 N), as in the finish
+// of k_icd_residue.  The symbol enters below 2 p (icd_load64), the product with the twiddle is below p + 2^250; out: canonical.
+// steps: the one write step of the row (never nullptr here)
+static __global__ void __launch_bounds__(256)
+k_icd_row0(const IcdDesc* __restrict__ desc, const uint32_t* __restrict__ twp, uint32_t tw_n, int tw_log, uint32_t ncols) {
+    const IcdDesc D = desc[blockIdx.y];
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncols) return;
+    const uint32_t e = tw_log ? __brev((uint32_t)D.steps[0] & (tw_n - 1u)) >> (32 - tw_log) : 0u;
+    const F30<IccFp> r = icc30_mul<IccFp>(icd_tw<IccFp>(twp, tw_n, e), icd_load64<IccFp>(D.rows + 64 * (size_t)c));
+    st_fe<IccFp>(reinterpret_cast<uint32_t*>(D.out + 32 * (size_t)c), icc30_finish_p(r));
 }
 
 // the counters of the requests that have one, zeroed in front of the passes

@@ -144,6 +144,21 @@ PORLA_EXTRACT_FOUND, PORLA_EXTRACT_UNSURE, PORLA_EXTRACT_RESIDUE = 1, 2, 4
 assert ctypes.sizeof(ExtractReq) == PORLA_EXTRACT_REQ_BYTES
 
 
+class ExtractXyReq(ctypes.Structure):
+    """porla_extract_xy_req, include/porla_gpu.h: one file of porla_kzg_extract_xy_batch_device / porla_ipa_extract_xy_batch_device
+    (PORLA_EXTRACT_XY_REQ_BYTES = 160): ExtractReq field for field, then the Y stores.  data_y, mac_y and align_y are HOST arrays of
+    device pointers."""
+    _fields_ = ExtractReq._fields_ + [("data_y", ctypes.c_void_p), ("mac_y", ctypes.c_void_p), ("align_y", ctypes.c_void_p),
+                                      ("d_prf_y", ctypes.c_void_p), ("d_work_y", ctypes.c_void_p), ("d_row_status_y", ctypes.c_void_p),
+                                      ("y_levels", ctypes.c_ulonglong)]
+
+
+PORLA_EXTRACT_XY_REQ_BYTES = 160
+PORLA_EXTRACT_FROM_Y = 8
+PORLA_EXTRACT_ROW_NOT_TRIED = 2
+assert ctypes.sizeof(ExtractXyReq) == PORLA_EXTRACT_XY_REQ_BYTES
+
+
 class PrfRun(ctypes.Structure):
     """porla_prf_run, include/porla_gpu.h: count triples (level, index0 + t, time0 + t * time_stride) of the MAC PRF
     (PORLA_PRF_RUN_BYTES = 32)."""
@@ -345,6 +360,10 @@ def _declare(L):
     L.porla_kzg_extract_batch_device.restype = ctypes.c_int
     L.porla_ipa_extract_batch_device.argtypes = [vp, vp, u8p, ctypes.POINTER(ExtractReq), sz, sz, ctypes.c_int, vp]
     L.porla_ipa_extract_batch_device.restype = ctypes.c_int
+    L.porla_kzg_extract_xy_batch_device.argtypes = [ctypes.POINTER(ExtractXyReq), sz, sz, ctypes.c_int, vp]
+    L.porla_kzg_extract_xy_batch_device.restype = ctypes.c_int
+    L.porla_ipa_extract_xy_batch_device.argtypes = [vp, vp, u8p, ctypes.POINTER(ExtractXyReq), sz, sz, ctypes.c_int, vp]
+    L.porla_ipa_extract_xy_batch_device.restype = ctypes.c_int
     L.porla_kzg_retrieve_aligned_host.argtypes = [u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp, ctypes.POINTER(ctypes.c_uint)]
     L.porla_kzg_retrieve_aligned_host.restype = ctypes.c_int
     L.porla_ipa_retrieve_aligned_host.argtypes = [vp, vp, u8p, u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp,

@@ -467,6 +467,41 @@ def kzg_extract_batch_device(reqs, n_total, top_form, stream=0):
     del keep
 
 
+def _host_pointer_array(fam, keep):
+    """a HOST array of device addresses as a c_void_p (None stays None); the array itself goes into `keep`"""
+    if fam is None:
+        return None
+    host = (ctypes.c_void_p * max(len(fam), 1))(*[p or None for p in fam])
+    keep.append(host)
+    return ctypes.cast(host, ctypes.c_void_p)
+
+
+def extract_xy_requests(reqs):
+    """(a ctypes array of porla_extract_xy_req, what must stay alive beside it) from per-file tuples: the 13 fields extract_requests
+    takes, then (data_y, mac_y, align_y, d_prf_y or 0, d_work_y or 0, d_row_status_y or 0, y_levels) -- the three families sequences of
+    the levels' device addresses (entries of untried levels, and any entry of align_y, may be 0), or None"""
+    from .loader import ExtractXyReq
+    arr = (ExtractXyReq * max(len(reqs), 1))()
+    keep = []
+    for i, r in enumerate(reqs):
+        if len(r) != 20:
+            raise ValueError("extract_xy_batch_device: request %d has %d fields, want 20" % (i, len(r)))
+        x = [_host_pointer_array(fam, keep) for fam in r[1:3]]
+        y = [_host_pointer_array(fam, keep) for fam in r[13:16]]
+        arr[i] = ExtractXyReq(r[0], x[0], x[1], *([v or None for v in r[3:13]] + y + [v or None for v in r[16:19]] + [r[19]]))
+    return arr, keep
+
+
+def kzg_extract_xy_batch_device(reqs, n_total, top_form, stream=0):
+    """kzg_extract_batch_device with the lower levels' Y halves as a second source (porla_kzg_extract_xy_batch_device): a level of
+    y_levels whose X half has a failed row is taken from its Y half -- chunks mod p_icc, flags FOUND | RESIDUE | FROM_Y -- when that
+    half checks clean; a Y block whose index is ambiguous mod p_icc is set aside and counted in d_counts[5] (six words).  `reqs`:
+    tuples as extract_xy_requests takes them."""
+    arr, keep = extract_xy_requests(reqs)
+    _check(lib.porla_kzg_extract_xy_batch_device(arr, len(reqs), n_total, RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
+    del keep
+
+
 def kzg_retrieve_aligned_host(rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None, want_blocks=True):
     """one level from host memory (porla_kzg_retrieve_aligned_host; it waits) -> what kzg_retrieve_host returns"""
     n_cols = kzg_row_coefficients()
@@ -581,6 +616,14 @@ class FixedBase:
         arr, keep = extract_requests(reqs)
         _check(lib.porla_ipa_extract_batch_device(self.h, h_fb.h if h_fb is not None else None, _alpha_be(alpha), arr, len(reqs), n_total,
                                                   RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
+        del keep
+
+    def ipa_extract_xy_batch_device(self, h_fb, alpha, reqs, n_total, top_form, stream=0):
+        """kzg_extract_xy_batch_device for the IPA build (porla_ipa_extract_xy_batch_device: 128 columns); self, h_fb and alpha as for
+        ipa_extract_batch_device."""
+        arr, keep = extract_xy_requests(reqs)
+        _check(lib.porla_ipa_extract_xy_batch_device(self.h, h_fb.h if h_fb is not None else None, _alpha_be(alpha), arr, len(reqs), n_total,
+                                                     RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
         del keep
 
     def ipa_retrieve_aligned_host(self, h_fb, alpha, rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None,
