@@ -895,6 +895,35 @@ int porla_icc_decode_batch_device(const porla_icc_decode_req *reqs, size_t k, si
 int porla_icc_decode_host(const uint8_t *rows, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form,
                           const unsigned long long *write_steps, uint8_t *out, unsigned int *bad);
 
+/* ---- the ragged ICC decode: K levels of UNEQUAL sizes in ONE asynchronous call ----
+ * porla_icc_decode_batch_device with n_rows moved from the call into the request: a hierarchy's resident levels are never of one size,
+ * and one call per size pays the upload, the counters' reset, the workspace's lock and fence and the table lease each time for a few
+ * tiles of work.  Request a is one level: the four pointers of porla_icc_decode_req with the same meaning, alignment and form rules
+ * (d_write_steps: that request's n_rows values), then
+ *   n_rows         a power of two, 2 .. n_total (levels of one row stay with the callers that handle them today)
+ * One form, one n_cols, one curve per call.  For every request d_out and *d_bad are byte for byte what
+ * porla_icc_decode_batch_device writes for that request alone; they do not depend on the order of the requests.
+ * Contract: that of the uniform call -- asynchronous on hip_stream, no host wait, no side stream -- and the launch sequence depends on
+ * the PASS CLASSES present (n_rows <= 2^9: one pass; above: two), never on k and never on which sizes are present: one upload (the
+ * requests with their shapes, largest first, the n_rows^-1 table, the tile starts), the counters' reset (EXACT), one launch over all
+ * one-pass requests, two over all two-pass requests; a work-group finds its request and tile by binary search in the launch's tile
+ * starts.  The workspace's lock and fence and the table lease are taken once.
+ * PORLA_ERR_ARG (with a message, before the device is touched): every refusal of porla_icc_decode_batch_device, n_rows judged per
+ * request and the overlap rule applied with each request's own byte sizes; more tiles in one launch than a grid holds (2^24 - 1:
+ * beyond 16 Gi symbols).  k = 0 returns 0; valid arguments without a device: PORLA_ERR_NO_DEVICE.
+ * tools/bench_icc_decode_ragged.py times it beside one uniform call per size on the same stores, every output byte compared
+ * (DESIGN s4, profiles/r25_a_decode_ragged.jsonl). */
+#define PORLA_ICC_DECODE_RAGGED_REQ_BYTES 40   /* sizeof(porla_icc_decode_ragged_req) on LP64; static_asserted with each offset */
+typedef struct {
+    const void *d_rows;                       /*  0  as porla_icc_decode_req */
+    void *d_out;                              /*  8 */
+    const unsigned long long *d_write_steps;  /* 16 */
+    unsigned int *d_bad;                      /* 24 */
+    unsigned long long n_rows;                /* 32: this level's rows */
+} porla_icc_decode_ragged_req;
+int porla_icc_decode_ragged_batch_device(const porla_icc_decode_ragged_req *reqs, size_t k, size_t n_cols, size_t n_total, int curve,
+                                         int form, void *hip_stream);
+
 /* ---- the ICC MAC decode: the coded MAC rows of a level back to its per-block MACs, for K independent levels in ONE asynchronous call ----
  * The MAC-side twin of the ICC decode: a block recovered by porla_icc_decode_batch_device counts only once it has been checked against
  * its MAC, alpha * commit(block) + PRF * h, and the per-block MACs of a level exist only in coded form (mac_x / mac_y: the MAC network
@@ -1087,9 +1116,11 @@ int porla_ipa_retrieve_aligned_host(porla_fixed_base *alpha_generators_fb, porla
  *      upper half), [2] the blocks dropped under 5, [3] the slots that are not FOUND or are UNSURE.
  * Launches: one upload; one clear; the aligned retrieval's check launches ONCE over all 64-byte rows of all files and levels and once
  * more over the RESIDUE32 top levels (the rows find their half by a binary search in the halves' start rows; IPA in its coefficient
- * workspace groups) -- their number depends on the symbol widths present, not on K and not on which levels are resident; the data
- * decode once per level size present (top level straight into d_blocks, lower levels into d_work, level 0 by a copy kernel); three
- * merge kernels.  Contract: that of the other batches -- asynchronous on hip_stream, no side stream, no host wait beyond the retrieval
+ * workspace groups) -- their number depends on the symbol widths present, not on K and not on which levels are resident; ONE ragged
+ * data decode (porla_icc_decode_ragged_batch_device's body) over the lower levels of two rows and more and the exact top levels of
+ * all files (top level straight into d_blocks, lower levels into d_work): at most three pass launches, by whether levels of up to
+ * 2^9 rows and larger ones are present, not by which sizes; the uniform decode for RESIDUE32 top levels; level 0 by a copy kernel;
+ * three merge kernels.  Contract: that of the other batches -- asynchronous on hip_stream, no side stream, no host wait beyond the retrieval
  * calls' first-use upload of the tau table; workspaces under their locks and fences.
  * PORLA_ERR_ARG (with a message, before the device is touched): NULL reqs with k > 0; NULL d_blocks, d_steps or d_flags; NULL d_prf or
  * d_row_status with a resident row; NULL d_top_macs beside d_top_rows; NULL data_x, mac_x or d_work with t > 0 (they may be NULL only when
@@ -1158,9 +1189,9 @@ int porla_ipa_extract_batch_device(porla_fixed_base *alpha_generators_fb, porla_
  *       greater than the winner's rank; a slot without a winner has rank -1.
  *   7y. d_counts, SIX words: [0] the X and top rows with status 0, [1] as above, [2] the blocks dropped for their index, from either
  *       source, [3] the slots that are not FOUND or are UNSURE, [4] the tried Y rows with status 0, [5] the blocks set aside as ambiguous.
- * Launches: those of the call above, plus the step-array kernel, the RESIDUE64 decode once per level size present among the tried Y
- * halves, and the level-0 Y kernel.  The sequence depends on the symbol widths and on the level sizes present among the X halves and
- * among the tried Y halves, never on K.  Contract: as the call above.
+ * Launches: those of the call above, plus the step-array kernel, ONE ragged RESIDUE64 decode over the tried Y halves of two rows and
+ * more, and the level-0 Y kernel.  The sequence depends on the symbol widths and on the pass classes present (levels of up to 2^9
+ * rows, larger ones) among the X halves and among the tried Y halves, never on K and never on which sizes are present.  Contract: as the call above.
  * PORLA_ERR_ARG (with a message, before the device is touched): everything the call above refuses (d_counts is 24 bytes here); with
  * y_levels & t != 0 a NULL data_y, mac_y, align_y (the array itself), d_prf_y, d_work_y or d_row_status_y, and a tried level with a NULL
  * entry in data_y or mac_y; whenever the pointer is given, a tried level's pointer of the three Y families, d_prf_y or d_work_y not

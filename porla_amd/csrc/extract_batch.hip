@@ -3,8 +3,8 @@
 // rows, the halves decoded, and the decoded blocks merged into each file's block store by "newest authentic copy wins", in ONE
 // asynchronous call.  Kernels and the layout of a file's rows: extract_batch.hip.h.  Both pairs of entry points go through ex_check and
 // ex_enqueue; a request of the first pair is one of the second without Y stores.  Every step is on the caller's stream.  The launch
-// sequence depends on the symbol widths and the level sizes present in the call (among the X halves, among the tried Y halves), never
-// on K and -- the row check -- never on which levels are resident:
+// sequence depends on the symbol widths and the pass classes present in the call (levels of up to 2^9 rows, larger ones; among the X
+// halves, among the tried Y halves), never on K and never on which levels are resident:
 //
 //   upload                the files (ExFile), the halves as requests of the row check (RtDesc) and their start rows, one copy
 //   k_ex_clear            counters, failed-level masks, decode counters, the ranks and doubts of all slots, the untried Y statuses
@@ -12,9 +12,11 @@
 //   the row check         retrieve_batch.hip: rt_check_starts_{kzg,ipa}, the aligned retrieval's launches with the search map -- one
 //                         pass over ALL halves of 64-byte symbols (the lower levels' X and tried Y halves, an exact top level), one
 //                         over the RESIDUE32 top levels
-//   the decodes           icc_decode_form_enqueue once per level size present: lower levels into d_work, the top level into d_blocks;
-//                         k_ex_level0 for the one-row level; the tried Y halves in the form RESIDUE64 into d_work_y, once per level
-//                         size present among them, icc_decode_row0_enqueue for level 0's Y row
+//   the decodes           icc_decode_ragged_enqueue ONCE over the lower levels' X halves of two rows and more (into d_work) and the
+//                         exact top levels (into d_blocks): at most three pass launches whatever sizes are present; the uniform
+//                         icc_decode_form_enqueue for RESIDUE32 top levels; k_ex_level0 for the one-row level; the tried Y halves of
+//                         two rows and more in the form RESIDUE64 into d_work_y, one ragged call again, icc_decode_row0_enqueue for
+//                         level 0's Y row
 //   k_ex_verdict, k_ex_rank, k_ex_gather       the merge
 #include "extract_batch.hip.h"
 #include "write_batch_host.hpp"
@@ -161,7 +163,8 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
     uint32_t rows_of[2] = {0, 0};
     bool aligned[2] = {false, false};
     std::vector<ExFile> files(k);
-    std::vector<std::vector<porla_icc_decode_req>> dec(logn + 1), dec_y(logn);
+    std::vector<porla_icc_decode_ragged_req> dec, dec_y;               // the EXACT decodes; the tried Y halves of two rows and more
+    std::vector<porla_icc_decode_req> dec_top32, dec_y0;               // RESIDUE32 top levels; level 0's Y rows
     uint32_t t_max = 0, rows_max = 0;
     bool level0 = false, any_y = false;
     for (size_t a = 0; a < k && !any_y; a++) any_y = ex_tried(reqs.at(a), n_total) != 0;
@@ -207,7 +210,7 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
             if (!(t >> i & 1u)) continue;
             const size_t off = t & ((1u << i) - 1u);
             half_x(0, R.data_x[i], R.mac_x[i], nullptr, off, (size_t)1 << i);
-            if (i) dec[i].push_back(porla_icc_decode_req{R.data_x[i], (uint8_t*)R.d_work + off * bb, nullptr, scratch + 1 + i});
+            if (i) dec.push_back(porla_icc_decode_ragged_req{R.data_x[i], (uint8_t*)R.d_work + off * bb, nullptr, scratch + 1 + i, 1ull << i});
         }
         // the tried Y halves: further halves of the 64-byte pass, their failures counted in d_counts[4]
         for (int i = 0; i < logn; i++) {
@@ -215,11 +218,13 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
             const size_t off = t & ((1u << i) - 1u);
             half(0, RtDesc{(const uint8_t*)R.data_y[i], (const uint8_t*)R.mac_y[i], (const uint8_t*)R.d_prf_y + 16 * off, (const uint8_t*)R.align_y[i],
                            nullptr, nullptr, R.d_row_status_y + off, R.d_counts ? R.d_counts + 4 : nullptr}, (size_t)1 << i);
-            dec_y[i].push_back(porla_icc_decode_req{R.data_y[i], (uint8_t*)R.d_work_y + off * bb, ysteps + off, nullptr});
+            if (i) dec_y.push_back(porla_icc_decode_ragged_req{R.data_y[i], (uint8_t*)R.d_work_y + off * bb, ysteps + off, nullptr, 1ull << i});
+            else dec_y0.push_back(porla_icc_decode_req{R.data_y[i], (uint8_t*)R.d_work_y + off * bb, ysteps + off, nullptr});
         }
         if (F.has_top) {
             half_x(residue ? 1 : 0, R.d_top_rows, R.d_top_macs, R.d_top_align, t, n_total);
-            dec[logn].push_back(porla_icc_decode_req{R.d_top_rows, R.d_blocks, nullptr, residue ? nullptr : scratch + 1 + logn});
+            if (residue) dec_top32.push_back(porla_icc_decode_req{R.d_top_rows, R.d_blocks, nullptr, nullptr});
+            else dec.push_back(porla_icc_decode_ragged_req{R.d_top_rows, R.d_blocks, nullptr, scratch + 1 + logn, (unsigned long long)n_total});
         }
     }
     // one upload: files, requests of both widths, start rows of both widths
@@ -259,24 +264,19 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
                  : rt_check_starts_ipa(fb_alpha, fb_h, alpha_ipa, aligned[w], d_desc[w], map, rows_of[w], symb, stream);
         if (rc) return rc;
     }
-    // the decodes: one call per level size present
+    // the decodes: one ragged call over every size present; RESIDUE32 top levels are of one size and keep the uniform call
     if (level0) {
         ProfScope ps("extract_level0", stream);
         hipLaunchKernelGGL(k_ex_level0, dim3(blocks_of(ncols), ky), dim3(256), 0, stream, d_files, (uint32_t)ncols);
         PORLA_HIP(hipGetLastError());
     }
-    for (int i = 1; i <= logn; i++) {
-        if (dec[i].empty()) continue;
-        const int form = i == logn ? top_form : PORLA_ICC_DECODE_EXACT;
-        if ((rc = icc_decode_form_enqueue(dec[i].data(), dec[i].size(), (size_t)1 << i, ncols, n_total, curve, form, stream))) return rc;
-    }
-    // ... and per level size present among the tried Y halves
-    if (any_y && !dec_y[0].empty() && (rc = icc_decode_row0_enqueue(dec_y[0].data(), dec_y[0].size(), ncols, n_total, curve, stream))) return rc;
-    for (int i = 1; i < logn; i++) {
-        if (dec_y[i].empty()) continue;
-        if ((rc = icc_decode_form_enqueue(dec_y[i].data(), dec_y[i].size(), (size_t)1 << i, ncols, n_total, curve, PORLA_ICC_DECODE_RESIDUE64, stream)))
-            return rc;
-    }
+    if ((rc = icc_decode_ragged_enqueue(dec.data(), dec.size(), ncols, n_total, curve, PORLA_ICC_DECODE_EXACT, stream))) return rc;
+    if (!dec_top32.empty() &&
+        (rc = icc_decode_form_enqueue(dec_top32.data(), dec_top32.size(), n_total, ncols, n_total, curve, PORLA_ICC_DECODE_RESIDUE32, stream)))
+        return rc;
+    // ... and the tried Y halves
+    if (!dec_y0.empty() && (rc = icc_decode_row0_enqueue(dec_y0.data(), dec_y0.size(), ncols, n_total, curve, stream))) return rc;
+    if ((rc = icc_decode_ragged_enqueue(dec_y.data(), dec_y.size(), ncols, n_total, curve, PORLA_ICC_DECODE_RESIDUE64, stream))) return rc;
     // the merge
     ProfScope ps("extract_merge", stream);
     hipLaunchKernelGGL(k_ex_verdict, dim3(blocks_of(rows_max), ky), dim3(256), 0, stream, d_files, (uint32_t)n_total, (uint32_t)logn);

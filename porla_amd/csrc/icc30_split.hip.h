@@ -105,16 +105,27 @@ struct IccTile {           // what a block knows about its tile (the same for bo
 };
 // the tile of the calling block in a pass that runs stages s0 .. s0 + ns - 1 on tiles of 2^ns rows x 2^cc_log columns (grid.x =
 // column tiles x row tiles).  blocks b, b + 8, ... share an XCD (observed round-robin dispatch; speed only): XCD x takes tiles
-// [x G / 8, (x + 1) G / 8)
-__device__ __forceinline__ IccTile icc30_block_tile(uint32_t n, uint32_t ncols, int s0, int ns, int cc_log, bool raw) {
+// [x G / 8, (x + 1) G / 8).  Map: which tile of how many the block takes -- IccTileGrid, the default: the launch's own blockIdx.x of
+// gridDim.x; IccTileAt: a position the kernel worked out itself (the ragged decode, whose launch holds the tiles of many levels)
+struct IccTileGrid {
+    __device__ __forceinline__ uint32_t index() const { return blockIdx.x; }
+    __device__ __forceinline__ uint32_t count() const { return gridDim.x; }
+};
+struct IccTileAt {
+    uint32_t i, g;
+    __device__ __forceinline__ uint32_t index() const { return i; }
+    __device__ __forceinline__ uint32_t count() const { return g; }
+};
+template <class Map = IccTileGrid>
+__device__ __forceinline__ IccTile icc30_block_tile(uint32_t n, uint32_t ncols, int s0, int ns, int cc_log, bool raw, const Map& map = Map()) {
     IccTile T;
     T.n = n; T.ncols = ncols; T.s0 = s0; T.ns = ns; T.cc_log = (uint32_t)cc_log;
     T.elems = (1u << ns) << cc_log;
     T.raw = raw;
     T.lo_bits = (uint32_t)(s0 - 1);
     const uint32_t col_tiles = (ncols + (1u << cc_log) - 1) >> cc_log;
-    uint32_t tile = blockIdx.x;
-    if ((gridDim.x & 7u) == 0) tile = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    uint32_t tile = map.index();
+    if ((map.count() & 7u) == 0) tile = (map.index() & 7u) * (map.count() >> 3) + (map.index() >> 3);
     const uint32_t ct = tile % col_tiles;
     tile /= col_tiles;
     T.lo = tile & ((1u << T.lo_bits) - 1u);

@@ -7,8 +7,12 @@
 //   k_icd_exact /   ceil(log2 n_rows / 9) passes over 1 024-symbol tiles, the encode's plan in reverse order, grid.y = request, under
 //   k_icd_residue   the data side's table lease; the first reads the rows, the last writes the blocks; between them the residue
 //                   planes travel through this workspace
+//
+// porla_icc_decode_ragged_batch_device, further down, is the same decode for levels of unequal sizes: n_rows per request, launches by
+// the pass classes present (kernels: icc_decode_ragged.hip.h).
 #include "batch_host.hpp"
 #include "icc_decode.hip.h"
+#include "icc_decode_ragged.hip.h"
 #include "icc_host.hpp"
 
 #include <algorithm>
@@ -25,6 +29,8 @@ struct IccDecodeWs {
     Buf io_rows, io_out, io_steps, io_bad;     // the host form's device images
     PinnedList h_list;
     UseFence fence;
+    IcdScale rag_scales[2][ICD_RAG_MAX_LOG + 1];   // the ragged call's n_rows^-1 table per curve, made on first use
+    bool rag_scales_made[2] = {false, false};
 };
 static PerDevice<IccDecodeWs> g_icd_ws;
 
@@ -48,6 +54,44 @@ static int icd_check_shape(const char* who, size_t n_rows, size_t n_cols, size_t
     return PORLA_OK;
 }
 
+// the byte ranges of a call's requests, for the overlap rule
+struct IcdRange { uintptr_t lo, hi; bool out; };
+
+// the refusals that concern ONE request of n_rows rows (`at`: "request a: "), and its ranges
+static int icd_check_request(const char* who, const std::string& at, const void* d_rows, const void* d_out, const unsigned long long* d_write_steps,
+                             const unsigned int* d_bad, size_t n_rows, size_t n_cols, int form, std::vector<IcdRange>& ranges) {
+    auto bad = [&](const std::string& what) { return bad_arg(who, what); };
+    const size_t symbols = n_rows * n_cols;
+    const size_t in_b = symbols * icd_symbol_bytes(form), out_b = symbols * 32;
+    if (!d_rows || !d_out) return bad(at + "a NULL d_rows or d_out");
+    if (((uintptr_t)d_rows | (uintptr_t)d_out) & 15u) return bad(at + "d_rows or d_out is not 16-byte aligned");
+    if ((uintptr_t)d_write_steps & 7u) return bad(at + "d_write_steps is not 8-byte aligned");
+    if ((uintptr_t)d_bad & 3u) return bad(at + "d_bad is not 4-byte aligned");
+    if (d_write_steps && form == PORLA_ICC_DECODE_EXACT) return bad(at + "d_write_steps with PORLA_ICC_DECODE_EXACT: the unscale is the residue forms'");
+    if (d_bad && form != PORLA_ICC_DECODE_EXACT) return bad(at + "d_bad with a residue form: only PORLA_ICC_DECODE_EXACT counts");
+    if ((uintptr_t)d_rows + in_b < (uintptr_t)d_rows || (uintptr_t)d_out + out_b < (uintptr_t)d_out)
+        return bad(at + "a byte size overflows: a buffer wraps around the address space");
+    ranges.push_back(IcdRange{(uintptr_t)d_rows, (uintptr_t)d_rows + in_b, false});
+    ranges.push_back(IcdRange{(uintptr_t)d_out, (uintptr_t)d_out + out_b, true});
+    if (d_write_steps) ranges.push_back(IcdRange{(uintptr_t)d_write_steps, (uintptr_t)d_write_steps + n_rows * 8, false});
+    if (d_bad) ranges.push_back(IcdRange{(uintptr_t)d_bad, (uintptr_t)d_bad + 4, true});
+    return PORLA_OK;
+}
+
+// an output may overlap nothing, inputs may be shared: sorted by start, an output must begin at or after the end of everything
+// before it and an input at or after the end of every output before it
+static int icd_check_overlap(const char* who, std::vector<IcdRange>& ranges) {
+    std::sort(ranges.begin(), ranges.end(), [](const IcdRange& x, const IcdRange& y) { return x.lo < y.lo; });
+    uintptr_t end_any = 0, end_out = 0;
+    for (const IcdRange& r : ranges) {
+        if (r.lo < (r.out ? end_any : end_out))
+            return bad_arg(who, "an output (d_out or d_bad) overlaps an input or output of this call: outputs must be disjoint from everything");
+        end_any = std::max(end_any, r.hi);
+        if (r.out) end_out = std::max(end_out, r.hi);
+    }
+    return PORLA_OK;
+}
+
 // the checks made before the device is touched
 static int icd_check(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form) {
     auto bad = [&](const std::string& what) { return bad_arg(ICD_WHO, what); };
@@ -57,38 +101,15 @@ static int icd_check(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, 
     size_t t;
     if (k && (!mul_ok(n_rows * n_cols * 2 * ICC30_PLANE_WORDS * 4, k, &t)))
         return bad("a byte size overflows: the residue planes of k requests do not fit a buffer");
-    const size_t symbols = n_rows * n_cols;
-    const size_t in_b = symbols * icd_symbol_bytes(form), out_b = symbols * 32;
-    struct Range { uintptr_t lo, hi; bool out; };
-    std::vector<Range> ranges;
+    std::vector<IcdRange> ranges;
     ranges.reserve(4 * k);
     for (size_t a = 0; a < k; a++) {
         const porla_icc_decode_req& R = reqs[a];
-        const std::string at = "request " + std::to_string(a) + ": ";
-        if (!R.d_rows || !R.d_out) return bad(at + "a NULL d_rows or d_out");
-        if (((uintptr_t)R.d_rows | (uintptr_t)R.d_out) & 15u) return bad(at + "d_rows or d_out is not 16-byte aligned");
-        if ((uintptr_t)R.d_write_steps & 7u) return bad(at + "d_write_steps is not 8-byte aligned");
-        if ((uintptr_t)R.d_bad & 3u) return bad(at + "d_bad is not 4-byte aligned");
-        if (R.d_write_steps && form == PORLA_ICC_DECODE_EXACT) return bad(at + "d_write_steps with PORLA_ICC_DECODE_EXACT: the unscale is the residue forms'");
-        if (R.d_bad && form != PORLA_ICC_DECODE_EXACT) return bad(at + "d_bad with a residue form: only PORLA_ICC_DECODE_EXACT counts");
-        if ((uintptr_t)R.d_rows + in_b < (uintptr_t)R.d_rows || (uintptr_t)R.d_out + out_b < (uintptr_t)R.d_out)
-            return bad(at + "a byte size overflows: a buffer wraps around the address space");
-        ranges.push_back(Range{(uintptr_t)R.d_rows, (uintptr_t)R.d_rows + in_b, false});
-        ranges.push_back(Range{(uintptr_t)R.d_out, (uintptr_t)R.d_out + out_b, true});
-        if (R.d_write_steps) ranges.push_back(Range{(uintptr_t)R.d_write_steps, (uintptr_t)R.d_write_steps + n_rows * 8, false});
-        if (R.d_bad) ranges.push_back(Range{(uintptr_t)R.d_bad, (uintptr_t)R.d_bad + 4, true});
+        if (int rc = icd_check_request(ICD_WHO, "request " + std::to_string(a) + ": ", R.d_rows, R.d_out, R.d_write_steps, R.d_bad, n_rows, n_cols,
+                                       form, ranges))
+            return rc;
     }
-    // an output may overlap nothing, inputs may be shared: sorted by start, an output must begin at or after the end of everything
-    // before it and an input at or after the end of every output before it
-    std::sort(ranges.begin(), ranges.end(), [](const Range& x, const Range& y) { return x.lo < y.lo; });
-    uintptr_t end_any = 0, end_out = 0;
-    for (const Range& r : ranges) {
-        if (r.lo < (r.out ? end_any : end_out))
-            return bad("an output (d_out or d_bad) overlaps an input or output of this call: outputs must be disjoint from everything");
-        end_any = std::max(end_any, r.hi);
-        if (r.out) end_out = std::max(end_out, r.hi);
-    }
-    return PORLA_OK;
+    return icd_check_overlap(ICD_WHO, ranges);
 }
 
 // 2^e mod the modulus of M as a plain integer (e >= 0): e doublings of 1
@@ -203,6 +224,185 @@ int icc_decode_exact_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t 
     return icc_decode_form_enqueue(reqs, k, n_rows, n_cols, n_total, curve, PORLA_ICC_DECODE_EXACT, stream);
 }
 
+// ---- the ragged decode (porla_icc_decode_ragged_batch_device): levels of unequal sizes, kernels in icc_decode_ragged.hip.h.  The
+// launch sequence depends on the pass classes present, never on K or on which sizes are present:
+//
+//   upload              one copy: the requests with their shapes (IcdRagDesc), LARGEST FIRST so that a launch ends in small tiles and the
+//                       requests of one pass count are neighbours; the n_rows^-1 table; per launch the tile starts
+//   k_icd_clear_ragged  EXACT: the counters of the requests that have one
+//   k_icd_exact_ragged / k_icd_residue_ragged    per pass count P present (n_rows <= 2^9: 1; else 2), P launches over ALL requests of
+//                       that count, grid.x = their tiles; the residue planes of the requests of two passes sit one behind the other in
+//                       this workspace's planes
+static const char* const ICR_WHO = "porla_icc_decode_ragged_batch_device";
+constexpr size_t ICR_MAX_TILES = 0xffffffu;               // one launch's grid.x: 256 lanes a block, 2^32 lanes a grid
+
+// one launch: pass pz of the requests [first, first + count) of the sorted list, whose tile starts begin at starts[at]
+struct IcrLaunch { int passes, pz; size_t first, count, at; uint32_t tiles; };
+struct IcrPlan {
+    std::vector<IcdRagDesc> desc;
+    std::vector<uint32_t> starts;
+    std::vector<IcrLaunch> launches;
+    size_t plane_words = 0;
+    bool logn_used[ICD_RAG_MAX_LOG + 1] = {};
+};
+
+// the plan of a call, on the host alone; arguments checked but for the tile count, which is refused here
+static int icr_plan(const porla_icc_decode_ragged_req* reqs, size_t k, size_t ncols, int form, IcrPlan* out) {
+    static_assert(ICD_RAG_MAX_PASSES * (ICC_TILE_LOG - 1) >= ICD_RAG_MAX_LOG, "a level of 2^16 rows has at most ICD_RAG_MAX_PASSES passes");
+    const size_t planes_per = form == PORLA_ICC_DECODE_EXACT ? 2 : 1;
+    std::vector<uint32_t> order(k);
+    for (size_t a = 0; a < k; a++) order[a] = (uint32_t)a;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return reqs[x].n_rows > reqs[y].n_rows; });
+    out->desc.resize(k);
+    std::vector<int> passes_of(k);
+    std::vector<IccPass> plans(k * ICD_RAG_MAX_PASSES);
+    for (size_t i = 0; i < k; i++) {
+        const porla_icc_decode_ragged_req& R = reqs[order[i]];
+        const int logn = ilog2u((size_t)R.n_rows);
+        IccPass plan[ICC_MAX_PASSES];
+        passes_of[i] = icc_pass_plan(logn, ncols, plan);
+        IcdRagDesc& D = out->desc[i];
+        memset(&D, 0, sizeof D);
+        D.d = IcdDesc{(const uint8_t*)R.d_rows, (uint8_t*)R.d_out, R.d_write_steps, R.d_bad};
+        D.logn = (uint32_t)logn;
+        for (int z = 0; z < passes_of[i]; z++) {
+            plans[i * ICD_RAG_MAX_PASSES + z] = plan[z];
+            D.shape[z] = (uint32_t)plan[z].s | (uint32_t)plan[z].ns << 8 | (uint32_t)plan[z].cc_log << 16;
+        }
+        if (passes_of[i] > 1) {
+            D.work = out->plane_words;
+            out->plane_words += planes_per * ((size_t)R.n_rows * ncols * ICC30_PLANE_WORDS);
+        }
+        out->logn_used[logn] = true;
+    }
+    // the requests of one pass count are neighbours (the count grows with n_rows): the highest pass of each group first
+    for (size_t first = 0; first < k;) {
+        size_t end = first;
+        while (end < k && passes_of[end] == passes_of[first]) end++;
+        for (int pz = passes_of[first] - 1; pz >= 0; pz--) {
+            IcrLaunch L{passes_of[first], pz, first, end - first, out->starts.size(), 0};
+            size_t tiles = 0;
+            for (size_t i = first; i < end; i++) {
+                const IccPass& p = plans[i * ICD_RAG_MAX_PASSES + pz];
+                out->starts.push_back((uint32_t)tiles);
+                tiles += p.col_tiles * ((size_t)reqs[order[i]].n_rows >> p.ns);
+                if (tiles > ICR_MAX_TILES)
+                    return bad_arg(ICR_WHO, "more than 2^24 - 1 tiles in one launch: the levels of this call do not fit a grid, split it");
+            }
+            out->starts.push_back((uint32_t)tiles);
+            L.tiles = (uint32_t)tiles;
+            out->launches.push_back(L);
+        }
+        first = end;
+    }
+    return PORLA_OK;
+}
+
+// the checks made before the device is touched
+static int icr_check(const porla_icc_decode_ragged_req* reqs, size_t k, size_t n_cols, size_t n_total, int curve, int form) {
+    auto bad = [&](const std::string& what) { return bad_arg(ICR_WHO, what); };
+    if (k && !reqs) return bad("reqs is NULL");
+    if (int rc = icd_check_shape(ICR_WHO, 2, n_cols, n_total, curve, form)) return rc;          // the call's own arguments
+    if (int rc = check_request_count(ICR_WHO, k)) return rc;
+    std::vector<IcdRange> ranges;
+    ranges.reserve(4 * k);
+    for (size_t a = 0; a < k; a++) {
+        const porla_icc_decode_ragged_req& R = reqs[a];
+        const std::string at = "request " + std::to_string(a) + ": ";
+        const size_t n = (size_t)R.n_rows;
+        if (R.n_rows < 2 || (R.n_rows & (R.n_rows - 1)) != 0 || R.n_rows > n_total) return bad(at + "n_rows must be a power of two, 2 .. n_total");
+        // (n <= 2^16 and n_cols <= 65535: no byte size of one request overflows; all planes together stay below 2^56)
+        if (int rc = icd_check_request(ICR_WHO, at, R.d_rows, R.d_out, R.d_write_steps, R.d_bad, n, n_cols, form, ranges)) return rc;
+    }
+    return icd_check_overlap(ICR_WHO, ranges);
+}
+
+// ws->mu held, ws->fence entered; arguments checked, the plan made
+template <class Q>
+static int icr_enqueue(IccDecodeWs* ws, int curve, const IcrPlan& plan, size_t ncols, size_t n_total, int form, hipStream_t stream) {
+    int rc;
+    const bool exact = form == PORLA_ICC_DECODE_EXACT;
+    const size_t k = plan.desc.size();
+    if (!ws->rag_scales_made[curve]) {
+        for (int l = 0; l <= ICD_RAG_MAX_LOG; l++) {
+            icd_pow2<IccFp>(270 - l, ws->rag_scales[curve][l].p);
+            icd_pow2<Q>(270 - l, ws->rag_scales[curve][l].q);
+        }
+        ws->rag_scales_made[curve] = true;
+    }
+    const size_t desc_b = k * sizeof(IcdRagDesc), scales_b = sizeof ws->rag_scales[curve], starts_b = plan.starts.size() * 4;
+    const size_t list_b = desc_b + scales_b + starts_b;
+    if ((rc = ws->h_list.stage(list_b))) return rc;
+    if ((rc = ws->list.ensure(list_b))) return rc;
+    if (plan.plane_words && (rc = ws->planes.ensure(plan.plane_words * 4))) return rc;
+    uint8_t* h = (uint8_t*)ws->h_list.h;
+    memcpy(h, plan.desc.data(), desc_b);
+    memcpy(h + desc_b, ws->rag_scales[curve], scales_b);
+    memcpy(h + desc_b + scales_b, plan.starts.data(), starts_b);
+    if ((rc = ws->h_list.send(ws->list.p, list_b, stream))) return rc;
+    const uint8_t* d = (const uint8_t*)ws->list.p;
+    const IcdRagDesc* d_desc = (const IcdRagDesc*)d;
+    const IcdScale* d_scales = (const IcdScale*)(d + desc_b);
+    const uint32_t* d_starts = (const uint32_t*)(d + desc_b + scales_b);
+    if (exact) {
+        hipLaunchKernelGGL(k_icd_clear_ragged, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, stream, d_desc, (uint32_t)k);
+        PORLA_HIP(hipGetLastError());
+    }
+    const uint32_t *twp = nullptr, *twqi = nullptr;
+    if ((rc = icc_decode_tables_acquire(curve, n_total, exact, stream, &twp, &twqi))) return rc;
+    uint32_t* planes = (uint32_t*)ws->planes.p;
+    for (const IcrLaunch& L : plan.launches) {
+        const dim3 grid(L.tiles), block(ICC30_SPLIT_THREADS);
+        const bool first = L.pz == L.passes - 1, last = L.pz == 0;
+        const IcdRagDesc* desc = d_desc + L.first;
+        const uint32_t* starts = d_starts + L.at;
+        ProfScope ps("icc_decode_ragged", stream);
+#define PORLA_ICR_EXACT(F, L_)                                                                                                      \
+    hipLaunchKernelGGL((k_icd_exact_ragged<Q, F, L_>), grid, block, 0, stream, desc, starts, (uint32_t)L.count, L.pz, d_scales, planes, \
+                       twp, twqi, (uint32_t)n_total, (uint32_t)ncols)
+#define PORLA_ICR_RESIDUE(S, L_)                                                                                                    \
+    hipLaunchKernelGGL((k_icd_residue_ragged<S, L_>), grid, block, 0, stream, desc, starts, (uint32_t)L.count, L.pz, d_scales, planes,  \
+                       twp, (uint32_t)n_total, ilog2u(n_total), (uint32_t)ncols)
+        if (exact) {
+            if (first && last) PORLA_ICR_EXACT(true, true);
+            else if (first) PORLA_ICR_EXACT(true, false);
+            else if (last) PORLA_ICR_EXACT(false, true);
+            else if constexpr (2 * (ICC_TILE_LOG - 1) < ICD_RAG_MAX_LOG) PORLA_ICR_EXACT(false, false);    // (a third pass: small tiles only)
+        } else if (!first) {
+            if (last) PORLA_ICR_RESIDUE(ICD_WORK, true);
+            else if constexpr (2 * (ICC_TILE_LOG - 1) < ICD_RAG_MAX_LOG) PORLA_ICR_RESIDUE(ICD_WORK, false);
+        } else if (form == PORLA_ICC_DECODE_RESIDUE64) {
+            if (last) PORLA_ICR_RESIDUE(ICD_ROWS64, true);
+            else PORLA_ICR_RESIDUE(ICD_ROWS64, false);
+        } else {
+            if (last) PORLA_ICR_RESIDUE(ICD_ROWS32, true);
+            else PORLA_ICR_RESIDUE(ICD_ROWS32, false);
+        }
+#undef PORLA_ICR_EXACT
+#undef PORLA_ICR_RESIDUE
+    }
+    if (hipGetLastError() != hipSuccess) { set_last_error("porla: ragged ICC decode batch: a launch failed"); rc = PORLA_ERR_HIP; }
+    const int r1 = icc_mix_tables_release(stream);
+    return rc ? rc : r1;
+}
+
+static int icr_run(const IcrPlan& plan, size_t n_cols, size_t n_total, int curve, int form, hipStream_t stream) {
+    IccDecodeWs* ws = nullptr;
+    if (int rc = g_icd_ws.get(&ws)) return rc;
+    return FencedCall(ws, stream).run([&] {
+        return curve == 0 ? icr_enqueue<IccBn254Fr>(ws, 0, plan, n_cols, n_total, form, stream)
+                          : icr_enqueue<IccSecp256k1Fn>(ws, 1, plan, n_cols, n_total, form, stream);
+    });
+}
+
+int icc_decode_ragged_enqueue(const porla_icc_decode_ragged_req* reqs, size_t k, size_t n_cols, size_t n_total, int curve, int form,
+                              hipStream_t stream) {
+    if (k == 0) return PORLA_OK;
+    IcrPlan plan;
+    if (int rc = icr_plan(reqs, k, n_cols, form, &plan)) return rc;
+    return icr_run(plan, n_cols, n_total, curve, form, stream);
+}
+
 }  // namespace porla
 
 using namespace porla;
@@ -224,6 +424,25 @@ extern "C" int porla_icc_decode_batch_device(const porla_icc_decode_req* reqs, s
     if ((rc = g_icd_ws.get(&ws))) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
     return FencedCall(ws, stream).run([&] { return icd_run(ws, reqs, k, n_rows, n_cols, n_total, curve, form, stream); });
+}
+
+static_assert(sizeof(porla_icc_decode_ragged_req) == PORLA_ICC_DECODE_RAGGED_REQ_BYTES, "porla_icc_decode_ragged_req size");
+static_assert(offsetof(porla_icc_decode_ragged_req, d_rows) == 0 && offsetof(porla_icc_decode_ragged_req, d_out) == 8 &&
+              offsetof(porla_icc_decode_ragged_req, d_write_steps) == 16 && offsetof(porla_icc_decode_ragged_req, d_bad) == 24 &&
+              offsetof(porla_icc_decode_ragged_req, n_rows) == 32,
+              "porla_icc_decode_ragged_req offsets (include/porla_gpu.h): porla_icc_decode_req field for field, then n_rows");
+static_assert(offsetof(IcdRagDesc, d) == 0 && offsetof(IcdRagDesc, logn) == 32 && offsetof(IcdRagDesc, shape) == 36 &&
+              offsetof(IcdRagDesc, work) == 48, "IcdRagDesc: the request's pointers, its shape, its planes");
+
+extern "C" int porla_icc_decode_ragged_batch_device(const porla_icc_decode_ragged_req* reqs, size_t k, size_t n_cols, size_t n_total, int curve,
+                                                    int form, void* hip_stream) {
+    int rc = icr_check(reqs, k, n_cols, n_total, curve, form);
+    if (rc) return rc;
+    if (k == 0) return PORLA_OK;
+    IcrPlan plan;
+    if ((rc = icr_plan(reqs, k, n_cols, form, &plan))) return rc;
+    if ((rc = ensure_device())) return rc;
+    return icr_run(plan, n_cols, n_total, curve, form, (hipStream_t)hip_stream);
 }
 
 // one level from host memory: upload, the batch of one request on the engine's stream, download

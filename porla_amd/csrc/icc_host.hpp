@@ -67,6 +67,10 @@ int icc_decode_exact_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t 
 // ... and in any of the three forms (the aligned retrieval: the residue forms carry the requests' d_write_steps through)
 int icc_decode_form_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t n_rows, size_t n_cols, size_t n_total, int curve, int form,
                             hipStream_t stream);
+// ... and levels of UNEQUAL sizes (porla_icc_decode_ragged_batch_device's body; the file extraction): one upload, one lock, fence and
+// table lease, launches by the pass classes present.  n_rows of every request: a power of two, 2 .. n_total
+int icc_decode_ragged_enqueue(const porla_icc_decode_ragged_req* reqs, size_t k, size_t n_cols, size_t n_total, int curve, int form,
+                              hipStream_t stream);
 // ... and levels of ONE row in the form RESIDUE64 (below the decode's smallest level: level 0's Y row of the file extraction): d_out =
 // the row's symbols times wt^-1 mod p_icc, canonical; d_write_steps points to the row's one write step, d_bad is not read
 int icc_decode_row0_enqueue(const porla_icc_decode_req* reqs, size_t k, size_t n_cols, size_t n_total, int curve, hipStream_t stream);

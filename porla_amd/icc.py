@@ -4,7 +4,7 @@ C ABI (include/porla_gpu.h: porla_icc_encode_*).  Rows are in the reference's ow
 little-endian chunks in (utils.h:353-364), 64-byte little-endian values mod LCM out (utils.h:473-517)."""
 import ctypes
 
-from .loader import IccDecodeReq, IccMacDecodeReq, ServerRebuildReq, UpdateReq, lib
+from .loader import IccDecodeRaggedReq, IccDecodeReq, IccMacDecodeReq, ServerRebuildReq, UpdateReq, lib
 
 CURVE = {"bn254": 0, "secp256k1": 1}
 NUM_CHUNKS = 128  # config.hpp:22
@@ -254,6 +254,26 @@ def decode_batch_device(reqs, n_rows, n_cols, n_total, curve, form, stream=0):
     arr = decode_requests(reqs)
     _check(lib.porla_icc_decode_batch_device(arr, len(reqs), n_rows, n_cols, n_total, CURVE[curve], DECODE_FORM[form],
                                              ctypes.c_void_p(stream)))
+
+
+def decode_ragged_requests(reqs):
+    """a ctypes array of porla_icc_decode_ragged_req from per-level tuples (d_rows, d_out, d_write_steps or 0, d_bad or 0, n_rows):
+    device addresses as integers, then the level's own row count"""
+    arr = (IccDecodeRaggedReq * max(len(reqs), 1))()
+    for i, r in enumerate(reqs):
+        if len(r) != 5:
+            raise ValueError("decode_ragged_batch_device: request %d has %d fields, want 5" % (i, len(r)))
+        arr[i] = IccDecodeRaggedReq(*[(x or None) for x in r[:4]], r[4])
+    return arr
+
+
+def decode_ragged_batch_device(reqs, n_cols, n_total, curve, form, stream=0):
+    """decode_batch_device for levels of unequal sizes in ONE asynchronous call on `stream`: every request brings its own n_rows (a
+    power of two, 2 .. n_total) and gets the bytes decode_batch_device writes for it alone; the launches depend on whether levels of up
+    to 2^9 rows and larger ones are present, not on how many or which.  `reqs`: tuples as decode_ragged_requests takes them."""
+    arr = decode_ragged_requests(reqs)
+    _check(lib.porla_icc_decode_ragged_batch_device(arr, len(reqs), n_cols, n_total, CURVE[curve], DECODE_FORM[form],
+                                                    ctypes.c_void_p(stream)))
 
 
 def decode_host(rows, n_rows, n_cols, n_total, curve="bn254", form="exact", write_steps=None, want_bad=None):

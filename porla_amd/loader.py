@@ -97,6 +97,17 @@ PORLA_ICC_DECODE_REQ_BYTES = 32
 assert ctypes.sizeof(IccDecodeReq) == PORLA_ICC_DECODE_REQ_BYTES
 
 
+class IccDecodeRaggedReq(ctypes.Structure):
+    """porla_icc_decode_ragged_req, include/porla_gpu.h: one level of porla_icc_decode_ragged_batch_device: porla_icc_decode_req, then
+    the level's own n_rows (PORLA_ICC_DECODE_RAGGED_REQ_BYTES = 40)."""
+    _fields_ = [("d_rows", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("d_write_steps", ctypes.c_void_p), ("d_bad", ctypes.c_void_p),
+                ("n_rows", ctypes.c_ulonglong)]
+
+
+PORLA_ICC_DECODE_RAGGED_REQ_BYTES = 40
+assert ctypes.sizeof(IccDecodeRaggedReq) == PORLA_ICC_DECODE_RAGGED_REQ_BYTES
+
+
 class IccMacDecodeReq(ctypes.Structure):
     """porla_icc_mac_decode_req, include/porla_gpu.h: one level of porla_icc_mac_decode_batch_device
     (PORLA_ICC_MAC_DECODE_REQ_BYTES = 32)."""
@@ -337,6 +348,8 @@ def _declare(L):
     L.porla_ipa_server_rebuild_aligned_batch_device.restype = ctypes.c_int
     L.porla_icc_decode_batch_device.argtypes = [ctypes.POINTER(IccDecodeReq), sz, sz, sz, sz, ctypes.c_int, ctypes.c_int, vp]
     L.porla_icc_decode_batch_device.restype = ctypes.c_int
+    L.porla_icc_decode_ragged_batch_device.argtypes = [ctypes.POINTER(IccDecodeRaggedReq), sz, sz, sz, ctypes.c_int, ctypes.c_int, vp]
+    L.porla_icc_decode_ragged_batch_device.restype = ctypes.c_int
     L.porla_icc_decode_host.argtypes = [u8p, sz, sz, sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), vp,
                                         ctypes.POINTER(ctypes.c_uint)]
     L.porla_icc_decode_host.restype = ctypes.c_int
