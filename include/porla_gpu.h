@@ -1197,10 +1197,12 @@ int porla_ipa_extract_batch_device(porla_fixed_base *alpha_generators_fb, porla_
  * entry in data_y or mac_y; whenever the pointer is given, a tried level's pointer of the three Y families, d_prf_y or d_work_y not
  * 16-byte aligned, and a byte size that wraps; d_work_y and d_row_status_y are outputs in the overlap walk, the Y inputs may be shared
  * between requests.  k = 0, PORLA_ERR_STATE and PORLA_ERR_NO_DEVICE as in the call above.
- * Not in this call: the top level's Y half (a failed top level behaves as above); a host-memory form; n_total > 2^16; a cross-check
+ * Not in this call: the top level's Y half (a failed top level behaves as above; porla_*_extract_xyt_batch_device below takes it row
+ * by row); a host-memory form; n_total > 2^16; a cross-check
  * of a Y decode against a clean X decode of the same level.  tools/bench_extract_xy.py times it (profiles/r24_a_extract_xy.jsonl). */
 #define PORLA_EXTRACT_XY_REQ_BYTES 160   /* sizeof(porla_extract_xy_req) on LP64; the library static_asserts it and each offset */
-#define PORLA_EXTRACT_FROM_Y        8    /* d_flags: the copy comes from a level's Y half: chunks mod p_icc (RESIDUE is set too) */
+#define PORLA_EXTRACT_FROM_Y        8    /* d_flags: the copy comes from a level's Y half.  A lower level's: chunks mod p_icc, RESIDUE is
+                                            set too.  The top level's (porla_*_extract_xyt_batch_device): RESIDUE follows top_form alone */
 #define PORLA_EXTRACT_ROW_NOT_TRIED 2    /* d_row_status_y: the row's level is not in y_levels */
 typedef struct {
     unsigned long long  write_step;     /*   0: the fields of porla_extract_req, at its offsets */
@@ -1229,6 +1231,80 @@ typedef struct {
 int porla_kzg_extract_xy_batch_device(const porla_extract_xy_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
 int porla_ipa_extract_xy_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t alpha_be[32],
                                       const porla_extract_xy_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
+
+/* ---- verified file extraction with the top level's Y half: a damaged top level is rebuilt row by row from its second copy ----
+ * The top level holds U, every block not rewritten since the last rebuild, and the calls above drop all of it for one damaged X row.
+ * Its Y half is written by ONE rebuild with ONE wt = w^reverse_bits(top_step % n_total, log2 n_total) for all rows, and the network
+ * is linear: row by row Y_j = wt X_j mod LCM (porla_icc_encode_xy_device above), and mod p_icc in the aligned form of
+ * porla_*_server_rebuild_aligned_batch_device.  So no second decode is needed and no half has to be entirely clean: every damaged X
+ * row is replaced by wt^-1 times its own Y row, and the top level's one decode runs on the patched half.  A top level damaged in BOTH
+ * halves survives as long as no row index is damaged in both; in the exact form the recovered blocks are the exact 256-bit chunks.
+ * This call takes the arguments of the call above over porla_extract_xyt_req -- porla_extract_xy_req field for field in its first
+ * 160 bytes, then the top level's Y half.  With top_y == 1 and a top level present, everything else being the call above's:
+ *   1t. Check.  Every top-level Y row gets the status of porla_*_retrieve_aligned_batch_device on that half in top_form's symbol
+ *       width, with d_top_align_y and d_prf_top_y, in d_row_status_top_y.  The half is one more half of a pass that exists already
+ *       (the 64-byte pass for PORLA_ICC_DECODE_EXACT, the RESIDUE32 pass otherwise): the check's launch count does not grow.
+ *   2t. Source of a top-level row: X if its X status is OK; else Y if its Y status is OK; else none.  The top level is failed iff some
+ *       row has no source; bit log2 n_total of the failed mask and UNSURE then are as in rules 4 / 6y.
+ *   3t. Patch.  d_top_patch row j is X row j as it lies, or wt^-1 Y_j, canonical: below LCM as 64 little-endian bytes in the exact
+ *       form, below p_icc in the RESIDUE32 form.  wt^-1 has two planes: mod p_icc the factor w^(N - e) the residue decode's unscale
+ *       uses for that write step, mod q the inverse of (wt mod q).  Any 64 (32) bytes of a Y row are defined: they are reduced as
+ *       the decode's load reduces them.  With top_step % n_total == 0 (wt = 1) the Y row is copied as it lies; a row without a source
+ *       keeps its X row.
+ *   4t. Decode.  The top level's ONE decode (the ragged exact decode, or the uniform RESIDUE32 decode) reads d_top_patch instead of
+ *       d_top_rows and writes into d_blocks; its bad-symbol count goes into d_counts[1].
+ *   5t. A slot the top level wins: FOUND; RESIDUE iff top_form is RESIDUE32; FROM_Y iff d_counts[7] > 0 -- every decoded block
+ *       depends on every row.
+ *   6t. d_counts, EIGHT words: [0 .. 5] as above ([0] the X and top X rows with status 0), [6] the tried top-level Y rows with status
+ *       0, [7] the top-level rows taken from the Y half.  d_row_status is unchanged.
+ * With top_y == 0, or without a top level, the six outputs and d_counts[0 .. 5] of the call above come back byte for byte, d_counts[6
+ * .. 7] are 0, d_row_status_top_y -- if given -- is filled with PORLA_EXTRACT_ROW_NOT_TRIED and the six new pointers may be NULL.  With
+ * top_y == 1 and a clean X half the patched half is the X half and those outputs are the call above's again.
+ * Launches: when some file of the call has its top Y half tried, ONE patch kernel between the check and the decodes (a lane per symbol,
+ * one read and one write of the half) and the larger clear; files with and without top_y mix in one call.  The sequence depends on
+ * the symbol widths and pass classes present and on whether a top Y half is tried at all, never on K.  Contract: as the calls above.
+ * PORLA_ERR_ARG (with a message, before the device is touched): everything the call above refuses (d_counts is 32 bytes here); with
+ * top_y == 1 and a top level a NULL d_top_rows_y, d_top_macs_y, d_prf_top_y, d_top_patch or d_row_status_top_y; any of the six new
+ * pointers not 16-byte aligned, wherever given; top_y above 1; a byte size that wraps; d_top_patch and d_row_status_top_y are outputs
+ * in the overlap walk, the three Y inputs may be shared between requests.  k = 0, PORLA_ERR_STATE and PORLA_ERR_NO_DEVICE as above.
+ * Not in this call: a host-memory form; n_total > 2^16; writing the repaired rows back into the server's store; a row damaged in
+ * both halves.  tools/bench_extract_xyt.py times it (profiles/r26_a_extract_xyt.jsonl). */
+#define PORLA_EXTRACT_XYT_REQ_BYTES 224   /* sizeof(porla_extract_xyt_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    unsigned long long  write_step;         /*   0: the fields of porla_extract_xy_req, at its offsets */
+    void *const        *data_x;             /*   8 */
+    void *const        *mac_x;              /*  16 */
+    const void         *d_top_rows;         /*  24 */
+    const void         *d_top_macs;         /*  32 */
+    const void         *d_top_align;        /*  40 */
+    const void         *d_prf;              /*  48 */
+    void               *d_work;             /*  56 */
+    void               *d_blocks;           /*  64 */
+    unsigned int       *d_steps;            /*  72 */
+    unsigned char      *d_flags;            /*  80 */
+    unsigned char      *d_row_status;       /*  88 */
+    unsigned int       *d_counts;           /*  96: EIGHT words or NULL, zeroed by the call */
+    void *const        *data_y;             /* 104 */
+    void *const        *mac_y;              /* 112 */
+    void *const        *align_y;            /* 120 */
+    const void         *d_prf_y;            /* 128 */
+    void               *d_work_y;           /* 136 */
+    unsigned char      *d_row_status_y;     /* 144 */
+    unsigned long long  y_levels;           /* 152 */
+    const void         *d_top_rows_y;       /* 160: the top level's resident Y half: n_total rows in top_form (64-byte symbols below LCM,
+                                                    or 32-byte symbols below p_icc) */
+    const void         *d_top_macs_y;       /* 168: its MAC rows, 64 bytes each */
+    const void         *d_top_align_y;      /* 176: its alignment store; NULL = every alignment at infinity */
+    const void         *d_prf_top_y;        /* 184: 16 raw bytes per top-level Y row, read as d_prf is read */
+    void               *d_top_patch;        /* 192: scratch, n_total x n_cols x (64 or 32) bytes: the patched half */
+    unsigned char      *d_row_status_top_y; /* 200: n_total status bytes */
+    unsigned long long  top_step;           /* 208: the write step the rebuild that wrote the top level was given (the protocol:
+                                                    write_step - t, a multiple of n_total; any value is accepted, as the rebuild calls do) */
+    unsigned long long  top_y;              /* 216: 1 = try the top level's Y half; 0 = do not; anything else is refused */
+} porla_extract_xyt_req;
+int porla_kzg_extract_xyt_batch_device(const porla_extract_xyt_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
+int porla_ipa_extract_xyt_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t alpha_be[32],
+                                       const porla_extract_xyt_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
 
 /* ---- AES on the device: the MAC PRF of the client writes, the audit challenge from its seed, the client's complement scalar ----
  * These calls PRODUCE the buffers the batches above consume (d_prf; d_idx* / d_coef* / d_mac_*; the 32-byte scalars of

@@ -1,17 +1,20 @@
 // The verified file extraction (include/porla_gpu.h: porla_{kzg,ipa}_extract_batch_device and, with the lower levels' Y halves as a
-// second source, porla_{kzg,ipa}_extract_xy_batch_device): every resident level of K files checked row by row against its stored MAC
+// second source, porla_{kzg,ipa}_extract_xy_batch_device, and with the top level's Y half row by row,
+// porla_{kzg,ipa}_extract_xyt_batch_device): every resident level of K files checked row by row against its stored MAC
 // rows, the halves decoded, and the decoded blocks merged into each file's block store by "newest authentic copy wins", in ONE
-// asynchronous call.  Kernels and the layout of a file's rows: extract_batch.hip.h.  Both pairs of entry points go through ex_check and
-// ex_enqueue; a request of the first pair is one of the second without Y stores.  Every step is on the caller's stream.  The launch
-// sequence depends on the symbol widths and the pass classes present in the call (levels of up to 2^9 rows, larger ones; among the X
-// halves, among the tried Y halves), never on K and never on which levels are resident:
+// asynchronous call.  Kernels and the layout of a file's rows: extract_batch.hip.h.  All three pairs of entry points go through ex_check
+// and ex_enqueue; a request of the first pair is one of the second without Y stores, one of the second one of the third with top_y =
+// 0.  Every step is on the caller's stream.  The launch sequence depends on the symbol widths and the pass classes present in the call
+// (levels of up to 2^9 rows, larger ones; among the X halves, among the tried Y halves) and on whether a top level's Y half is tried
+// at all, never on K and never on which levels are resident:
 //
 //   upload                the files (ExFile), the halves as requests of the row check (RtDesc) and their start rows, one copy
 //   k_ex_clear            counters, failed-level masks, decode counters, the ranks and doubts of all slots, the untried Y statuses
 //   k_ex_ysteps           a Y half tried: the write steps of the lower-level entries, for the unscale
 //   the row check         retrieve_batch.hip: rt_check_starts_{kzg,ipa}, the aligned retrieval's launches with the search map -- one
-//                         pass over ALL halves of 64-byte symbols (the lower levels' X and tried Y halves, an exact top level), one
-//                         over the RESIDUE32 top levels
+//                         pass over ALL halves of 64-byte symbols (the lower levels' X and tried Y halves, an exact top level and
+//                         its tried Y half), one over the RESIDUE32 top levels and their tried Y halves
+//   k_ex_top_patch        a top level's Y half tried: the half its decode reads, X rows where they checked OK, wt^-1 Y rows elsewhere
 //   the decodes           icc_decode_ragged_enqueue ONCE over the lower levels' X halves of two rows and more (into d_work) and the
 //                         exact top levels (into d_blocks): at most three pass launches whatever sizes are present; the uniform
 //                         icc_decode_form_enqueue for RESIDUE32 top levels; k_ex_level0 for the one-row level; the tried Y halves of
@@ -44,22 +47,27 @@ struct ExtractWs {
 };
 static PerDevice<ExtractWs> g_ex_ws;
 
-// the requests of a call: an array of porla_extract_req, or of porla_extract_xy_req (xy), read as the latter -- the first has no Y stores
+// the requests of a call: an array of porla_extract_req (kind 0), of porla_extract_xy_req (1) or of porla_extract_xyt_req (2), read as
+// the widest -- the first has no Y stores, the second no top-level Y half
 struct ExReqs {
     const void* p;
-    bool xy;
-    porla_extract_xy_req at(size_t a) const {
-        porla_extract_xy_req R;
+    int kind;
+    size_t stride() const {
+        return kind == 2 ? sizeof(porla_extract_xyt_req) : kind == 1 ? sizeof(porla_extract_xy_req) : sizeof(porla_extract_req);
+    }
+    porla_extract_xyt_req at(size_t a) const {
+        porla_extract_xyt_req R;
         memset(&R, 0, sizeof R);
-        if (xy) memcpy(&R, (const uint8_t*)p + a * sizeof(porla_extract_xy_req), sizeof(porla_extract_xy_req));
-        else memcpy(&R, (const uint8_t*)p + a * sizeof(porla_extract_req), sizeof(porla_extract_req));
+        memcpy(&R, (const uint8_t*)p + a * stride(), stride());
         return R;
     }
-    size_t counts_bytes() const { return xy ? 24 : 16; }
+    size_t counts_bytes() const { return kind == 2 ? 32 : kind == 1 ? 24 : 16; }
 };
 
-static inline uint32_t ex_t(const porla_extract_xy_req& R, size_t n_total) { return (uint32_t)(R.write_step % n_total); }
-static inline uint32_t ex_tried(const porla_extract_xy_req& R, size_t n_total) { return (uint32_t)(R.y_levels & ex_t(R, n_total)); }
+static inline uint32_t ex_t(const porla_extract_xyt_req& R, size_t n_total) { return (uint32_t)(R.write_step % n_total); }
+static inline uint32_t ex_tried(const porla_extract_xyt_req& R, size_t n_total) { return (uint32_t)(R.y_levels & ex_t(R, n_total)); }
+// the top level's Y half is tried
+static inline bool ex_top_tried(const porla_extract_xyt_req& R) { return R.top_y == 1 && R.d_top_rows != nullptr; }
 
 // the checks made before the device is touched; n_cols: the row width the buffers are sized by
 static int ex_check(const char* who, const ExReqs& reqs, size_t k, size_t n_cols, size_t n_total, int top_form) {
@@ -72,7 +80,7 @@ static int ex_check(const char* who, const ExReqs& reqs, size_t k, size_t n_cols
     size_t bb, top_b, blocks_b, rows_all;
     // (the kernels number the rows of the call through in 32 bits)
     if (!mul_ok(n_cols, 64, &bb) || !mul_ok(bb, n_total, &top_b) ||
-        (k && (!mul_ok((reqs.xy ? 3 : 2) * n_total, k, &rows_all) || rows_all > 0xffffffffull)))
+        (k && (!mul_ok((size_t)(2 + reqs.kind) * n_total, k, &rows_all) || rows_all > 0xffffffffull)))
         return bad("a byte size overflows: the rows of the call do not fit a buffer");
     bb /= 2;                                                                 // a decoded block
     blocks_b = top_b / 2;
@@ -87,9 +95,16 @@ static int ex_check(const char* who, const ExReqs& reqs, size_t k, size_t n_cols
         ranges.push_back(Range{lo, lo + bytes, out});
     };
     for (size_t a = 0; a < k; a++) {
-        const porla_extract_xy_req R = reqs.at(a);
+        const porla_extract_xyt_req R = reqs.at(a);
         const std::string at = "request " + std::to_string(a) + ": ";
         const uint32_t t = ex_t(R, n_total), ym = ex_tried(R, n_total);
+        const bool ty = ex_top_tried(R);
+        if (R.top_y > 1) return bad(at + "top_y must be 0 or 1");
+        if (ty && (!R.d_top_rows_y || !R.d_top_macs_y || !R.d_prf_top_y || !R.d_top_patch || !R.d_row_status_top_y))
+            return bad(at + "a NULL d_top_rows_y, d_top_macs_y, d_prf_top_y, d_top_patch or d_row_status_top_y with the top level's Y half to try");
+        if (((uintptr_t)R.d_top_rows_y | (uintptr_t)R.d_top_macs_y | (uintptr_t)R.d_top_align_y | (uintptr_t)R.d_prf_top_y |
+             (uintptr_t)R.d_top_patch | (uintptr_t)R.d_row_status_top_y) & 15u)
+            return bad(at + "d_top_rows_y, d_top_macs_y, d_top_align_y, d_prf_top_y, d_top_patch or d_row_status_top_y is not 16-byte aligned");
         const size_t rows = t + (R.d_top_rows ? n_total : 0);
         if (!R.d_blocks || !R.d_steps || !R.d_flags) return bad(at + "a NULL d_blocks, d_steps or d_flags");
         if (rows && (!R.d_prf || !R.d_row_status)) return bad(at + "a NULL d_prf or d_row_status");
@@ -123,6 +138,14 @@ static int ex_check(const char* who, const ExReqs& reqs, size_t k, size_t n_cols
             add(R.d_top_macs, 64 * n_total, false);
             if (R.d_top_align) add(R.d_top_align, 64 * n_total, false);
         }
+        if (ty) {
+            add(R.d_top_rows_y, top_b, false);
+            add(R.d_top_macs_y, 64 * n_total, false);
+            if (R.d_top_align_y) add(R.d_top_align_y, 64 * n_total, false);
+            add(R.d_prf_top_y, 16 * n_total, false);
+            add(R.d_top_patch, top_b, true);
+        }
+        if (R.d_row_status_top_y) add(R.d_row_status_top_y, n_total, true);               // (untried: filled with NOT_TRIED)
         if (rows) {
             add(R.d_prf, 16 * rows, false);
             add(R.d_row_status, rows, true);
@@ -142,7 +165,8 @@ static int ex_check(const char* who, const ExReqs& reqs, size_t k, size_t n_cols
     uintptr_t end_any = 0, end_out = 0;
     for (const Range& r : ranges) {
         if (r.lo < (r.out ? end_any : end_out))
-            return bad(std::string("an output (d_work, d_blocks, d_steps, d_flags, d_row_status") + (reqs.xy ? ", d_work_y, d_row_status_y" : "") +
+            return bad(std::string("an output (d_work, d_blocks, d_steps, d_flags, d_row_status") +
+                       (reqs.kind ? ", d_work_y, d_row_status_y" : "") + (reqs.kind == 2 ? ", d_top_patch, d_row_status_top_y" : "") +
                        " or d_counts) overlaps an input or output of this call: outputs must be disjoint from everything");
         end_any = std::max(end_any, r.hi);
         if (r.out) end_out = std::max(end_out, r.hi);
@@ -166,13 +190,17 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
     std::vector<porla_icc_decode_ragged_req> dec, dec_y;               // the EXACT decodes; the tried Y halves of two rows and more
     std::vector<porla_icc_decode_req> dec_top32, dec_y0;               // RESIDUE32 top levels; level 0's Y rows
     uint32_t t_max = 0, rows_max = 0;
-    bool level0 = false, any_y = false;
-    for (size_t a = 0; a < k && !any_y; a++) any_y = ex_tried(reqs.at(a), n_total) != 0;
+    bool level0 = false, any_y = false, any_top_y = false;
+    for (size_t a = 0; a < k; a++) {
+        any_y = any_y || ex_tried(reqs.at(a), n_total) != 0;
+        any_top_y = any_top_y || ex_top_tried(reqs.at(a));
+    }
     if ((rc = ws->scratch.ensure(k * EX_SCRATCH_WORDS * 4))) return rc;
     if (any_y && ((rc = ws->doubt.ensure(k * n_total * 4)) || (rc = ws->ysteps.ensure(k * n_total * 8)))) return rc;
     for (size_t a = 0; a < k; a++) {
-        const porla_extract_xy_req R = reqs.at(a);
+        const porla_extract_xyt_req R = reqs.at(a);
         const uint32_t t = ex_t(R, n_total), ym = ex_tried(R, n_total);
+        const bool ty = ex_top_tried(R);
         uint32_t* scratch = (uint32_t*)ws->scratch.p + a * EX_SCRATCH_WORDS;
         unsigned long long* ysteps = ym ? (unsigned long long*)ws->ysteps.p + a * n_total : nullptr;
         ExFile& F = files[a];
@@ -193,6 +221,12 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
         F.has_top = R.d_top_rows != nullptr;
         F.y_tried = ym;
         F.n_counts = (uint32_t)(reqs.counts_bytes() / 4);
+        F.status_top_y = R.d_row_status_top_y;
+        F.top_x = (const uint8_t*)R.d_top_rows;
+        F.top_rows_y = (const uint8_t*)R.d_top_rows_y;
+        F.top_patch = (uint8_t*)R.d_top_patch;
+        F.top_y = ty ? 1u : 0u;
+        F.top_e = (uint32_t)rev_bits(R.top_step % n_total, logn);
         level0 = level0 || (t & 1u);
         t_max = std::max(t_max, t);
         rows_max = std::max(rows_max, t + (F.has_top ? (uint32_t)n_total : 0u));
@@ -223,8 +257,15 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
         }
         if (F.has_top) {
             half_x(residue ? 1 : 0, R.d_top_rows, R.d_top_macs, R.d_top_align, t, n_total);
-            if (residue) dec_top32.push_back(porla_icc_decode_req{R.d_top_rows, R.d_blocks, nullptr, nullptr});
-            else dec.push_back(porla_icc_decode_ragged_req{R.d_top_rows, R.d_blocks, nullptr, scratch + 1 + logn, (unsigned long long)n_total});
+            // the top level's tried Y half: one more half of the same pass, its failures counted in d_counts[6]; the decode then reads
+            // the patched half
+            if (ty)
+                half(residue ? 1 : 0, RtDesc{(const uint8_t*)R.d_top_rows_y, (const uint8_t*)R.d_top_macs_y, (const uint8_t*)R.d_prf_top_y,
+                                             (const uint8_t*)R.d_top_align_y, nullptr, nullptr, R.d_row_status_top_y,
+                                             R.d_counts ? R.d_counts + 6 : nullptr}, n_total);
+            const void* top_rows = ty ? R.d_top_patch : R.d_top_rows;
+            if (residue) dec_top32.push_back(porla_icc_decode_req{top_rows, R.d_blocks, nullptr, nullptr});
+            else dec.push_back(porla_icc_decode_ragged_req{top_rows, R.d_blocks, nullptr, scratch + 1 + logn, (unsigned long long)n_total});
         }
     }
     // one upload: files, requests of both widths, start rows of both widths
@@ -263,6 +304,27 @@ static int ex_enqueue(ExtractWs* ws, porla_fixed_base* fb_alpha, porla_fixed_bas
         rc = kzg ? rt_check_starts_kzg(aligned[w], d_desc[w], map, rows_of[w], ncols, symb, stream)
                  : rt_check_starts_ipa(fb_alpha, fb_h, alpha_ipa, aligned[w], d_desc[w], map, rows_of[w], symb, stream);
         if (rc) return rc;
+    }
+    // the patched top halves, under the data side's table lease
+    if (any_top_y) {
+        const uint32_t *twp = nullptr, *twqi = nullptr;
+        if ((rc = icc_decode_tables_acquire(curve, n_total, !residue, stream, &twp, &twqi))) return rc;
+        {
+            ProfScope ps("extract_top_patch", stream);
+            const dim3 grid(blocks_of(n_total * ncols), ky), block(256);
+            if (residue)
+                hipLaunchKernelGGL((k_ex_top_patch<PORLA_ICC_DECODE_RESIDUE32, IccBn254Fr>), grid, block, 0, stream, d_files, twp, twqi,
+                                   (uint32_t)n_total, (uint32_t)ncols);
+            else if (kzg)
+                hipLaunchKernelGGL((k_ex_top_patch<PORLA_ICC_DECODE_EXACT, IccBn254Fr>), grid, block, 0, stream, d_files, twp, twqi,
+                                   (uint32_t)n_total, (uint32_t)ncols);
+            else
+                hipLaunchKernelGGL((k_ex_top_patch<PORLA_ICC_DECODE_EXACT, IccSecp256k1Fn>), grid, block, 0, stream, d_files, twp, twqi,
+                                   (uint32_t)n_total, (uint32_t)ncols);
+        }
+        if (hipGetLastError() != hipSuccess) { set_last_error("porla: extraction: the top-level patch launch failed"); rc = PORLA_ERR_HIP; }
+        const int r1 = icc_mix_tables_release(stream);
+        if (rc || r1) return rc ? rc : r1;
     }
     // the decodes: one ragged call over every size present; RESIDUE32 top levels are of one size and keep the uniform call
     if (level0) {
@@ -349,21 +411,48 @@ static_assert(offsetof(porla_extract_xy_req, write_step) == 0 && offsetof(porla_
               offsetof(porla_extract_xy_req, d_row_status_y) == 144 && offsetof(porla_extract_xy_req, y_levels) == 152,
               "porla_extract_xy_req offsets (include/porla_gpu.h): porla_extract_req field for field, then the Y stores");
 
+static_assert(sizeof(porla_extract_xyt_req) == PORLA_EXTRACT_XYT_REQ_BYTES, "porla_extract_xyt_req size");
+static_assert(offsetof(porla_extract_xyt_req, write_step) == 0 && offsetof(porla_extract_xyt_req, data_x) == 8 &&
+              offsetof(porla_extract_xyt_req, mac_x) == 16 && offsetof(porla_extract_xyt_req, d_top_rows) == 24 &&
+              offsetof(porla_extract_xyt_req, d_top_macs) == 32 && offsetof(porla_extract_xyt_req, d_top_align) == 40 &&
+              offsetof(porla_extract_xyt_req, d_prf) == 48 && offsetof(porla_extract_xyt_req, d_work) == 56 &&
+              offsetof(porla_extract_xyt_req, d_blocks) == 64 && offsetof(porla_extract_xyt_req, d_steps) == 72 &&
+              offsetof(porla_extract_xyt_req, d_flags) == 80 && offsetof(porla_extract_xyt_req, d_row_status) == 88 &&
+              offsetof(porla_extract_xyt_req, d_counts) == 96 && offsetof(porla_extract_xyt_req, data_y) == 104 &&
+              offsetof(porla_extract_xyt_req, mac_y) == 112 && offsetof(porla_extract_xyt_req, align_y) == 120 &&
+              offsetof(porla_extract_xyt_req, d_prf_y) == 128 && offsetof(porla_extract_xyt_req, d_work_y) == 136 &&
+              offsetof(porla_extract_xyt_req, d_row_status_y) == 144 && offsetof(porla_extract_xyt_req, y_levels) == 152 &&
+              offsetof(porla_extract_xyt_req, d_top_rows_y) == 160 && offsetof(porla_extract_xyt_req, d_top_macs_y) == 168 &&
+              offsetof(porla_extract_xyt_req, d_top_align_y) == 176 && offsetof(porla_extract_xyt_req, d_prf_top_y) == 184 &&
+              offsetof(porla_extract_xyt_req, d_top_patch) == 192 && offsetof(porla_extract_xyt_req, d_row_status_top_y) == 200 &&
+              offsetof(porla_extract_xyt_req, top_step) == 208 && offsetof(porla_extract_xyt_req, top_y) == 216,
+              "porla_extract_xyt_req offsets (include/porla_gpu.h): porla_extract_xy_req field for field, then the top level's Y half");
+
 extern "C" int porla_kzg_extract_batch_device(const porla_extract_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
-    return ex_kzg("porla_kzg_extract_batch_device", ExReqs{reqs, false}, k, n_total, top_form, hip_stream);
+    return ex_kzg("porla_kzg_extract_batch_device", ExReqs{reqs, 0}, k, n_total, top_form, hip_stream);
 }
 
 extern "C" int porla_ipa_extract_batch_device(porla_fixed_base* alpha_generators_fb, porla_fixed_base* h_fb, const uint8_t alpha_be[32],
                                               const porla_extract_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
-    return ex_ipa("porla_ipa_extract_batch_device", alpha_generators_fb, h_fb, alpha_be, ExReqs{reqs, false}, k, n_total, top_form, hip_stream);
+    return ex_ipa("porla_ipa_extract_batch_device", alpha_generators_fb, h_fb, alpha_be, ExReqs{reqs, 0}, k, n_total, top_form, hip_stream);
 }
 
 extern "C" int porla_kzg_extract_xy_batch_device(const porla_extract_xy_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
-    return ex_kzg("porla_kzg_extract_xy_batch_device", ExReqs{reqs, true}, k, n_total, top_form, hip_stream);
+    return ex_kzg("porla_kzg_extract_xy_batch_device", ExReqs{reqs, 1}, k, n_total, top_form, hip_stream);
 }
 
 extern "C" int porla_ipa_extract_xy_batch_device(porla_fixed_base* alpha_generators_fb, porla_fixed_base* h_fb, const uint8_t alpha_be[32],
                                                  const porla_extract_xy_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
-    return ex_ipa("porla_ipa_extract_xy_batch_device", alpha_generators_fb, h_fb, alpha_be, ExReqs{reqs, true}, k, n_total, top_form,
+    return ex_ipa("porla_ipa_extract_xy_batch_device", alpha_generators_fb, h_fb, alpha_be, ExReqs{reqs, 1}, k, n_total, top_form,
+                  hip_stream);
+}
+
+extern "C" int porla_kzg_extract_xyt_batch_device(const porla_extract_xyt_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
+    return ex_kzg("porla_kzg_extract_xyt_batch_device", ExReqs{reqs, 2}, k, n_total, top_form, hip_stream);
+}
+
+extern "C" int porla_ipa_extract_xyt_batch_device(porla_fixed_base* alpha_generators_fb, porla_fixed_base* h_fb, const uint8_t alpha_be[32],
+                                                  const porla_extract_xyt_req* reqs, size_t k, size_t n_total, int top_form, void* hip_stream) {
+    return ex_ipa("porla_ipa_extract_xyt_batch_device", alpha_generators_fb, h_fb, alpha_be, ExReqs{reqs, 2}, k, n_total, top_form,
                   hip_stream);
 }

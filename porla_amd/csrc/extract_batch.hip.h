@@ -18,8 +18,15 @@
 // offsets o_i, decoded mod p_icc.  A level whose X half failed and whose tried Y half is clean is Y-sourced: its blocks bid with the
 // same ranks when chunk 0 mod p_icc names ONE index, and are set aside with a doubt (step + 1, a per-slot maximum) on the slots they
 // may name when it names two -- r0 < D = 2^256 - p_icc: the chunk may be r0 + p_icc, whose low 64 bits are one more.
+//
+// The top level's second source (porla_*_extract_xyt_batch_device) works ROW BY ROW, not level by level: the rebuild that wrote the top
+// level scaled every chunk by ONE wt = w^e, e = reverse_bits(top_step % n_total), and the network is linear, so Y_j = wt X_j mod LCM
+// (mod p_icc in the RESIDUE32 form).  k_ex_top_patch writes the half the top level's one decode reads: row j as its X row lies when
+// that row checked OK, else wt^-1 Y_j when its Y row checked OK -- the p_icc plane by entry (N - e) mod N of the decode's tw30p, the q
+// plane by entry e of its table of inverses -- else the X row again (the level is failed then: k_ex_verdict).
 #pragma once
 #include "retrieve_batch.hip.h"
+#include "icc_decode.hip.h"
 #include "../../include/porla_gpu.h"
 
 namespace porla {
@@ -46,11 +53,19 @@ struct ExFile {
     uint32_t t;                // write_step % n_total
     uint32_t has_top;
     uint32_t y_tried;          // y_levels & t
-    uint32_t n_counts;         // 4, or 6 in the call with Y halves
+    uint32_t n_counts;         // 4, 6 in the call with Y halves, or 8 in the call with the top level's Y half
+    // the top level's Y half (porla_*_extract_xyt_batch_device); top_y == 0 leaves every kernel on the paths above
+    uint8_t* status_top_y;     // d_row_status_top_y or nullptr
+    const uint8_t* top_x;      // d_top_rows
+    const uint8_t* top_rows_y; // d_top_rows_y
+    uint8_t* top_patch;        // d_top_patch: the half the top level's decode reads
+    uint32_t top_y;            // 1: the top level's Y half is tried (top_y == 1 and a top level present)
+    uint32_t top_e;            // reverse_bits(top_step % n_total, log2 n_total): wt = w^top_e
 };
 constexpr int EX_SCRATCH_WORDS = 20;
 constexpr int EX_SCRATCH_FAILED_Y = 18;
-static_assert(sizeof(ExFile) == 120, "ExFile: twelve pointers, the epoch and four words");
+constexpr int EX_SCRATCH_TOP_FROM_Y = 19;                                 // the top-level rows taken from the Y half
+static_assert(sizeof(ExFile) == 160, "ExFile: sixteen pointers, the epoch and six words");
 
 // the level of entry r < t of a file's ascending layout, and the entry's place in the level
 __device__ __forceinline__ uint32_t ex_level_of_entry(uint32_t t, uint32_t r, uint32_t& p) {
@@ -64,10 +79,16 @@ __device__ __forceinline__ uint32_t ex_level_of_entry(uint32_t t, uint32_t r, ui
 }
 // the epoch write step of entry p of level i
 __device__ __forceinline__ uint32_t ex_step_of(uint32_t t, uint32_t i, uint32_t p) { return (t & ~((2u << i) - 1u)) + 1u + p; }
+// the source of top-level row j: 0 the X row, 1 the Y row, 2 none
+__device__ __forceinline__ uint32_t ex_top_source(const ExFile& F, uint32_t j) {
+    if (F.status[F.t + j] != 0) return 0u;
+    return F.top_y && F.status_top_y[j] == PORLA_RETRIEVE_ROW_OK ? 1u : 2u;
+}
 // the levels whose source is the Y half: X failed, Y tried and clean
 __device__ __forceinline__ uint32_t ex_y_sourced(const ExFile& F) { return F.scratch[0] & F.y_tried & ~F.scratch[EX_SCRATCH_FAILED_Y]; }
 
-// counters, failed-level masks, decode counters, the ranks and doubts of every slot: zero; the Y statuses of untried levels
+// counters, failed-level masks, decode counters, the ranks and doubts of every slot: zero; the Y statuses of untried levels and of
+// an untried top level
 __global__ void __launch_bounds__(256)
 k_ex_clear(const ExFile* __restrict__ files, uint32_t n_total) {
     const ExFile& F = files[blockIdx.y];
@@ -79,6 +100,43 @@ k_ex_clear(const ExFile* __restrict__ files, uint32_t n_total) {
     if (i < F.t && F.status_y) {
         uint32_t p;
         if (!(F.y_tried >> ex_level_of_entry(F.t, i, p) & 1u)) F.status_y[i] = PORLA_EXTRACT_ROW_NOT_TRIED;
+    }
+    if (i < n_total && F.status_top_y && !F.top_y) F.status_top_y[i] = PORLA_EXTRACT_ROW_NOT_TRIED;
+}
+
+// ---- the patched top half: a lane per symbol of file blockIdx.y.  FORM: PORLA_ICC_DECODE_EXACT (64-byte symbols, both planes, joined
+// below LCM as the encode's finish joins them) or PORLA_ICC_DECODE_RESIDUE32 (32-byte symbols, the p_icc plane alone; Q is unused).
+// A row from the X half, a row without a source and -- with wt = 1 -- a row from the Y half are copied as they lie.  Any 64 (32) input
+// bytes are defined: the symbol enters below 2 p by the decode's load step (icd_load64; a 256-bit value is below 2 p_icc as it is), the
+// product with the table entry is below p + 2^250, the finish makes it canonical.  16-byte accesses, plain vector stores.
+template <int FORM, class Q>
+__global__ void __launch_bounds__(256)
+k_ex_top_patch(const ExFile* __restrict__ files, const uint32_t* __restrict__ twp, const uint32_t* __restrict__ twqi, uint32_t n_total,
+               uint32_t ncols) {
+    constexpr uint32_t SYMB = FORM == PORLA_ICC_DECODE_EXACT ? 64u : 32u;
+    const ExFile& F = files[blockIdx.y];
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!F.top_y || i >= (size_t)n_total * ncols) return;
+    const uint32_t j = (uint32_t)(i / ncols);
+    const bool from_y = ex_top_source(F, j) == 1u;
+    const uint8_t* src = (from_y ? F.top_rows_y : F.top_x) + SYMB * i;
+    uint8_t* dst = F.top_patch + SYMB * i;
+    if (!from_y || F.top_e == 0u) {
+        const uint4* s = reinterpret_cast<const uint4*>(src);
+        uint4* d = reinterpret_cast<uint4*>(dst);
+#pragma unroll
+        for (uint32_t w = 0; w < SYMB / 16u; w++) d[w] = s[w];
+        return;
+    }
+    if (FORM == PORLA_ICC_DECODE_EXACT) {
+        const F30<IccFp> rp = icc30_mul<IccFp>(icd_tw<IccFp>(twp, n_total, F.top_e), icd_load64<IccFp>(src));
+        const F30<Q> rq = icc30_mul<Q>(icd_tw<Q>(twqi, n_total, F.top_e), icd_load64<Q>(src));
+        IccOut o;
+        o.x = F.top_patch; o.al = nullptr; o.sc = nullptr; o.qres = nullptr; o.scalar_le = 0;
+        icc30_finish_q<Q>(icc30_finish_p(rp), rq, i, o);
+    } else {
+        const F30<IccFp> y = f30_unpack<IccFp>(ld_fe<IccFp>(reinterpret_cast<const uint32_t*>(src)).v);
+        st_fe<IccFp>(reinterpret_cast<uint32_t*>(dst), icc30_finish_p(icc30_mul<IccFp>(icd_tw<IccFp>(twp, n_total, F.top_e), y)));
     }
 }
 
@@ -107,7 +165,8 @@ k_ex_level0(const ExFile* __restrict__ files, uint32_t ncols) {
     if ((x.x | x.y | x.z | x.w | y.x | y.y | y.z | y.w) != 0u) atomicAdd(F.scratch + 1, 1u);
 }
 
-// the verdict: a lane per resident row; a row with status 0 fails its level -- an X or top row in word 0, a tried Y row in the Y word
+// the verdict: a lane per resident row; a row with status 0 fails its level -- an X row in word 0, a tried Y row in the Y word -- and a
+// top-level row fails the top level when it has no source; the top-level rows taken from the Y half are counted
 __global__ void __launch_bounds__(256)
 k_ex_verdict(const ExFile* __restrict__ files, uint32_t n_total, uint32_t top_bit) {
     const ExFile& F = files[blockIdx.y];
@@ -120,8 +179,17 @@ k_ex_verdict(const ExFile* __restrict__ files, uint32_t n_total, uint32_t top_bi
     }
     if (r >= rows) return;
     uint32_t p;
-    if (F.status[r] == 0) atomicOr(F.scratch, 1u << (r < F.t ? ex_level_of_entry(F.t, r, p) : top_bit));
-    if (r < F.t && F.y_tried && F.status_y[r] == 0) atomicOr(F.scratch + EX_SCRATCH_FAILED_Y, 1u << ex_level_of_entry(F.t, r, p));
+    if (r >= F.t) {
+        const uint32_t source = ex_top_source(F, r - F.t);
+        if (source == 2u) atomicOr(F.scratch, 1u << top_bit);
+        if (source == 1u) {
+            atomicAdd(F.scratch + EX_SCRATCH_TOP_FROM_Y, 1u);
+            if (F.counts) atomicAdd(F.counts + 7, 1u);
+        }
+        return;
+    }
+    if (F.status[r] == 0) atomicOr(F.scratch, 1u << ex_level_of_entry(F.t, r, p));
+    if (F.y_tried && F.status_y[r] == 0) atomicOr(F.scratch + EX_SCRATCH_FAILED_Y, 1u << ex_level_of_entry(F.t, r, p));
 }
 
 // r0 < D = 2^256 - p_icc = 49 * 2^248 - 1, r0 as eight little-endian words: then r0 + p_icc is a 256-bit chunk too
@@ -166,7 +234,8 @@ k_ex_rank(const ExFile* __restrict__ files, uint32_t n_total, uint32_t ncols) {
     }
 }
 
-// gather: a block per slot.  The winner's bytes (a top-level winner lies in d_blocks already), or zeros; step, flags, counts[3]
+// gather: a block per slot.  The winner's bytes (a top-level winner lies in d_blocks already), or zeros; step, flags, counts[3].  A
+// top-level winner carries FROM_Y when any row of the patched half came from the Y half: every decoded block depends on every row
 __global__ void __launch_bounds__(64)
 k_ex_gather(const ExFile* __restrict__ files, uint32_t ncols, uint32_t top_bit, uint32_t residue) {
     const ExFile& F = files[blockIdx.y];
@@ -197,7 +266,8 @@ k_ex_gather(const ExFile* __restrict__ files, uint32_t ncols, uint32_t top_bit, 
     if (threadIdx.x == 0u) {
         F.steps[slot] = enc ? enc - 1u : 0xffffffffu;
         F.flags[slot] = (uint8_t)((enc ? PORLA_EXTRACT_FOUND : 0) | (unsure ? PORLA_EXTRACT_UNSURE : 0) |
-                                  (enc == 1u && residue ? PORLA_EXTRACT_RESIDUE : 0) | (y ? PORLA_EXTRACT_RESIDUE | PORLA_EXTRACT_FROM_Y : 0));
+                                  (enc == 1u && residue ? PORLA_EXTRACT_RESIDUE : 0) | (y ? PORLA_EXTRACT_RESIDUE | PORLA_EXTRACT_FROM_Y : 0) |
+                                  (enc == 1u && F.scratch[EX_SCRATCH_TOP_FROM_Y] ? PORLA_EXTRACT_FROM_Y : 0));
         if ((enc == 0u || unsure) && F.counts) atomicAdd(F.counts + 3, 1u);
     }
 }

@@ -170,6 +170,18 @@ PORLA_EXTRACT_ROW_NOT_TRIED = 2
 assert ctypes.sizeof(ExtractXyReq) == PORLA_EXTRACT_XY_REQ_BYTES
 
 
+class ExtractXytReq(ctypes.Structure):
+    """porla_extract_xyt_req, include/porla_gpu.h: one file of porla_kzg_extract_xyt_batch_device / porla_ipa_extract_xyt_batch_device
+    (PORLA_EXTRACT_XYT_REQ_BYTES = 224): ExtractXyReq field for field, then the top level's Y half."""
+    _fields_ = ExtractXyReq._fields_ + [("d_top_rows_y", ctypes.c_void_p), ("d_top_macs_y", ctypes.c_void_p), ("d_top_align_y", ctypes.c_void_p),
+                                        ("d_prf_top_y", ctypes.c_void_p), ("d_top_patch", ctypes.c_void_p),
+                                        ("d_row_status_top_y", ctypes.c_void_p), ("top_step", ctypes.c_ulonglong), ("top_y", ctypes.c_ulonglong)]
+
+
+PORLA_EXTRACT_XYT_REQ_BYTES = 224
+assert ctypes.sizeof(ExtractXytReq) == PORLA_EXTRACT_XYT_REQ_BYTES
+
+
 class PrfRun(ctypes.Structure):
     """porla_prf_run, include/porla_gpu.h: count triples (level, index0 + t, time0 + t * time_stride) of the MAC PRF
     (PORLA_PRF_RUN_BYTES = 32)."""
@@ -377,6 +389,10 @@ def _declare(L):
     L.porla_kzg_extract_xy_batch_device.restype = ctypes.c_int
     L.porla_ipa_extract_xy_batch_device.argtypes = [vp, vp, u8p, ctypes.POINTER(ExtractXyReq), sz, sz, ctypes.c_int, vp]
     L.porla_ipa_extract_xy_batch_device.restype = ctypes.c_int
+    L.porla_kzg_extract_xyt_batch_device.argtypes = [ctypes.POINTER(ExtractXytReq), sz, sz, ctypes.c_int, vp]
+    L.porla_kzg_extract_xyt_batch_device.restype = ctypes.c_int
+    L.porla_ipa_extract_xyt_batch_device.argtypes = [vp, vp, u8p, ctypes.POINTER(ExtractXytReq), sz, sz, ctypes.c_int, vp]
+    L.porla_ipa_extract_xyt_batch_device.restype = ctypes.c_int
     L.porla_kzg_retrieve_aligned_host.argtypes = [u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp, ctypes.POINTER(ctypes.c_uint)]
     L.porla_kzg_retrieve_aligned_host.restype = ctypes.c_int
     L.porla_ipa_retrieve_aligned_host.argtypes = [vp, vp, u8p, u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp,

@@ -502,6 +502,33 @@ def kzg_extract_xy_batch_device(reqs, n_total, top_form, stream=0):
     del keep
 
 
+def extract_xyt_requests(reqs):
+    """(a ctypes array of porla_extract_xyt_req, what must stay alive beside it) from per-file tuples: the 20 fields extract_xy_requests
+    takes, then (d_top_rows_y, d_top_macs_y, d_top_align_y, d_prf_top_y, d_top_patch, d_row_status_top_y -- device addresses or 0 --
+    top_step, top_y)"""
+    from .loader import ExtractXytReq
+    arr = (ExtractXytReq * max(len(reqs), 1))()
+    keep = []
+    for i, r in enumerate(reqs):
+        if len(r) != 28:
+            raise ValueError("extract_xyt_batch_device: request %d has %d fields, want 28" % (i, len(r)))
+        x = [_host_pointer_array(fam, keep) for fam in r[1:3]]
+        y = [_host_pointer_array(fam, keep) for fam in r[13:16]]
+        arr[i] = ExtractXytReq(r[0], x[0], x[1], *([v or None for v in r[3:13]] + y + [v or None for v in r[16:19]] + [r[19]] +
+                                                   [v or None for v in r[20:26]] + [r[26], r[27]]))
+    return arr, keep
+
+
+def kzg_extract_xyt_batch_device(reqs, n_total, top_form, stream=0):
+    """kzg_extract_xy_batch_device with the top level's Y half as a second source, row by row (porla_kzg_extract_xyt_batch_device): a
+    top-level X row that fails its check is replaced by wt^-1 times its Y row when that row checks OK, and the top level's one decode
+    runs on the patched half; a slot the top level then wins carries FROM_Y; d_counts has eight words ([6] the tried top Y rows with
+    status 0, [7] the rows taken from the Y half).  `reqs`: tuples as extract_xyt_requests takes them."""
+    arr, keep = extract_xyt_requests(reqs)
+    _check(lib.porla_kzg_extract_xyt_batch_device(arr, len(reqs), n_total, RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
+    del keep
+
+
 def kzg_retrieve_aligned_host(rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None, want_blocks=True):
     """one level from host memory (porla_kzg_retrieve_aligned_host; it waits) -> what kzg_retrieve_host returns"""
     n_cols = kzg_row_coefficients()
@@ -624,6 +651,14 @@ class FixedBase:
         arr, keep = extract_xy_requests(reqs)
         _check(lib.porla_ipa_extract_xy_batch_device(self.h, h_fb.h if h_fb is not None else None, _alpha_be(alpha), arr, len(reqs), n_total,
                                                      RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
+        del keep
+
+    def ipa_extract_xyt_batch_device(self, h_fb, alpha, reqs, n_total, top_form, stream=0):
+        """kzg_extract_xyt_batch_device for the IPA build (porla_ipa_extract_xyt_batch_device: 128 columns); self, h_fb and alpha as for
+        ipa_extract_batch_device."""
+        arr, keep = extract_xyt_requests(reqs)
+        _check(lib.porla_ipa_extract_xyt_batch_device(self.h, h_fb.h if h_fb is not None else None, _alpha_be(alpha), arr, len(reqs), n_total,
+                                                      RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
         del keep
 
     def ipa_retrieve_aligned_host(self, h_fb, alpha, rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None,
