@@ -95,6 +95,25 @@ int         porla_gpu_set_msm_small(int on, int window_bits);
 int         porla_gpu_set_msm_glv(int on);
 /* diagnostic: window bits, window count and GLV flag of the most recently launched MSM (what the automatic choice was) */
 int         porla_gpu_last_msm_shape(int *c, int *windows, int *glv);
+/* diagnostic: HOST execution of the single-launch MSM's shape function and launch decision (no device needed), for `count` elements:
+ *   curve 0 = BN254, 1 = secp256k1;  n in 1 .. 32 768;  used_bits in 0 .. 256: bit length of the OR of the scalars;
+ *   c_flags: forced window bits 0 .. 8 in the low byte (0 = automatic, porla_gpu_set_msm_small), 0x100 = never split (porla_gpu_set_msm_glv(0));
+ *   form: PORLA_SMALL_FORM_LONE      one MSM on the lone call's blocks, the shape the kernel derives from used_bits;
+ *         PORLA_SMALL_FORM_PAIR      one point set of a pair on the pair's blocks, the shape the kernel derives from used_bits;
+ *         PORLA_SMALL_FORM_PAIR_HINT the same with used_bits (>= 1) passed as the caller's bound, as the audit's pairs pass 32;
+ *         PORLA_SMALL_FORM_PAIR_ANY  the pair as the host decides it with no bound: single-launch only if EVERY bit length 0 .. 256 fits
+ *                                    (used_bits is ignored; the shape reported is that of 256-bit scalars).
+ * out[6 i ..]: 1 = the shape fits and is launched / 0 = it does not fit (more windows than blocks, or a slice of more than 8 192
+ * sub-scalars) and is not launched, blocks, split flag, window bits c, windows W, slices per window S.  The kernels refuse exactly the shapes reported 0.
+ * A pair reported 0 -- secp256k1 only: above 28 672 pairs with scalars over 128 bits, above 24 576 with the split off and scalars of
+ * 250 bits and more -- runs as two MSMs, one after the other, each of them a lone single launch of its own on 256 blocks (lone shapes
+ * always fit).  PORLA_ERR_ARG for an element out of range; nothing is written then. */
+#define PORLA_SMALL_FORM_LONE      0
+#define PORLA_SMALL_FORM_PAIR      1
+#define PORLA_SMALL_FORM_PAIR_HINT 2
+#define PORLA_SMALL_FORM_PAIR_ANY  3
+int         porla_msm_small_shape(size_t count, const int32_t *curve, const uint32_t *n, const int32_t *used_bits,
+                                  const int32_t *c_flags, const int32_t *form, int32_t *out);
 /* diagnostic: HOST execution of the 8 x 32-bit field helpers the kernels are built from (borrow / carry chains, negation, the
  * bounded reduction of the ICC finish step), for the CPU test suite.  op 0: reduce a value below 5 x modulus (modulus 0 = BN254
  * group order) or below the modulus + 2^256 - n (modulus 1 = secp256k1 group order: one conditional subtraction) to its residue;
@@ -113,7 +132,8 @@ int porla_bn254_msm_device_partial(const void *d_scalars, const void *d_points, 
 /* The audit's pair: ONE scalar array over TWO point arrays -- replaces the two back-to-back calls
  *   bn254_multi_exp(combined_MAC, ptc, sc, n); bn254_multi_exp(combined_align, pta, sc, n);    (porla/Server/Server.hpp:900-901,
  *   and the secp256k1 twins secp256k1_ecmult_multi_var x2 at :842-848)
- * For n <= 32 768 both run in ONE kernel launch (half the chip each); above that they run one after the other.
+ * For n <= 32 768 both run in ONE kernel launch (half the chip each) where the shape fits the launch (porla_msm_small_shape; every
+ * BN254 size does, secp256k1 up to 28 672 pairs, 24 576 with the split off); otherwise they run one after the other, one lone single launch per point set.
  * out_a = sum scalars[i] * points_a[i], out_b = sum scalars[i] * points_b[i]; encodings as porla_bn254_msm_device. */
 int porla_bn254_msm_pair_device(const void *d_scalars, const void *d_points_a, const void *d_points_b, size_t n,
                                 uint8_t out_a[64], uint8_t out_b[64], void *hip_stream);

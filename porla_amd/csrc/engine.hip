@@ -277,6 +277,19 @@ struct IccSecp256k1FnHost {  // secp256k1 group order, only P is needed (fe_redu
 };
 }  // namespace
 
+// host execution of the single-launch MSM's shape function and of the launch decision built on it (msm_small.hip.h: small_cfg, small_fits,
+// small_decide -- the code the kernels and msm_pair_locked run): no device is touched
+template <class C>
+static void small_shape_one(uint32_t n, int used_bits, int c_flags, int form, int32_t* o) {
+    const int blocks = (int)(form == PORLA_SMALL_FORM_LONE ? small_lone_blocks(n) : small_pair_blocks(n));
+    SmallCfg g;
+    bool fits;
+    if (form == PORLA_SMALL_FORM_PAIR_ANY) fits = small_decide<C>(n, blocks, c_flags, 0, &g);
+    else if (form == PORLA_SMALL_FORM_PAIR_HINT) fits = small_decide<C>(n, blocks, c_flags, used_bits, &g);
+    else { g = small_cfg<C>(n, used_bits, c_flags, blocks); fits = small_fits(g, blocks); }
+    o[0] = fits ? 1 : 0; o[1] = blocks; o[2] = g.glv; o[3] = g.c; o[4] = g.W; o[5] = g.S;
+}
+
 extern "C" {
 
 int porla_gpu_device_count(void) {
@@ -356,6 +369,25 @@ int porla_gpu_set_msm_small(int on, int window_bits) {
     return PORLA_OK;
 }
 int porla_gpu_set_msm_glv(int on) { g_use_glv = on < 0 ? -1 : (on != 0); return PORLA_OK; }
+
+// the shape function and launch decision of the single-launch MSM on the host (small_shape_one above): no device is touched
+int porla_msm_small_shape(size_t count, const int32_t* curve, const uint32_t* n, const int32_t* used_bits, const int32_t* c_flags,
+                          const int32_t* form, int32_t* out) {
+    if (count && (!curve || !n || !used_bits || !c_flags || !form || !out)) { set_last_error("porla: small shape: null array"); return PORLA_ERR_ARG; }
+    for (size_t i = 0; i < count; i++) {                 // every element stands before any is answered
+        const bool hint = form[i] == PORLA_SMALL_FORM_PAIR_HINT;
+        if ((curve[i] != 0 && curve[i] != 1) || n[i] < 1 || n[i] > SMALL_MAX_N || used_bits[i] < (hint ? 1 : 0) || used_bits[i] > 256 ||
+            (c_flags[i] & ~0x1ff) || (c_flags[i] & 0xff) > SMALL_MAX_C || form[i] < PORLA_SMALL_FORM_LONE || form[i] > PORLA_SMALL_FORM_PAIR_ANY) {
+            set_last_error("porla: small shape: element " + std::to_string(i) + " is out of range");
+            return PORLA_ERR_ARG;
+        }
+    }
+    for (size_t i = 0; i < count; i++) {
+        if (curve[i] == 0) small_shape_one<Bn254G1>(n[i], used_bits[i], c_flags[i], form[i], out + 6 * i);
+        else small_shape_one<Secp256k1G>(n[i], used_bits[i], c_flags[i], form[i], out + 6 * i);
+    }
+    return PORLA_OK;
+}
 
 // host execution of the very code the digit kernel runs (glv.hip.h is __host__ __device__): lets the CPU tests pin the
 // split against the Python model of tools/gen_glv.py

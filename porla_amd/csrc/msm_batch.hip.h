@@ -154,7 +154,7 @@ k_batch_bucket(const uint8_t* __restrict__ scalars_r, const uint8_t* __restrict_
         scalars_r + (size_t)E.off * 32, points_r + (size_t)E.off * 64, E.n, bx, (int)E.blocks, c_flags, 0, part + (size_t)E.base * SMALL_MAX_C,
         counters + E.base, [&](const SmallCfg& g) {
             // (the host sizes every allotment so that neither bound is ever met: W <= blocks, a slice fits the LDS)
-            if (g.W > (int)E.blocks || (g.n_sub + (uint32_t)g.S - 1) / (uint32_t)g.S > SMALL_MAX_SUB) return false;
+            if (!small_fits(g, (int)E.blocks)) return false;
             if (bx == 0 && threadIdx.x == 0) shape[eidx] = (uint32_t)g.W | ((uint32_t)g.c << 8);
             return true;
         } SMALL_STAMP_PASS(nullptr));

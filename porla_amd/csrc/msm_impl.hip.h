@@ -86,7 +86,17 @@ static inline int choose_window(size_t m, int bits) {
 // bn254_multi_exp(combined_align, pta, sc, n), porla/Server/Server.hpp:900-901; the IPA twins :842-848) -- is one launch of it
 // (d_points_b non-null): half of the chip's blocks per point set.  Both are chains of ~15 dependent additions, so side by side
 // they take little longer than one alone.  Results: one region of the slot's pinned area per set, PAIR_STRIDE bytes apart.
-constexpr uint32_t SMALL_PAIR_STRIDE = 64 * 1024;
+// (SMALL_PAIR_STRIDE, small_pair_blocks: msm_small.hip.h)
+static inline int small_host_c_flags() { return g_small_c | (g_use_glv == 0 ? 0x100 : 0); }
+// Does the pair of n pairs take the single launch?  The switches, n <= SMALL_MAX_N -- and the shape must fit its 96 / 128 blocks per set
+// (msm_small.hip.h:small_decide; secp256k1 pairs above 28 672 pairs, 24 576 with the split off, do not unless a hint says the scalars
+// are short): a pair that does not goes through msm_core twice -- up to SMALL_MAX_N pairs that is one LONE single launch per point
+// set (msm_launch; 192 / 256 blocks, which every lone shape fits), above it the general path twice
+template <class C>
+static inline bool msm_pair_takes_small(size_t n, int bits_hint) {
+    if (n == 0 || n > SMALL_MAX_N || g_small_mode == 0 || g_window_override != 0) return false;
+    return small_decide<C>((uint32_t)n, (int)small_pair_blocks(n), small_host_c_flags(), bits_hint);
+}
 template <class C>
 static int msm_small_pair_launch(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_points_a, const uint8_t* d_points_b, size_t n,
                                  hipStream_t stream, int bits_hint = 0) {
@@ -115,9 +125,9 @@ static int msm_small_pair_launch(Workspace* ws, const uint8_t* d_scalars, const 
         // 128 each (0.120 against 0.124 ms at 3 200 pairs) and the audit's other chain, which runs beside this kernel (row combine, the
         // three commitments: short launches that need a compute unit NOW), no longer queues behind 256 long-lived blocks:
         // 0.183 -> 0.151 ms per audit
-        const unsigned blocks = d_points_b ? (n <= 8192 ? 96u : (unsigned)SMALL_BLOCKS / 2) : small_lone_blocks(n);
+        const unsigned blocks = d_points_b ? small_pair_blocks(n) : small_lone_blocks(n);
         hipLaunchKernelGGL((k_small_msm<C>), dim3(blocks, sets), dim3(SMALL_THREADS), 0, stream, d_scalars, d_points_a, (uint32_t)n,
-                           g_small_c | (g_use_glv == 0 ? 0x100 : 0) | (bits_hint << 16), (XYZZ<M>*)ws->small_part.p, counters,
+                           small_host_c_flags() | (bits_hint << 16), (XYZZ<M>*)ws->small_part.p, counters,
                            (uint32_t*)h_dev, (XYZZ<M>*)((uint8_t*)h_dev + SMALL_HDR_WORDS * 4), ws->small_seq, d_points_b, SMALL_PAIR_STRIDE);
     }
     PORLA_HIP(hipGetLastError());
@@ -448,15 +458,15 @@ int msm_device(const uint8_t* d_scalars, const uint8_t* d_points, size_t n, hipS
     ws->lone = true;
     return msm_core<C>(ws, d_scalars, d_points, n, stream, total);
 }
-// ONE scalar array over TWO point arrays (device pointers).  Up to SMALL_MAX_N pairs: one launch for both (msm_small_pair_launch);
-// above: the two MSMs through the general path, one after the other on this slot (callers that want them overlapped use the
-// two-phase form on two streams).
+// ONE scalar array over TWO point arrays (device pointers).  Up to SMALL_MAX_N pairs, where the shape fits the pair's blocks
+// (msm_pair_takes_small): one launch for both (msm_small_pair_launch); otherwise: the two MSMs through msm_core (a lone single launch each up to
+// SMALL_MAX_N pairs, the general path above), one after the other on this slot (callers that want them overlapped use the two-phase form on two streams).
 template <class C>
 static int msm_pair_locked(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_points_a, const uint8_t* d_points_b, size_t n,
                            hipStream_t stream, XYZZ<typename C::Fp>* total_a, XYZZ<typename C::Fp>* total_b, int bits_hint = 0) {
     int rc;
     ws->lone = true;
-    if (n <= SMALL_MAX_N && g_small_mode != 0 && g_window_override == 0) {
+    if (msm_pair_takes_small<C>(n, bits_hint)) {
         ws->pend_W = 0;
         if ((rc = msm_small_pair_launch<C>(ws, d_scalars, d_points_a, d_points_b, n, stream, bits_hint))) return rc;
         if ((rc = msm_small_pair_finish<C>(ws, 0, total_a))) return rc;
@@ -770,7 +780,7 @@ int msm_pair_gather_begin(int slot, const uint8_t* d_store_a, const uint8_t* d_s
                           hipStream_t stream) {
     int rc = ensure_device();
     if (rc) return rc;
-    if (n == 0 || n > SMALL_MAX_N || g_small_mode == 0 || g_window_override != 0) {
+    if (!msm_pair_takes_small<C>(n, 32)) {               // (32-bit coefficients fit at every n <= SMALL_MAX_N and every forced width)
         set_last_error("porla: the two-phase audit pair takes 1 .. 32768 challenged rows (single-launch path on)");
         return PORLA_ERR_ARG;
     }

@@ -47,6 +47,10 @@ constexpr uint32_t SMALL_HDR_WORDS = 32;             // pinned header in front o
 // coefficients, 0.163 / 0.171 with 256-bit scalars; 16 384 pairs: 0.284 against 0.262) and leave a quarter of the chip to whatever
 // short kernels run beside this one
 inline uint32_t small_lone_blocks(uint64_t n) { return n <= 4096 ? 192u : (uint32_t)SMALL_BLOCKS; }
+// blocks per point set of a pair (msm_impl.hip.h:msm_small_pair_launch, where the figures behind the 96 stand)
+inline uint32_t small_pair_blocks(uint64_t n) { return n <= 8192 ? 96u : (uint32_t)SMALL_BLOCKS / 2; }
+// a pair's result regions (header + window sums per point set) lie this many bytes apart in the slot's pinned area
+constexpr uint32_t SMALL_PAIR_STRIDE = 64 * 1024;
 
 // the single-launch commitment of fixed_base.hip.h (k_fb_commit_small): rows per launch, slices per row
 constexpr int FB_SMALL_MAX_ROWS = 64;            // 64 rows x 8 slices = 512 blocks, two per compute unit (96 rows: 0.19 ms, the batch kernels 0.22)
@@ -103,11 +107,42 @@ __host__ __device__ inline SmallCfg small_cfg(uint32_t n, int used_bits, int c_f
                            0.01f * (float)W;
         if (cost < best_cost) { best_cost = cost; best_c = c; g.c = c; g.W = W; g.S = (int)S; }
     }
-    if (best_c == 0) {                                   // no admissible shape (a forced width with more windows than blocks): c = 8 always fits (W <= 32)
+    if (best_c == 0) {
+        // no admissible width (a forced one with more windows than blocks, or slices too large at every width): the shape with the
+        // fewest windows (c = 8: W <= 33) and so the most slices.  It need NOT fit either -- small_fits says whether it does, and
+        // nothing runs a shape that does not
         g.c = SMALL_MAX_C; g.W = (g.L + 1 + g.c - 1) / g.c;
         g.S = blocks / g.W < 1 ? 1 : (blocks / g.W > SMALL_MAX_S ? SMALL_MAX_S : blocks / g.W);
     }
     return g;
+}
+
+// THE predicate of the single-launch block body: can `blocks` blocks run shape g?  Every window needs a block, and a slice must fit
+// the block's LDS arrays (ent[], raw[]) and the 13-bit local index.  The host asks before it launches (small_decide), k_small_msm and
+// k_batch_bucket ask again on the device (small_block's admit) and leave without a write when the answer is no.
+__host__ __device__ inline bool small_fits(const SmallCfg& g, int blocks) {
+    return g.W >= 1 && g.S >= 1 && g.W <= blocks && (g.n_sub + (uint32_t)g.S - 1) / (uint32_t)g.S <= SMALL_MAX_SUB;
+}
+
+// The host's decision for ONE MSM of n pairs on `blocks` blocks: true = the single launch can take it.  bits_hint > 0: the caller's
+// bound on the scalars' bit length, the shape is that of the hint (*shape, when asked for).  bits_hint == 0: the kernel will scan the
+// scalars, so the answer must hold for every bit length 0 .. 256 (*shape is then the shape of 256-bit scalars).
+// Two or three evaluations of small_cfg decide that: the shape depends on the bit length only through (split, L), and within one
+// split class a longer L never fits where a shorter one does not -- W grows with L, S = min(blocks / W, ..) shrinks with W, a slice
+// grows as S shrinks, and the shape taken is an admissible width if there is one, else the fallback, each of which obeys the same order.
+// So the longest L of each class speaks for the class: 128 bits unsplit and anything longer split, or, with the split off, 256 bits.
+template <class C>
+inline bool small_decide(uint32_t n, int blocks, int c_flags, int bits_hint, SmallCfg* shape = nullptr) {
+    if (bits_hint > 0) {
+        const SmallCfg g = small_cfg<C>(n, bits_hint, c_flags, blocks);
+        if (shape) *shape = g;
+        return small_fits(g, blocks);
+    }
+    const SmallCfg longest = small_cfg<C>(n, 256, c_flags, blocks);
+    if (shape) *shape = longest;
+    if (!small_fits(longest, blocks)) return false;
+    if (c_flags & 0x100) return true;
+    return small_fits(small_cfg<C>(n, 128, c_flags, blocks), blocks);
 }
 
 // `tasks` independent additions on the block's quads; get(t, &pa, &pb, &out) names the operands of task t (memory form)
@@ -460,7 +495,7 @@ k_small_msm(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ poi
     // bits 16..24 of c_override: the scalars' bit length when the caller knows it (the audit's coefficients are abs(int32), expanded
     // to 32-byte scalars by k_audit_gather: 32 bits, no scan -- ~10 us of a ~100 us kernel)
     const SmallWindow<M> win = small_block<C>(scalars, points, n, blockIdx.x, (int)gridDim.x, c_override, (c_override >> 16) & 0x1ff, part,
-                                              counters, [](const SmallCfg&) { return true; } SMALL_STAMP_PASS(stamps));
+                                              counters, [&](const SmallCfg& g) { return small_fits(g, (int)gridDim.x); } SMALL_STAMP_PASS(stamps));
     if (!win.sums) return;
     const uint32_t tid = threadIdx.x;
     const int c = win.g.c;

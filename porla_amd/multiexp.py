@@ -969,6 +969,28 @@ def last_msm_shape():
     return c.value, w.value, bool(g.value)
 
 
+SMALL_FORMS = {"lone": 0, "pair": 1, "hint": 2, "any": 3}
+
+
+def msm_small_shape(curve, n, used_bits, c_flags, form):
+    """porla_msm_small_shape on arrays of equal length (no device needed): curve 0 = BN254 / 1 = secp256k1, n, used_bits, c_flags (forced
+    window bits | 0x100 = never split), form (SMALL_FORMS).  Returns an int32 array of shape (count, 6): the shape fits and is launched (1) or not (0;
+    a pair then runs as two lone single launches), blocks, split flag, c, W, S."""
+    import numpy as np
+    arrs = [np.ascontiguousarray(a, dtype=t) for a, t in
+            zip((curve, n, used_bits, c_flags, form), (np.int32, np.uint32, np.int32, np.int32, np.int32))]
+    count = len(arrs[0])
+    if any(len(a) != count for a in arrs):
+        raise ValueError("msm_small_shape: arrays of unequal length")
+    out = np.zeros((count, 6), dtype=np.int32)
+    ptr = lambda a, t: a.ctypes.data_as(ctypes.POINTER(t))
+    rc = lib.porla_msm_small_shape(count, ptr(arrs[0], ctypes.c_int32), ptr(arrs[1], ctypes.c_uint32), ptr(arrs[2], ctypes.c_int32),
+                                   ptr(arrs[3], ctypes.c_int32), ptr(arrs[4], ctypes.c_int32), ptr(out, ctypes.c_int32))
+    if rc != 0:
+        raise RuntimeError("porla_msm_small_shape failed (%d): %s" % (rc, lib.porla_gpu_last_error().decode()))
+    return out
+
+
 def profile_get():
     """[(kernel name, total ms, launches)]"""
     res = []

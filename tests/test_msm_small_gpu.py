@@ -281,3 +281,55 @@ def test_audit_pair_two_phase_and_commit_to_host(mx, inputs):
         got = mx.kzg_commit_batch_device_to_host(d_rows.data_ptr(), rows, torch.cuda.current_stream().cuda_stream)
         for r in (0, rows - 1):
             assert got[64 * r:64 * r + 64] == mx.compute_digest_from_srs(data[4096 * r:4096 * r + 4096])
+
+
+# ---------------------------------------------------------------- the pair at the edge of what one launch can take
+@pytest.fixture(scope="module")
+def secp_large():
+    """32 768 full scalars over two point orders, and the oracle's pair per size (computed once, shared by the split-on and -off cases)"""
+    n = 32768
+    sc, pa = common.secp_bench_scalars(n), common.secp_bench_points(n)
+    pb = pa[64 * 77:] + pa[:64 * 77]
+    want = {}
+
+    def expected(k):
+        if k not in want:
+            want[k] = (common.oracle_secp_msm(sc, pa, k), common.oracle_secp_msm(sc, pb, k))
+        return want[k]
+    return sc, pa, pb, expected
+
+
+@pytest.mark.parametrize("n", [28672, 28673, 32768])
+def test_secp256k1_pair_full_scalars_around_the_single_launch_limit(mx, secp_large, n):
+    """split on: 28 672 pairs are the last that fit one launch (W = 17, S = 7: slices of exactly 8 192 sub-scalars); above, the pair
+    runs as two MSMs -- same 64 bytes either way"""
+    sc, pa, pb, expected = secp_large
+    assert mx.msm_pair_host("secp256k1", sc[:32 * n], pa[:64 * n], pb[:64 * n], n) == expected(n)
+    shape = mx.msm_small_shape([1], [n], [0], [0], [mx.SMALL_FORMS["any"]])[0]
+    assert shape[0] == (1 if n <= 28672 else 0)
+
+
+@pytest.mark.parametrize("n", [24576, 24577, 32768])
+def test_secp256k1_pair_full_scalars_split_off_around_the_single_launch_limit(mx, secp_large, n):
+    """porla_gpu_set_msm_glv(0): 24 576 pairs are the last that fit (slices of exactly 8 192 scalars)"""
+    from porla_amd import lib
+    sc, pa, pb, expected = secp_large
+    lib.porla_gpu_set_msm_glv(0)
+    try:
+        assert mx.msm_pair_host("secp256k1", sc[:32 * n], pa[:64 * n], pb[:64 * n], n) == expected(n)
+    finally:
+        lib.porla_gpu_set_msm_glv(-1)
+    shape = mx.msm_small_shape([1], [n], [0], [0x100], [mx.SMALL_FORMS["any"]])[0]
+    assert shape[0] == (1 if n <= 24576 else 0)
+
+
+def test_bn254_pair_at_32768_one_launch_with_full_slices(mx):
+    """BN254 at SMALL_MAX_N: W = 16, S = 8 on 128 blocks per set, slices of exactly 8 192 sub-scalars -- still one launch"""
+    n = 32768
+    sc, pt = common.synth_inputs(8192)
+    s, pa = sc * 4, pt * 4
+    pb = pa[64 * 100:] + pa[:64 * 100]
+    assert mx.msm_pair_host("bn254", s, pa, pb, n) == (common.oracle_msm(s, pa, n), common.oracle_msm(s, pb, n))
+    cc, W, glv = mx.last_msm_shape()
+    assert glv and W == (126 + 1 + cc - 1) // cc
+    assert mx.msm_small_shape([0], [n], [0], [0], [mx.SMALL_FORMS["any"]])[0][0] == 1
