@@ -1287,8 +1287,8 @@ int porla_ipa_extract_xy_batch_device(porla_fixed_base *alpha_generators_fb, por
  * top_y == 1 and a top level a NULL d_top_rows_y, d_top_macs_y, d_prf_top_y, d_top_patch or d_row_status_top_y; any of the six new
  * pointers not 16-byte aligned, wherever given; top_y above 1; a byte size that wraps; d_top_patch and d_row_status_top_y are outputs
  * in the overlap walk, the three Y inputs may be shared between requests.  k = 0, PORLA_ERR_STATE and PORLA_ERR_NO_DEVICE as above.
- * Not in this call: a host-memory form; n_total > 2^16; writing the repaired rows back into the server's store; a row damaged in
- * both halves.  tools/bench_extract_xyt.py times it (profiles/r26_a_extract_xyt.jsonl). */
+ * Not in this call: a host-memory form; n_total > 2^16; a row damaged in both halves.  Writing the repaired rows back into the
+ * server's store is porla_*_repair_top_batch_device below.  tools/bench_extract_xyt.py times it (profiles/r26_a_extract_xyt.jsonl). */
 #define PORLA_EXTRACT_XYT_REQ_BYTES 224   /* sizeof(porla_extract_xyt_req) on LP64; the library static_asserts it and each offset */
 typedef struct {
     unsigned long long  write_step;         /*   0: the fields of porla_extract_xy_req, at its offsets */
@@ -1325,6 +1325,74 @@ typedef struct {
 int porla_kzg_extract_xyt_batch_device(const porla_extract_xyt_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
 int porla_ipa_extract_xyt_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t alpha_be[32],
                                        const porla_extract_xyt_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
+
+/* ---- top-level repair: damaged rows of a top level written back, in place, from the other half ----
+ * The call above computes wt^-1 Y_j for every top-level X row that fails its check and leaves it in scratch; the store stays damaged,
+ * every later audit that draws the row fails, and a second hit on the same row index in the other half loses the level.  This call
+ * heals the store: one request is one file's top level, both halves with their MAC rows, alignment stores and PRF values;
+ * n_total is a power of two, 2 .. 2^16; top_form is PORLA_ICC_DECODE_EXACT or PORLA_ICC_DECODE_RESIDUE32 for the whole call; n_cols is
+ * the SRS size (KZG) or 128 (IPA).
+ *   1. Check.  Every row of both halves gets the status of porla_*_retrieve_aligned_batch_device on that half, byte for byte, in
+ *      top_form's symbol width with the half's alignment store and PRF values: d_status_x, d_status_y.  Both halves of all K files are
+ *      halves of ONE pass of the row check.  The statuses are the rows' BEFORE the repair.
+ *   2. Source.  Row j of a half is repairable iff its own status is 0 and row j of the other half is OK; lost iff both are 0; untouched
+ *      otherwise.
+ *   3. Data row.  e = reverse_bits(top_step % n_total, log2 n_total), wt = w^e.  The candidate for an X row is wt^-1 Y_j, rule 3t
+ *      above.  The candidate for a Y row is wt X_j: the p_icc plane by entry e of the encode's table of w^e mod p_icc, the q plane by
+ *      (w^e mod p_icc) mod q, entry e of the encode's q-plane table; in the exact form the two are joined below LCM as the encode's
+ *      finish joins them, in RESIDUE32 it is the p_icc plane alone.  With e == 0 the sibling row is copied as it lies.  Any 64 (32)
+ *      bytes of the sibling row are defined: they are reduced as the decode's load reduces them.  The candidate is written over the
+ *      row IN PLACE; PORLA_REPAIR_DATA is set iff the stored bytes differed from it.
+ *   4. MAC row.  For every repairable row the expected MAC is E_j - alpha A_j, E_j taken over the row AS REPAIRED, A_j the half's
+ *      alignment row as it lies; it is written over the row's MAC bytes as canonical affine bytes, and PORLA_REPAIR_MAC is set iff the
+ *      stored bytes differed.  A repairable row whose data bytes were intact therefore always gets MAC.
+ *   5. Lost rows get PORLA_REPAIR_LOST in both halves; not one byte of their data or MAC is written in either half.
+ *   6. Rows that are OK are never written.  Alignment stores and PRF values are never written.
+ *   7. d_counts, EIGHT words: [0] X rows with status 0, [1] Y rows with status 0, [2] X data rows rewritten, [3] X MAC rows rewritten,
+ *      [4] Y data rows rewritten, [5] Y MAC rows rewritten, [6] lost row indices, [7] always 0.
+ *   8. After the call every row of both halves that is not lost passes the aligned retrieval's check, and a second call on the same
+ *      stores writes nothing: its actions are 0 except LOST, its counts [2 .. 5] are 0.
+ * The authenticity of a repaired row rests on its sibling's check and on the linearity Y_j = wt X_j of the rebuild that wrote both
+ * halves: the candidate is a function of a row that passed its MAC check, and the MAC written is the one the client would have sent
+ * for it.  A damaged ALIGNMENT row is not restored: the row then fails its check with intact data, and the MAC written is the one
+ * that satisfies the relation with the alignment as stored.
+ * Launches: one upload, one clear, the row check, ONE patch kernel for both directions and all files (a lane per symbol, 16-byte
+ * accesses, plain vector stores), and one more pass of the check's expected-MAC stages over all rows of both halves whose last
+ * kernel writes the selected rows' MAC bytes instead of comparing.  The sequence does not depend on K, on which rows are damaged or
+ * on whether any are.  Contract: as the calls above -- asynchronous on hip_stream, no side stream, no host wait beyond the retrieval
+ * calls' first-use table upload, workspaces under their locks and fences.
+ * PORLA_ERR_ARG (with a message, before the device is touched): reqs NULL with k > 0; any of the four store pointers, the two PRF
+ * pointers, the two status pointers or the two action pointers NULL; a store, alignment or PRF pointer not 16-byte aligned; d_counts
+ * not 4-byte aligned; n_total out of range; a top_form that is neither of the two; reserved != 0; more than 65535 requests; a byte
+ * size that wraps; NULL alpha_be or bases (IPA); an overlap -- the four stores, the statuses, the actions and the counts are OUTPUTS
+ * in the overlap walk, so, unlike in the extraction, no two requests may share a store and a store may overlap no input of the call.
+ * k = 0 returns 0; KZG without key + SRS: PORLA_ERR_STATE; valid arguments without a device: PORLA_ERR_NO_DEVICE.
+ * Not in this call: the lower levels (their Y halves are no row-wise multiples of their X halves); restoring alignment stores; a row
+ * damaged in both halves; a host-memory form; n_total > 2^16.  tools/bench_repair_top.py times it. */
+#define PORLA_REPAIR_DATA 1   /* the row's data bytes were rewritten */
+#define PORLA_REPAIR_MAC  2   /* the row's MAC bytes were rewritten */
+#define PORLA_REPAIR_LOST 4   /* the row index is damaged in both halves: nothing was written */
+#define PORLA_REPAIR_TOP_REQ_BYTES 120   /* sizeof(porla_repair_top_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    void               *d_rows_x;    /*   0: the top X half, n_total rows in top_form.  Read AND WRITTEN */
+    void               *d_macs_x;    /*   8: its MAC rows, 64 bytes each.  Read and written */
+    const void         *d_align_x;   /*  16: its alignment store; NULL = every alignment at infinity.  Read only */
+    const void         *d_prf_x;     /*  24: 16 raw bytes per row, read as d_prf is read everywhere */
+    void               *d_rows_y;    /*  32: the top Y half, likewise */
+    void               *d_macs_y;    /*  40 */
+    const void         *d_align_y;   /*  48 */
+    const void         *d_prf_y;     /*  56 */
+    unsigned char      *d_status_x;  /*  64: n_total bytes: the row's status BEFORE the repair, PORLA_RETRIEVE_ROW_OK or 0 */
+    unsigned char      *d_status_y;  /*  72 */
+    unsigned char      *d_action_x;  /*  80: n_total bytes: what the call did to the row, PORLA_REPAIR_* bits */
+    unsigned char      *d_action_y;  /*  88 */
+    unsigned int       *d_counts;    /*  96: EIGHT words or NULL, zeroed by the call */
+    unsigned long long  top_step;    /* 104: the write step the rebuild that wrote the top level was given, as in porla_extract_xyt_req */
+    unsigned long long  reserved;    /* 112: must be 0; anything else is refused */
+} porla_repair_top_req;
+int porla_kzg_repair_top_batch_device(const porla_repair_top_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
+int porla_ipa_repair_top_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t alpha_be[32],
+                                      const porla_repair_top_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
 
 /* ---- AES on the device: the MAC PRF of the client writes, the audit challenge from its seed, the client's complement scalar ----
  * These calls PRODUCE the buffers the batches above consume (d_prf; d_idx* / d_coef* / d_mac_*; the 32-byte scalars of

@@ -322,6 +322,9 @@ int icc_mix_tables_release(hipStream_t stream);
 int icc_encode_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** twp, const uint32_t** twq);
 // ... and, for the decode (icc_decode.hip), with the q plane's inverse twiddles (want_q) instead of twq; the same release
 int icc_decode_tables_acquire(int curve, size_t n_total, bool want_q, hipStream_t stream, const uint32_t** twp, const uint32_t** twqi);
+// ... and with the encode's q-plane table beside its inverses (repair_batch.hip: wt in one direction, wt^-1 in the other)
+int icc_scale_tables_acquire(int curve, size_t n_total, bool want_q, hipStream_t stream, const uint32_t** twp, const uint32_t** twq,
+                             const uint32_t** twqi);
 int mac_mix_tables_acquire(int curve, size_t n_total, hipStream_t stream, const uint32_t** tws, int* quad_max_log);
 int mac_mix_tables_release(hipStream_t stream);
 // ... and, under that lease, the stages 1 .. log2 n_total of the MAC network over a work array of `points` projective points

@@ -263,7 +263,13 @@ static int ensure_qinv_twiddles(IccWs* ws, int curve, size_t n, hipStream_t stre
 }
 int icc_decode_tables_acquire(int curve, size_t n_total, bool want_q, hipStream_t stream, const uint32_t** twp, const uint32_t** twqi) {
     const uint32_t* twq = nullptr;
-    int rc = icc_encode_tables_acquire(curve, n_total, stream, twp, &twq);
+    return icc_scale_tables_acquire(curve, n_total, want_q, stream, twp, &twq, twqi);
+}
+// For repair_batch.hip: the same, and the encode's q-plane table handed out beside its inverses -- a row is scaled by wt in one
+// direction and by wt^-1 in the other
+int icc_scale_tables_acquire(int curve, size_t n_total, bool want_q, hipStream_t stream, const uint32_t** twp, const uint32_t** twq,
+                             const uint32_t** twqi) {
+    int rc = icc_encode_tables_acquire(curve, n_total, stream, twp, twq);
     if (rc) return rc;
     *twqi = nullptr;
     if (!want_q) return PORLA_OK;

@@ -192,12 +192,12 @@ static int rt_kzg_expected(const RtDesc* d_desc, const Map& map, size_t rows, si
 }
 
 // the aligned compare: its dynamic LDS is the quad ladder's, told once per device
-template <class C, bool ADD, class Map>
+template <class C, bool ADD, class Map, class Act>
 static void rt_compare_aligned_launch(const RtDesc* d_desc, const Map& map, size_t g0, size_t m, uint8_t* d_exp, const uint8_t* d_hpts,
                                       const MacScalar& alpha, hipStream_t stream) {
     static LdsOnce once;
-    once.set({lds_kernel(&k_rt_compare_aligned<C, ADD, Map>, macq_lds_bytes<C>())});
-    hipLaunchKernelGGL((k_rt_compare_aligned<C, ADD, Map>), dim3((unsigned)((m + RT_ALIGNED_ROWS - 1) / RT_ALIGNED_ROWS)), dim3(4 * MACQ_BF),
+    once.set({lds_kernel(&k_rt_compare_aligned<C, ADD, Map, Act>, macq_lds_bytes<C>())});
+    hipLaunchKernelGGL((k_rt_compare_aligned<C, ADD, Map, Act>), dim3((unsigned)((m + RT_ALIGNED_ROWS - 1) / RT_ALIGNED_ROWS)), dim3(4 * MACQ_BF),
                        macq_lds_bytes<C>(), stream, d_desc, map, (uint32_t)g0, (uint32_t)m, d_exp, d_hpts, alpha);
 }
 
@@ -222,7 +222,8 @@ static int rt_ensure(RetrieveWs* ws, size_t rows, size_t ncols) {
 
 // The check of the rows 0 .. rows - 1 of the requests at d_desc under `map`: expected MACs, then the compare -> status bytes, failures
 // counted.  ws->mu held, ws->fence entered, rt_ensure done.  alpha: the IPA build's, for the aligned compare (the KZG build reads its key)
-template <class C, class Map>
+// Act = RtActWrite: the same stages, and the last kernel writes the selected rows' MAC bytes instead of judging (the top-level repair)
+template <class C, class Map, class Act = RtActCompare>
 static int rt_check_rows(RetrieveWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* fb_h, MacScalar alpha, bool aligned, const RtDesc* d_desc,
                          const Map& map, size_t rows, size_t ncols, size_t symb, hipStream_t stream) {
     using Q = typename IccCurve<C>::Q;
@@ -250,11 +251,11 @@ static int rt_check_rows(RetrieveWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* f
             if ((rc = client_block_pass<C>(fb_alpha, (const uint8_t*)ws->coeffs.p, m, ncols, d_exp, stream))) return rc;
             if ((rc = client_h_pass<C>(fb_h, (const uint8_t*)ws->scalars.p, m, (uint8_t*)ws->hpts.p, stream))) return rc;
         }
-        ProfScope ps("retrieve_compare", stream);
+        ProfScope ps(std::is_same<Act, RtActCompare>::value ? "retrieve_compare" : "retrieve_write", stream);
         if (aligned)
-            rt_compare_aligned_launch<C, !kzg>(d_desc, map, g0, m, d_exp, (const uint8_t*)ws->hpts.p, alpha, stream);
+            rt_compare_aligned_launch<C, !kzg, Map, Act>(d_desc, map, g0, m, d_exp, (const uint8_t*)ws->hpts.p, alpha, stream);
         else
-            hipLaunchKernelGGL((k_rt_compare<C, !kzg, Map>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, stream, d_desc, map,
+            hipLaunchKernelGGL((k_rt_compare<C, !kzg, Map, Act>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, stream, d_desc, map,
                                (uint32_t)g0, (uint32_t)m, d_exp, (const uint8_t*)ws->hpts.p);
         PORLA_HIP(hipGetLastError());
     }
@@ -302,7 +303,7 @@ static int rt_enqueue(RetrieveWs* ws, FixedBase<C>* fb_alpha, FixedBase<C>* fb_h
 
 // The same check for halves of unequal sizes (the extraction, extract_batch.hip): the requests at d_desc, row numbering by `map`,
 // `rows` rows of `symb`-byte symbols; under this file's workspace, its lock and fence
-template <class C>
+template <class C, class Act = RtActCompare>
 static int rt_check_starts(FixedBase<C>* fb_alpha, FixedBase<C>* fb_h, const uint32_t* alpha_ipa, bool aligned, const RtDesc* d_desc,
                            const RtMapStarts& map, size_t rows, size_t ncols, size_t symb, hipStream_t stream) {
     RetrieveWs* ws = nullptr;
@@ -312,7 +313,7 @@ static int rt_check_starts(FixedBase<C>* fb_alpha, FixedBase<C>* fb_h, const uin
     if (alpha_ipa && aligned) memcpy(alpha.v, alpha_ipa, sizeof(alpha.v));
     return FencedCall(ws, stream).run([&] {
         if (int r = rt_ensure<C>(ws, rows, ncols)) return r;
-        return rt_check_rows<C>(ws, fb_alpha, fb_h, alpha, aligned, d_desc, map, rows, ncols, symb, stream);
+        return rt_check_rows<C, RtMapStarts, Act>(ws, fb_alpha, fb_h, alpha, aligned, d_desc, map, rows, ncols, symb, stream);
     });
 }
 int rt_check_starts_kzg(bool aligned, const RtDesc* d_desc, const RtMapStarts& map, size_t rows, size_t ncols, size_t symb, hipStream_t stream) {
@@ -321,6 +322,17 @@ int rt_check_starts_kzg(bool aligned, const RtDesc* d_desc, const RtMapStarts& m
 int rt_check_starts_ipa(porla_fixed_base* alpha_generators_fb, porla_fixed_base* h_fb, const uint32_t alpha[8], bool aligned, const RtDesc* d_desc,
                         const RtMapStarts& map, size_t rows, size_t symb, hipStream_t stream) {
     return rt_check_starts<Secp256k1G>(&alpha_generators_fb->secp, &h_fb->secp, alpha, aligned, d_desc, map, rows, IPA_COLS, symb, stream);
+}
+
+// The repair's second pass over the same halves (repair_batch.hip): the expected-MAC stages again, over the rows as they lie now, and
+// the last kernel writes (RtActWrite, retrieve_batch.hip.h: what the requests' members mean there)
+int rt_write_starts_kzg(bool aligned, const RtDesc* d_desc, const RtMapStarts& map, size_t rows, size_t ncols, size_t symb, hipStream_t stream) {
+    return rt_check_starts<Bn254G1, RtActWrite>(nullptr, nullptr, nullptr, aligned, d_desc, map, rows, ncols, symb, stream);
+}
+int rt_write_starts_ipa(porla_fixed_base* alpha_generators_fb, porla_fixed_base* h_fb, const uint32_t alpha[8], bool aligned, const RtDesc* d_desc,
+                        const RtMapStarts& map, size_t rows, size_t symb, hipStream_t stream) {
+    return rt_check_starts<Secp256k1G, RtActWrite>(&alpha_generators_fb->secp, &h_fb->secp, alpha, aligned, d_desc, map, rows, IPA_COLS, symb,
+                                                   stream);
 }
 
 // one level from host memory: upload, the batch of one request on the engine's stream, download; `run` enqueues that batch

@@ -244,8 +244,40 @@ __device__ __forceinline__ void rt_compare_bytes(const RtDesc& D, uint32_t jr, c
     D.status[jr] = diff ? 0 : PORLA_RETRIEVE_ROW_OK;
     if (diff && D.counts) atomicAdd(D.counts, 1u);
 }
+// What the last kernel of the check does with a row's 64 expected bytes, a template parameter of the compare kernels.  RtActCompare (the
+// default): judge -- rt_compare_bytes, the retrieval calls' and the extraction's instances.  RtActWrite: the top-level repair's second
+// pass (repair_batch.hip), whose requests read the members the check does not use another way:
+//   status   the half's row statuses as the check pass left them (read)
+//   steps    the OTHER half's row statuses, n bytes (read)
+//   out      the half's action bytes: the data bit is there already, this kernel adds the MAC bit
+//   counts   two words or nullptr: [0] the half's data rows rewritten, [1] its MAC rows rewritten
+// A row is written iff its own status is 0 and its sibling's is OK; the expected bytes go over the row's MAC bytes when they differ.
+struct RtActCompare {
+    static __device__ __forceinline__ void row(const RtDesc& D, uint32_t jr, const uint8_t* mine) { rt_compare_bytes(D, jr, mine); }
+};
+struct RtActWrite {
+    static __device__ __forceinline__ void row(const RtDesc& D, uint32_t jr, const uint8_t* mine) {
+        const uint8_t* other = reinterpret_cast<const uint8_t*>(D.steps);
+        if (D.status[jr] != 0 || other[jr] != PORLA_RETRIEVE_ROW_OK) return;
+        const uint4* e = reinterpret_cast<const uint4*>(mine);
+        uint4* m = reinterpret_cast<uint4*>(const_cast<uint8_t*>(D.macs) + 64 * (size_t)jr);
+        const uint4 e0 = e[0], e1 = e[1], e2 = e[2], e3 = e[3], m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3];
+        const uint32_t diff = (e0.x ^ m0.x) | (e0.y ^ m0.y) | (e0.z ^ m0.z) | (e0.w ^ m0.w) | (e1.x ^ m1.x) | (e1.y ^ m1.y) | (e1.z ^ m1.z) |
+                              (e1.w ^ m1.w) | (e2.x ^ m2.x) | (e2.y ^ m2.y) | (e2.z ^ m2.z) | (e2.w ^ m2.w) | (e3.x ^ m3.x) | (e3.y ^ m3.y) |
+                              (e3.z ^ m3.z) | (e3.w ^ m3.w);
+        const uint8_t data = D.out[jr];
+        if (diff) {
+            m[0] = e0; m[1] = e1; m[2] = e2; m[3] = e3;
+            D.out[jr] = (uint8_t)(data | PORLA_REPAIR_MAC);
+        }
+        if (D.counts) {
+            if (data & PORLA_REPAIR_DATA) atomicAdd(D.counts, 1u);
+            if (diff) atomicAdd(D.counts + 1, 1u);
+        }
+    }
+};
 // row g0 + gl on the calling lane
-template <class C, bool ADD, class Map>
+template <class C, bool ADD, class Map, class Act = RtActCompare>
 __device__ __forceinline__ void rt_compare_row(const RtDesc* __restrict__ desc, const Map map, uint32_t g0, uint32_t gl,
                                                uint8_t* __restrict__ exp, const uint8_t* __restrict__ hpts) {
     using M = typename C::Fp;
@@ -258,15 +290,15 @@ __device__ __forceinline__ void rt_compare_row(const RtDesc* __restrict__ desc, 
         xyzz30_add_mem<M>(&a, &b, 0, 0, nullptr);
         store_affine_be<M>(mine, xyzz30_to_xyzz<M>(xyzz30_load_lazy<M>(&a)));
     }
-    rt_compare_bytes(D, jr, mine);
+    Act::row(D, jr, mine);
 }
-template <class C, bool ADD, class Map = RtMapShift>
+template <class C, bool ADD, class Map = RtMapShift, class Act = RtActCompare>
 __global__ void __launch_bounds__(64)
 k_rt_compare(const RtDesc* __restrict__ desc, const Map map, uint32_t g0, uint32_t rows, uint8_t* __restrict__ exp,
              const uint8_t* __restrict__ hpts) {
     const size_t gl64 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gl64 >= rows) return;
-    rt_compare_row<C, ADD>(desc, map, g0, (uint32_t)gl64, exp, hpts);
+    rt_compare_row<C, ADD, Map, Act>(desc, map, g0, (uint32_t)gl64, exp, hpts);
 }
 
 // ---- the aligned compare: a QUAD per row, RT_ALIGNED_ROWS = MACQ_BF rows per block of 256 lanes.  The stored MAC row must equal
@@ -274,7 +306,8 @@ k_rt_compare(const RtDesc* __restrict__ desc, const Map map, uint32_t g0, uint32
 // load_affine_be_lazy: coordinates reduced, 64 zero bytes = infinity, not checked to be on the curve -- into its table slot, alpha A_j
 // is the wave-uniform ladder (macq_ladder_uniform: alpha is the launch's one scalar), and um + (-(alpha A_j)) goes through the quad
 // kernels' out path (macq_sum_out: tm at infinity, um at infinity, equal and opposite points through macq_add's general addition).
-// Lane 0 of the quad converts to canonical affine bytes in place of the row's expected bytes and compares as k_rt_compare does.
+// Lane 0 of the quad converts to canonical affine bytes in place of the row's expected bytes and compares as k_rt_compare does (Act:
+// or writes, RtActWrite above).
 // The skip: a block none of whose rows has a nonzero byte in its alignment row (a request without d_align; an X half; a cached top
 // level) pays for no ladder -- its first wave runs k_rt_compare's body, a lane per row, and the other three leave.  The decision is
 // the block's (__syncthreads_or), so no wave with live quads diverges into the ladder; inside a block that runs it, a quad whose A_j
@@ -282,7 +315,7 @@ k_rt_compare(const RtDesc* __restrict__ desc, const Map map, uint32_t g0, uint32
 // ladder's path and gets the same answer there.)  Padding quads (rows beyond the last) hold infinity on both sides -- row 0's expected
 // bytes may be in the middle of being rewritten by that row's own quad -- so they leave the ladder at once, and store nothing.
 constexpr int RT_ALIGNED_ROWS = MACQ_BF;
-template <class C, bool ADD, class Map = RtMapShift>
+template <class C, bool ADD, class Map = RtMapShift, class Act = RtActCompare>
 __global__ void __launch_bounds__(4 * MACQ_BF) MACQ_GUEST_ATTR
 k_rt_compare_aligned(const RtDesc* __restrict__ desc, const Map map, uint32_t g0, uint32_t rows, uint8_t* __restrict__ exp,
                      const uint8_t* __restrict__ hpts, MacScalar alpha) {
@@ -302,7 +335,7 @@ k_rt_compare_aligned(const RtDesc* __restrict__ desc, const Map map, uint32_t g0
     }
     if (!__syncthreads_or(finite)) {
         const size_t mine64 = (size_t)blockIdx.x * MACQ_BF + threadIdx.x;
-        if (threadIdx.x < (uint32_t)MACQ_BF && mine64 < rows) rt_compare_row<C, ADD>(desc, map, g0, (uint32_t)mine64, exp, hpts);
+        if (threadIdx.x < (uint32_t)MACQ_BF && mine64 < rows) rt_compare_row<C, ADD, Map, Act>(desc, map, g0, (uint32_t)mine64, exp, hpts);
         return;
     }
     uint8_t* mine = exp + 64 * (size_t)gl;
@@ -329,7 +362,7 @@ k_rt_compare_aligned(const RtDesc* __restrict__ desc, const Map map, uint32_t g0
     macq_sync();
     if (valid && r == 0u) {
         store_affine_be<M>(mine, xyzz30_to_xyzz<M>(xyzz30_load_lazy<M>(&L.qd[q].tbl[1])));
-        rt_compare_bytes(D, jr, mine);
+        Act::row(D, jr, mine);
     }
 }
 

@@ -182,6 +182,21 @@ PORLA_EXTRACT_XYT_REQ_BYTES = 224
 assert ctypes.sizeof(ExtractXytReq) == PORLA_EXTRACT_XYT_REQ_BYTES
 
 
+class RepairTopReq(ctypes.Structure):
+    """porla_repair_top_req, include/porla_gpu.h: one file's top level of porla_kzg_repair_top_batch_device /
+    porla_ipa_repair_top_batch_device (PORLA_REPAIR_TOP_REQ_BYTES = 120).  The four stores are read AND written."""
+    _fields_ = [("d_rows_x", ctypes.c_void_p), ("d_macs_x", ctypes.c_void_p), ("d_align_x", ctypes.c_void_p), ("d_prf_x", ctypes.c_void_p),
+                ("d_rows_y", ctypes.c_void_p), ("d_macs_y", ctypes.c_void_p), ("d_align_y", ctypes.c_void_p), ("d_prf_y", ctypes.c_void_p),
+                ("d_status_x", ctypes.c_void_p), ("d_status_y", ctypes.c_void_p), ("d_action_x", ctypes.c_void_p),
+                ("d_action_y", ctypes.c_void_p), ("d_counts", ctypes.c_void_p), ("top_step", ctypes.c_ulonglong),
+                ("reserved", ctypes.c_ulonglong)]
+
+
+PORLA_REPAIR_TOP_REQ_BYTES = 120
+PORLA_REPAIR_DATA, PORLA_REPAIR_MAC, PORLA_REPAIR_LOST = 1, 2, 4
+assert ctypes.sizeof(RepairTopReq) == PORLA_REPAIR_TOP_REQ_BYTES
+
+
 class PrfRun(ctypes.Structure):
     """porla_prf_run, include/porla_gpu.h: count triples (level, index0 + t, time0 + t * time_stride) of the MAC PRF
     (PORLA_PRF_RUN_BYTES = 32)."""
@@ -395,6 +410,10 @@ def _declare(L):
     L.porla_kzg_extract_xyt_batch_device.restype = ctypes.c_int
     L.porla_ipa_extract_xyt_batch_device.argtypes = [vp, vp, u8p, ctypes.POINTER(ExtractXytReq), sz, sz, ctypes.c_int, vp]
     L.porla_ipa_extract_xyt_batch_device.restype = ctypes.c_int
+    L.porla_kzg_repair_top_batch_device.argtypes = [ctypes.POINTER(RepairTopReq), sz, sz, ctypes.c_int, vp]
+    L.porla_kzg_repair_top_batch_device.restype = ctypes.c_int
+    L.porla_ipa_repair_top_batch_device.argtypes = [vp, vp, u8p, ctypes.POINTER(RepairTopReq), sz, sz, ctypes.c_int, vp]
+    L.porla_ipa_repair_top_batch_device.restype = ctypes.c_int
     L.porla_kzg_retrieve_aligned_host.argtypes = [u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp, ctypes.POINTER(ctypes.c_uint)]
     L.porla_kzg_retrieve_aligned_host.restype = ctypes.c_int
     L.porla_ipa_retrieve_aligned_host.argtypes = [vp, vp, u8p, u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp,

@@ -529,6 +529,27 @@ def kzg_extract_xyt_batch_device(reqs, n_total, top_form, stream=0):
     del keep
 
 
+def repair_top_requests(reqs):
+    """a ctypes array of porla_repair_top_req from per-file tuples (d_rows_x, d_macs_x, d_align_x, d_prf_x, d_rows_y, d_macs_y, d_align_y,
+    d_prf_y, d_status_x, d_status_y, d_action_x, d_action_y, d_counts -- device addresses or 0 -- top_step[, reserved])"""
+    from .loader import RepairTopReq
+    arr = (RepairTopReq * max(len(reqs), 1))()
+    for i, r in enumerate(reqs):
+        if len(r) not in (14, 15):
+            raise ValueError("repair_top_batch_device: request %d has %d fields, want 14 or 15" % (i, len(r)))
+        arr[i] = RepairTopReq(*([v or None for v in r[:13]] + [r[13], r[14] if len(r) == 15 else 0]))
+    return arr
+
+
+def kzg_repair_top_batch_device(reqs, n_total, top_form, stream=0):
+    """the top-level repair (porla_kzg_repair_top_batch_device): every row of both halves of a file's top level is checked, and a row
+    that fails while row j of the other half passes is written back IN PLACE -- wt^-1 Y_j over an X row, wt X_j over a Y row, then its
+    MAC row.  d_status_*: the statuses before the repair; d_action_*: PORLA_REPAIR_DATA | _MAC | _LOST per row; d_counts: eight words.
+    Asynchronous on `stream`.  `reqs`: tuples as repair_top_requests takes them."""
+    arr = repair_top_requests(reqs)
+    _check(lib.porla_kzg_repair_top_batch_device(arr, len(reqs), n_total, RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
+
+
 def kzg_retrieve_aligned_host(rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None, want_blocks=True):
     """one level from host memory (porla_kzg_retrieve_aligned_host; it waits) -> what kzg_retrieve_host returns"""
     n_cols = kzg_row_coefficients()
@@ -660,6 +681,13 @@ class FixedBase:
         _check(lib.porla_ipa_extract_xyt_batch_device(self.h, h_fb.h if h_fb is not None else None, _alpha_be(alpha), arr, len(reqs), n_total,
                                                       RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
         del keep
+
+    def ipa_repair_top_batch_device(self, h_fb, alpha, reqs, n_total, top_form, stream=0):
+        """kzg_repair_top_batch_device for the IPA build (porla_ipa_repair_top_batch_device: 128 columns); self, h_fb and alpha as for
+        ipa_extract_batch_device."""
+        arr = repair_top_requests(reqs)
+        _check(lib.porla_ipa_repair_top_batch_device(self.h, h_fb.h if h_fb is not None else None, _alpha_be(alpha), arr, len(reqs), n_total,
+                                                     RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
 
     def ipa_retrieve_aligned_host(self, h_fb, alpha, rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None,
                                   want_blocks=True):
