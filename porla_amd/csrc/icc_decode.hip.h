@@ -52,6 +52,9 @@ enum IcdSrc { ICD_WORK = 0, ICD_ROWS64 = 1, ICD_ROWS32 = 2, ICD_LDS = 3 };
 
 // the q plane's inverse twiddles: entry e = ((w^e mod p_icc) mod q)^-1 in the 2^270 form, 40-byte slots like tw30q.  tw: the
 // twiddle table of icc.hip.h (2^256 Montgomery form).  The division steps vote across the wave, so no lane leaves early.
+// The raw inverse is v^-1 plus a multiple of q that depends on the rounds the lane's WAVE ran (inv30.hip.h), so a slot of twqi is a
+// representative of its residue below q + 2^250, not canonical bytes: the same entry may hold another representative in a table
+// of another size or launch shape.  The butterflies take any representative in that range.
 template <class Q>
 __global__ void __launch_bounds__(256)
 k_icd_twiddles_qinv(const IccElem<Q>* __restrict__ tw, uint32_t n, uint32_t* __restrict__ twqi) {

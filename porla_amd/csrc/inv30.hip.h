@@ -1,6 +1,8 @@
 // Modular inversion on the device by division steps (used by the finish kernels: fixed_base.hip.h:k_fb_finish,
 // mac_fft.hip.h:k_mac_finish / store_affine_be).  Checked directly by tools/fe30_check.hip (a * a^-1 over edge and random residues,
-// both base fields) and modelled on Python integers, register ranges asserted, by tools/safegcd_model.py.
+// both base fields) and modelled on Python integers, register ranges asserted, by tools/safegcd_model.py.  tools/inv_check.hip /
+// tests/test_inv_gpu.py compare the raw limbs of all four moduli word for word with that model run for the wave's round count
+// (tests/inv_vectors.py): inputs at and above the modulus, partial waves, waves that mix fast and slow inputs.
 #pragma once
 #include "fe.hip.h"
 #include "fe30.hip.h"
@@ -35,8 +37,12 @@ __device__ __noinline__ F30<M> f30_inv_safegcd_raw(Fe<M> a) {
 #pragma unroll 1
     for (int round = 0; round < 25; round++) {
         // once g = 0 a round changes nothing that matters: its matrix is [[2^30, 0], [0, 1]], so f stays and d stays modulo p (a
-        // negative d becomes d + p) -- the wave leaves as soon as every lane is there (~20 rounds for random inputs, not 25); the
-        // result bytes are those of the full 25 rounds
+        // negative d becomes d + p) -- the wave leaves as soon as every lane that runs the call is there: 18 or 19 rounds for
+        // random inputs (17 for about one in 200), not 25; no input is done before round 9, so the vote alone decides.  The
+        // integer this function returns therefore DEPENDS on the rounds its wave runs: by a multiple of p (-2 p .. +1 p between
+        // a lane's own exit and later rounds), always inside (0, 4 p) and right modulo p.  Only fe_inv_safegcd's bytes, behind
+        // its product and canonical form, are those of the full 25 rounds whatever the neighbours hold
+        // (tests/test_inv_gpu.py: the raw limbs against tests/inv_vectors.py:raw_limbs at the wave's round count)
         if (round >= 8) {
             int32_t nz = g[0];
 #pragma unroll
