@@ -1367,7 +1367,8 @@ int porla_ipa_extract_xyt_batch_device(porla_fixed_base *alpha_generators_fb, po
  * size that wraps; NULL alpha_be or bases (IPA); an overlap -- the four stores, the statuses, the actions and the counts are OUTPUTS
  * in the overlap walk, so, unlike in the extraction, no two requests may share a store and a store may overlap no input of the call.
  * k = 0 returns 0; KZG without key + SRS: PORLA_ERR_STATE; valid arguments without a device: PORLA_ERR_NO_DEVICE.
- * Not in this call: the lower levels (their Y halves are no row-wise multiples of their X halves); restoring alignment stores; a row
+ * Not in this call: the lower levels (their Y halves are no row-wise multiples of their X halves: porla_*_repair_levels_batch_device
+ * below rebuilds a whole Y half from its X half); restoring alignment stores; a row
  * damaged in both halves; a host-memory form; n_total > 2^16.  tools/bench_repair_top.py times it. */
 #define PORLA_REPAIR_DATA 1   /* the row's data bytes were rewritten */
 #define PORLA_REPAIR_MAC  2   /* the row's MAC bytes were rewritten */
@@ -1393,6 +1394,106 @@ typedef struct {
 int porla_kzg_repair_top_batch_device(const porla_repair_top_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
 int porla_ipa_repair_top_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t alpha_be[32],
                                       const porla_repair_top_req *reqs, size_t k, size_t n_total, int top_form, void *hip_stream);
+
+/* ---- lower-level repair: the damaged rows of a lower level's Y half written back, in place, from the level's X half ----
+ * porla_*_extract_xy_batch_device reports a damaged Y row of a lower level (d_counts[4], d_row_status_y) and heals nothing: every
+ * later audit that draws the row fails, and a second hit on the X half of the same level then loses up to 2^i blocks, of which a
+ * clean Y half would have kept the residues mod p_icc only.  Row by row the two halves share nothing, every block having been scaled
+ * by its own wt; but the WHOLE Y half is an exact function of the whole X half, byte for byte (tests/test_repair_levels_cpu.py):
+ *   data rows       the resident X half of level i is the one-shot data network (porla_icc_encode_device) over the chunks of its
+ *                   epoch's 2^i blocks in write order, the resident Y half the same network over the rows y_p = chunk_p * wt_p mod
+ *                   p_icc, wt_p = w^reverse_bits(step_p % n_total, log2 n_total), step_p rule 3y's "entry p of level i"; level 0's
+ *                   one row is the input row itself, zero-extended.  So Y half = Encode(HAdd_y(DecodeExact(X half))).
+ *   alignment rows  row j of the Y alignment store is the point network over Commit(c_p), c_p = (y_p - chunk_p * wt_p) mod q.  A
+ *                   point butterfly multiplies by the integer v^i mod p_icc and so does the data network's q plane: by linearity
+ *                   row j = Commit(N_j mod q), N the data network over the rows c_p.  No group-element network runs.
+ * One request is one file's lower levels as porla_update_req lays them out; t = write_step % n_total decides residency as in the
+ * extraction, and only the levels of levels & t are NAMED.  The mask is the caller's for the reason y_levels is: the launch shapes
+ * are fixed on the host.  n_total is a power of two, 2 .. 2^16; n_cols is the SRS size (KZG) or 128 (IPA).
+ *   1. Check.  Every row of the X half and of the Y half of every named level gets the status of
+ *      porla_*_retrieve_aligned_batch_device, byte for byte: the X halves as PORLA_ICC_DECODE_EXACT without an alignment store, the Y
+ *      halves as PORLA_ICC_DECODE_RESIDUE64 with align_y; level 0's rows are included.  All halves of all files are halves of ONE
+ *      pass of the row check.  d_status_x, d_status_y hold the statuses BEFORE the repair, laid out like d_row_status_y of
+ *      porla_extract_xy_req; the rows of unnamed levels get PORLA_EXTRACT_ROW_NOT_TRIED.
+ *   2. Verdict per named level, d_level[i], in this order: PORLA_REPAIR_LEVEL_CLEAN -- no row of either half failed;
+ *      PORLA_REPAIR_LEVEL_X_DAMAGED -- some X row failed: nothing of the level is written, its Y rows included; otherwise the level
+ *      is UNDER REPAIR and ends as INCONSISTENT (rule 4) or REPAIRED (rule 5).  d_level[i] of a level that is not named is 0.
+ *   3. Candidates of a level under repair: the exact decode of the X half (the ragged decode's body; level 0's row as it lies, a
+ *      symbol with a nonzero upper half counted as bad); per block y_p and c_p with the block's own wt; the data network over the rows
+ *      y_p on both planes, joined below LCM: the candidate data rows; the network over the rows c_p on the q plane, then one
+ *      commitment per row against the resident SRS (KZG) or the generators (IPA): the candidate alignment rows as canonical affine
+ *      bytes, a row of zero scalars giving 64 zero bytes.  The IPA call is handed the ALPHA generators only: it scales the rows c_p by
+ *      alpha^-1 mod q before the network, which is linear, so the commitment is the one against the generators; alpha = 0 mod q is
+ *      refused.
+ *   4. Witnesses.  A level under repair is PORLA_REPAIR_LEVEL_INCONSISTENT if any Y row with status OK holds data bytes or alignment
+ *      bytes that differ from its candidate, or if the X decode counts a bad symbol.  Such a level is not written at all; the differing
+ *      rows are counted in d_counts[7].  Two halves that each pass their checks and disagree mean that write_step or the stores do not
+ *      belong together, and writing then would destroy an authentic copy.  A level ALL of whose Y rows failed has no witness and is
+ *      repaired: what is written there rests on the X half's row check and on the write steps the caller gave alone.
+ *   5. Write, for a level under repair that is not inconsistent (PORLA_REPAIR_LEVEL_REPAIRED), on each FAILED Y row only: the data
+ *      bytes that differ from the candidate are overwritten and PORLA_REPAIR_DATA is set; the alignment bytes likewise,
+ *      PORLA_REPAIR_ALIGN; then the expected MAC E_j - alpha A_j over the row and the alignment as they now lie is written where the
+ *      stored bytes differ, PORLA_REPAIR_MAC -- the top-level repair's write pass, a per-row permit in the place of the sibling's
+ *      statuses.  Rows that checked OK, the X stores and the PRF values are never written.
+ *   6. d_counts, EIGHT words: [0] X rows with status 0, [1] Y rows with status 0, [2] Y data rows rewritten, [3] Y alignment rows
+ *      rewritten, [4] Y MAC rows rewritten, [5] levels repaired, [6] levels left X_DAMAGED or INCONSISTENT, [7] witness rows that
+ *      differ.
+ *   7. After the call every Y row of a REPAIRED level passes the aligned retrieval's check, its data, alignment and MAC bytes are
+ *      those the update batch wrote before the damage, and a second call reports the level CLEAN and writes nothing.
+ * d_work: porla_repair_levels_work_bytes(n_total, n_cols, write_step, levels) bytes of scratch, 16-byte aligned: 200 * n_cols * m
+ * with m = levels & (write_step % n_total), the number of named rows -- per named row and column 32 bytes of decoded chunk (then
+ * y_p), 32 of c_p, 64 of candidate symbol and 72 of residue planes between two passes.  0 for an n_total out of range or a size that
+ * overflows.  The function touches no device.
+ * Launches: one upload, one fill of the rows of alignment scalars with zeros, the clear, the row check, the plan, ONE ragged exact
+ * decode over the named X halves of two rows and more, the per-block HAdd, then per level SIZE named in the call (two rows and more)
+ * the passes of the data network over the rows y_p and over the rows c_p, the named level in blockIdx.y; ONE commitment pass over all
+ * named rows and the kernel that makes its sums affine; the compare, the write, the write pass of the row check over the Y halves,
+ * and the tally of actions, counters and verdicts.  The sequence depends on which level sizes are named in the call, never on K, on
+ * which rows are damaged or on whether any are.  The per-level flag: the HAdd, the data passes, the compare and the write leave at
+ * once for a level that is not under repair (a work-group reads the level's state word the plan set); the row check, the X decode,
+ * the commitment pass (over rows of zero scalars for such a level) and the write pass run over ALL named rows.
+ * Contract: as the calls above -- asynchronous on hip_stream, no side stream, no host wait beyond the retrieval calls' first-use table
+ * upload, workspaces under their locks and fences.
+ * PORLA_ERR_ARG (with a message, before the device is touched): reqs NULL with k > 0; n_total out of range; more than 65535
+ * requests; reserved != 0; a byte size that wraps; more than 2^18 named rows in the call (the workspace of alignment scalars stops
+ * there); with t > 0 a NULL d_status_x, d_status_y or d_action_y; a NULL d_level; with named levels a NULL data_x, mac_x, data_y, mac_y
+ * or align_y (the arrays), d_prf_x, d_prf_y or d_work, and a named level with a NULL entry in any of the five families (align_y
+ * included: the call may write it); a level pointer, d_prf_x, d_prf_y or d_work not 16-byte aligned, d_counts not 4-byte aligned; NULL
+ * alpha_be or bases, alpha = 0 mod q (IPA); an overlap -- the Y stores, the statuses, the actions, the verdicts, the counts and d_work
+ * are OUTPUTS in the overlap walk, the X stores and PRF values inputs that may be shared.  k = 0 returns 0; KZG without key + SRS:
+ * PORLA_ERR_STATE; valid arguments without a device: PORLA_ERR_NO_DEVICE.
+ * Not in this call: healing an X half (a clean Y half gives the chunks mod p_icc only, an X row is a value mod LCM); the top level
+ * (porla_*_repair_top_batch_device above); a ragged forward network (one group of data-pass launches per level size instead); a
+ * host-memory form; n_total > 2^16.  tools/bench_repair_levels.py times it. */
+#define PORLA_REPAIR_ALIGN 8   /* d_action_y: the row's alignment bytes were rewritten (beside PORLA_REPAIR_DATA and PORLA_REPAIR_MAC) */
+#define PORLA_REPAIR_LEVEL_CLEAN        1   /* d_level: no row of either half failed */
+#define PORLA_REPAIR_LEVEL_X_DAMAGED    2   /* an X row failed: nothing of the level was written */
+#define PORLA_REPAIR_LEVEL_INCONSISTENT 3   /* the halves pass their checks and disagree, or the X decode met a bad symbol: nothing written */
+#define PORLA_REPAIR_LEVEL_REPAIRED     4   /* every failed Y row was written back */
+#define PORLA_REPAIR_LEVELS_REQ_BYTES 128   /* sizeof(porla_repair_levels_req) on LP64; the library static_asserts it and each offset */
+typedef struct {
+    unsigned long long  write_step;  /*   0: the server's counter; t = write_step % n_total */
+    unsigned long long  levels;      /*   8: bit i = check and repair level i; only the bits of levels & t count */
+    void *const        *data_x;      /*  16: HOST array of log2(n_total) DEVICE pointers, as in porla_extract_req: the X data stores.  Read only */
+    void *const        *mac_x;       /*  24: the X MAC stores.  Read only */
+    const void         *d_prf_x;     /*  32: 16 raw bytes per lower-level row, laid out like the lower-level part of d_prf in
+                                             porla_extract_xy_req (t entries); only the entries of named levels are read */
+    const void         *d_prf_y;     /*  40: the same for the Y halves */
+    void *const        *data_y;      /*  48: the Y data stores.  Read AND WRITTEN */
+    void *const        *mac_y;       /*  56: the Y MAC stores.  Read and written */
+    void *const        *align_y;     /*  64: the Y alignment stores.  Read and written; a named level's entry must not be NULL */
+    void               *d_work;      /*  72: porla_repair_levels_work_bytes(...) bytes of scratch */
+    unsigned char      *d_status_x;  /*  80: t bytes: the row's status BEFORE the repair, or PORLA_EXTRACT_ROW_NOT_TRIED */
+    unsigned char      *d_status_y;  /*  88 */
+    unsigned char      *d_action_y;  /*  96: t bytes: what the call did to the Y row, PORLA_REPAIR_DATA | _MAC | _ALIGN */
+    unsigned char      *d_level;     /* 104: 16 bytes: level i's verdict, PORLA_REPAIR_LEVEL_*, 0 = not named */
+    unsigned int       *d_counts;    /* 112: EIGHT words or NULL, zeroed by the call */
+    unsigned long long  reserved;    /* 120: must be 0; anything else is refused */
+} porla_repair_levels_req;
+size_t porla_repair_levels_work_bytes(size_t n_total, size_t n_cols, unsigned long long write_step, unsigned long long levels);
+int porla_kzg_repair_levels_batch_device(const porla_repair_levels_req *reqs, size_t k, size_t n_total, void *hip_stream);
+int porla_ipa_repair_levels_batch_device(porla_fixed_base *alpha_generators_fb, porla_fixed_base *h_fb, const uint8_t alpha_be[32],
+                                         const porla_repair_levels_req *reqs, size_t k, size_t n_total, void *hip_stream);
 
 /* ---- AES on the device: the MAC PRF of the client writes, the audit challenge from its seed, the client's complement scalar ----
  * These calls PRODUCE the buffers the batches above consume (d_prf; d_idx* / d_coef* / d_mac_*; the 32-byte scalars of

@@ -197,6 +197,22 @@ PORLA_REPAIR_DATA, PORLA_REPAIR_MAC, PORLA_REPAIR_LOST = 1, 2, 4
 assert ctypes.sizeof(RepairTopReq) == PORLA_REPAIR_TOP_REQ_BYTES
 
 
+class RepairLevelsReq(ctypes.Structure):
+    """porla_repair_levels_req, include/porla_gpu.h: one file's lower levels of porla_kzg_repair_levels_batch_device /
+    porla_ipa_repair_levels_batch_device (PORLA_REPAIR_LEVELS_REQ_BYTES = 128).  The five families are HOST arrays of device pointers;
+    the Y stores are read AND written."""
+    _fields_ = [("write_step", ctypes.c_ulonglong), ("levels", ctypes.c_ulonglong), ("data_x", ctypes.c_void_p), ("mac_x", ctypes.c_void_p),
+                ("d_prf_x", ctypes.c_void_p), ("d_prf_y", ctypes.c_void_p), ("data_y", ctypes.c_void_p), ("mac_y", ctypes.c_void_p),
+                ("align_y", ctypes.c_void_p), ("d_work", ctypes.c_void_p), ("d_status_x", ctypes.c_void_p), ("d_status_y", ctypes.c_void_p),
+                ("d_action_y", ctypes.c_void_p), ("d_level", ctypes.c_void_p), ("d_counts", ctypes.c_void_p), ("reserved", ctypes.c_ulonglong)]
+
+
+PORLA_REPAIR_LEVELS_REQ_BYTES = 128
+PORLA_REPAIR_ALIGN = 8
+PORLA_REPAIR_LEVEL_CLEAN, PORLA_REPAIR_LEVEL_X_DAMAGED, PORLA_REPAIR_LEVEL_INCONSISTENT, PORLA_REPAIR_LEVEL_REPAIRED = 1, 2, 3, 4
+assert ctypes.sizeof(RepairLevelsReq) == PORLA_REPAIR_LEVELS_REQ_BYTES
+
+
 class PrfRun(ctypes.Structure):
     """porla_prf_run, include/porla_gpu.h: count triples (level, index0 + t, time0 + t * time_stride) of the MAC PRF
     (PORLA_PRF_RUN_BYTES = 32)."""
@@ -414,6 +430,12 @@ def _declare(L):
     L.porla_kzg_repair_top_batch_device.restype = ctypes.c_int
     L.porla_ipa_repair_top_batch_device.argtypes = [vp, vp, u8p, ctypes.POINTER(RepairTopReq), sz, sz, ctypes.c_int, vp]
     L.porla_ipa_repair_top_batch_device.restype = ctypes.c_int
+    L.porla_repair_levels_work_bytes.argtypes = [sz, sz, ctypes.c_ulonglong, ctypes.c_ulonglong]
+    L.porla_repair_levels_work_bytes.restype = sz
+    L.porla_kzg_repair_levels_batch_device.argtypes = [ctypes.POINTER(RepairLevelsReq), sz, sz, vp]
+    L.porla_kzg_repair_levels_batch_device.restype = ctypes.c_int
+    L.porla_ipa_repair_levels_batch_device.argtypes = [vp, vp, u8p, ctypes.POINTER(RepairLevelsReq), sz, sz, vp]
+    L.porla_ipa_repair_levels_batch_device.restype = ctypes.c_int
     L.porla_kzg_retrieve_aligned_host.argtypes = [u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp, ctypes.POINTER(ctypes.c_uint)]
     L.porla_kzg_retrieve_aligned_host.restype = ctypes.c_int
     L.porla_ipa_retrieve_aligned_host.argtypes = [vp, vp, u8p, u8p, u8p, u8p, u8p, vp, sz, sz, ctypes.c_int, vp, vp,

@@ -550,6 +550,39 @@ def kzg_repair_top_batch_device(reqs, n_total, top_form, stream=0):
     _check(lib.porla_kzg_repair_top_batch_device(arr, len(reqs), n_total, RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
 
 
+def repair_levels_requests(reqs):
+    """(a ctypes array of porla_repair_levels_req, what must stay alive beside it) from per-file tuples (write_step, levels, data_x,
+    mac_x, d_prf_x, d_prf_y, data_y, mac_y, align_y, d_work, d_status_x, d_status_y, d_action_y, d_level, d_counts[, reserved]): the five
+    families sequences of the levels' device addresses (entries of unnamed levels may be 0) or None, the rest device addresses or 0"""
+    from .loader import RepairLevelsReq
+    arr = (RepairLevelsReq * max(len(reqs), 1))()
+    keep = []
+    for i, r in enumerate(reqs):
+        if len(r) not in (15, 16):
+            raise ValueError("repair_levels_batch_device: request %d has %d fields, want 15 or 16" % (i, len(r)))
+        x = [_host_pointer_array(fam, keep) for fam in r[2:4]]
+        y = [_host_pointer_array(fam, keep) for fam in r[6:9]]
+        arr[i] = RepairLevelsReq(r[0], r[1], x[0], x[1], r[4] or None, r[5] or None, y[0], y[1], y[2],
+                                 *([v or None for v in r[9:15]] + [r[15] if len(r) == 16 else 0]))
+    return arr, keep
+
+
+def repair_levels_work_bytes(n_total, n_cols, write_step, levels):
+    """the byte size of porla_repair_levels_req.d_work (porla_repair_levels_work_bytes; no device is touched)"""
+    return int(lib.porla_repair_levels_work_bytes(n_total, n_cols, write_step, levels))
+
+
+def kzg_repair_levels_batch_device(reqs, n_total, stream=0):
+    """the lower-level repair (porla_kzg_repair_levels_batch_device): every row of both halves of the named lower levels of a file is
+    checked, and the failed Y rows of a level whose X half is clean are rebuilt from that half -- decode, per-block y_p and c_p, the data
+    network, one commitment per row -- and written back IN PLACE: data, alignment and MAC row.  d_status_*: the statuses before the
+    repair; d_action_y: PORLA_REPAIR_DATA | _MAC | _ALIGN per row; d_level: PORLA_REPAIR_LEVEL_* per level; d_counts: eight words.
+    Asynchronous on `stream`.  `reqs`: tuples as repair_levels_requests takes them."""
+    arr, keep = repair_levels_requests(reqs)
+    _check(lib.porla_kzg_repair_levels_batch_device(arr, len(reqs), n_total, ctypes.c_void_p(stream)))
+    del keep
+
+
 def kzg_retrieve_aligned_host(rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None, want_blocks=True):
     """one level from host memory (porla_kzg_retrieve_aligned_host; it waits) -> what kzg_retrieve_host returns"""
     n_cols = kzg_row_coefficients()
@@ -688,6 +721,14 @@ class FixedBase:
         arr = repair_top_requests(reqs)
         _check(lib.porla_ipa_repair_top_batch_device(self.h, h_fb.h if h_fb is not None else None, _alpha_be(alpha), arr, len(reqs), n_total,
                                                      RETRIEVE_FORM[top_form], ctypes.c_void_p(stream)))
+
+    def ipa_repair_levels_batch_device(self, h_fb, alpha, reqs, n_total, stream=0):
+        """kzg_repair_levels_batch_device for the IPA build (porla_ipa_repair_levels_batch_device: 128 columns); self, h_fb and alpha as
+        for ipa_extract_batch_device.  self holds the ALPHA generators: the call commits the alignment scalars times alpha^-1."""
+        arr, keep = repair_levels_requests(reqs)
+        _check(lib.porla_ipa_repair_levels_batch_device(self.h, h_fb.h if h_fb is not None else None, _alpha_be(alpha), arr, len(reqs), n_total,
+                                                        ctypes.c_void_p(stream)))
+        del keep
 
     def ipa_retrieve_aligned_host(self, h_fb, alpha, rows, macs, prf, n_rows, n_total, form, align=None, write_steps=None,
                                   want_blocks=True):
