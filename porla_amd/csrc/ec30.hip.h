@@ -360,7 +360,7 @@ __device__ __forceinline__ void xyzz30_store_coord(XYZZ<M>* p, int c, const F30<
     store_words8(d, t.v);
 }
 template <class M>
-__device__ __noinline__ void xyzz30_add_one_lane(const XYZZ<M>* pa, const XYZZ<M>* pb, XYZZ<M>* out, bool final) {
+__device__ __forceinline__ void xyzz30_add_one_lane_body(const XYZZ<M>* pa, const XYZZ<M>* pb, XYZZ<M>* out, bool final) {
     XYZZ30<M> a = xyzz30_load_lazy<M>(pa), b = xyzz30_load_lazy<M>(pb);
     xyzz30_add<M>(a, b);
     if (final) {
@@ -371,9 +371,23 @@ __device__ __noinline__ void xyzz30_add_one_lane(const XYZZ<M>* pa, const XYZZ<M
         xyzz30_store_lazy<M>(out, a);
     }
 }
+template <class M>
+__device__ __noinline__ void xyzz30_add_one_lane(const XYZZ<M>* pa, const XYZZ<M>* pb, XYZZ<M>* out, bool final) {
+    xyzz30_add_one_lane_body<M>(pa, pb, out, final);
+}
+// The same with INTERNAL linkage.  A called function is compiled to a register budget of its own -- ~210 here -- and the kernel's
+// descriptor takes the larger of the two, whatever the kernel's amdgpu_waves_per_eu says.  Only a function of internal linkage, whose
+// callers the compiler all sees, inherits their budget: this one must be called by kernels of ONE budget only.
+template <class M>
+static __device__ __noinline__ void xyzz30_add_one_lane_guest(const XYZZ<M>* pa, const XYZZ<M>* pb, XYZZ<M>* out, bool final) {
+    xyzz30_add_one_lane_body<M>(pa, pb, out, final);
+}
 // *out = *pa + *pb.  Called by ALL FOUR lanes of a quad with the same arguments; lane = position in the wave;
 // live = false: compute but do not store (padding quads keep the permutes well defined).
-template <class M>
+// COLD: how the one-lane addition of the exceptional cases is reached.  0: called (xyzz30_add_one_lane).  For kernels held to a
+// register budget by amdgpu_waves_per_eu (msm.hip.h: the tree as guests): 1: inlined under the kernel's own budget;
+// 2: xyzz30_add_one_lane_guest, where inlining it makes the kernel spill.
+template <class M, int COLD = 0>
 __device__ __forceinline__ void xyzz30_add_quad(const XYZZ<M>* pa, const XYZZ<M>* pb, XYZZ<M>* out, bool final, bool live,
                                                 uint32_t lane) {
     const uint32_t r = lane & 3u;
@@ -406,7 +420,11 @@ __device__ __forceinline__ void xyzz30_add_quad(const XYZZ<M>* pa, const XYZZ<M>
     if (r == 0u && f30_product_is_zero<M>(M2)) special = true;                                    // same x
     const unsigned long long bal = __ballot(special);
     if ((bal >> (lane & 60u)) & 0xfull) {
-        if (r == 0u && live) xyzz30_add_one_lane<M>(pa, pb, out, final);
+        if (r == 0u && live) {
+            if constexpr (COLD == 1) xyzz30_add_one_lane_body<M>(pa, pb, out, final);
+            else if constexpr (COLD == 2) xyzz30_add_one_lane_guest<M>(pa, pb, out, final);
+            else xyzz30_add_one_lane<M>(pa, pb, out, final);
+        }
         return;
     }
     const F30<M> bPP = f30_quad<M, 0x00>(M2);

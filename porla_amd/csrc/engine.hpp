@@ -235,6 +235,10 @@ constexpr int MSM_POOL_SLOT0 = 8;
 int order_after_caller(Workspace* ws, hipStream_t caller, hipStream_t a, hipStream_t b = nullptr);
 constexpr size_t MSM_SCAN_MAX = 1u << 16;  // inputs up to this size are scanned for their longest scalar first
 constexpr size_t MSM_RANGE_MAX = 1u << 22; // larger inputs run as ranges of this size into one bucket array (msm_launch)
+// from this many pairs a pipelined caller's accumulation leaves guest room (msm.hip.h: three blocks per compute unit).  Two MSMs in
+// flight, same box, parent -> guest room: 2^17 pairs 0.373 -> 0.329 ms per step, 2^18 0.530 -> 0.438, 2^19 0.807 -> 0.707, 2^20
+// 1.321 -> 1.272 (profiles/r29_a_msm_guest_room.txt); smaller inputs were not measured and launch as before
+constexpr size_t MSM_GUEST_MIN_PAIRS = 1u << 17;
 // Batched fixed-base commitments (fixed_base.hip.h): resident table of window multiples of one base.
 // Calls on one object are serialised by `mu`; the *_device form leaves its kernels in flight on the caller's stream, and a
 // later call on another stream waits (on the device, through `fence`) for them before it reuses the slice-partial scratch.

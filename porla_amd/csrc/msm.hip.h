@@ -53,6 +53,9 @@ struct Bn254G1 {
     // combine and tree kernels
     static constexpr bool F30_LAZY = true;
     static constexpr int BUCKET_SUM_WAVES = 4;   // waves per SIMD k_bucket_sum30 is compiled for
+    // the reduction tree and k_bucket_combine as GUESTS of another MSM's accumulation (MSM_TREE_GUEST_ATTR below): 128 registers
+    static constexpr bool TREE_GUEST = true;
+    static constexpr int TREE_WAVES_MIN = TREE_GUEST ? 4 : 1, TREE_WAVES_MAX = TREE_GUEST ? 4 : 8;
     static constexpr int FB_COMMIT_WAVES = 3;    // ... and k_fb_commit (fixed_base.hip.h: 161-169 registers by build; 168 is the most three waves leave each)
     static constexpr int MACQ_WAVES = 4;         // the quad-lane MAC kernels: 128 registers, they run beside the commitments of a CRebuild (mac_fft.hip.h)
 };
@@ -70,6 +73,8 @@ struct Secp256k1G {
     static constexpr bool F30_BUCKETS = true;    // special-form product on 30-bit limbs: 194 against 133 G products/s
     static constexpr bool F30_LAZY = true;       // memory form: canonical residues (5p > 2^256: an unreduced X does not fit 32 bytes)
     static constexpr int BUCKET_SUM_WAVES = 3;   // 148 registers; held to 120 for four waves it measures the same (698-700 Mmul/s both, round 5)
+    static constexpr bool TREE_GUEST = false;    // no guest-room accumulation on this curve: the tree kernels keep the registers they take
+    static constexpr int TREE_WAVES_MIN = 1, TREE_WAVES_MAX = 8;
     static constexpr int FB_COMMIT_WAVES = 2;    // k_fb_commit: ~205 registers
     static constexpr int MACQ_WAVES = 2;         // no combined CRebuild stage on this curve: the quad-lane MAC kernels take the registers the fold wants (no spills)
 };
@@ -312,6 +317,9 @@ k_digits_partition(const uint8_t* __restrict__ scalars, uint32_t n, int c, int W
     __shared__ uint32_t hist[MAX_PARTS];
     __shared__ uint32_t cursor[MAX_PARTS];
     __shared__ uint32_t stage[TILE * SUBS];
+    // wave priority 3, as every kernel of the sort front: with another MSM in flight this chain runs beside that MSM's accumulation,
+    // four compute-bound waves per SIMD at priority 0, and each of its dependent steps would wait a turn in the issue arbitration
+    __builtin_amdgcn_s_setprio(3);
     const uint32_t tile = blockIdx.x, T = gridDim.x, tid = threadIdx.x;
     // the control words of the kernels behind this one (sort cursor, item counters: see CTRL_WORDS below) start at zero -- cleared
     // here instead of by a memset packet in front of the chain (a 9-us fill kernel on a lone caller's critical path)
@@ -466,6 +474,7 @@ k_partition_sort(const uint32_t* __restrict__ tile_items, const uint16_t* __rest
     __shared__ uint32_t stage[STAGE_CAP];
     __shared__ uint32_t wsum[16];
     __shared__ uint32_t base_sh, total_sh;
+    __builtin_amdgcn_s_setprio(3);                       // (as k_digits_partition: the front beside another MSM's accumulation)
     const int P = 1 << (c - 1 - lowbits);
     const uint32_t nlow = 1u << lowbits;
     const uint32_t w = blockIdx.x / P, p = blockIdx.x % P;
@@ -694,6 +703,7 @@ static __global__ void __launch_bounds__(1024)
 k_size_hist(const uint32_t* __restrict__ counts, uint32_t nb, uint32_t* __restrict__ blk_hist, uint32_t nblocks,
             uint32_t* __restrict__ ctrl) {
     __shared__ uint32_t hist[CHUNK];
+    __builtin_amdgcn_s_setprio(3);                       // (as k_digits_partition: the front beside another MSM's accumulation)
     if (threadIdx.x < CHUNK) hist[threadIdx.x] = 0;
     __syncthreads();
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -715,6 +725,7 @@ static __global__ void __launch_bounds__(1024)
 k_size_scan(const uint32_t* __restrict__ blk_hist, uint32_t* __restrict__ blk_off, uint32_t nblocks,
             uint32_t* __restrict__ ctrl) {
     __shared__ uint32_t wsum[16];
+    __builtin_amdgcn_s_setprio(3);                       // (as k_digits_partition: the front beside another MSM's accumulation)
     const uint32_t row = blockIdx.x, tid = threadIdx.x;
     // offsets inside the row; the row's total goes to ctrl[4 + row] and k_size_order adds the rows before it
     uint32_t run = 0;
@@ -737,6 +748,7 @@ k_size_order(const uint32_t* __restrict__ counts, uint32_t nb, const uint32_t* _
              uint32_t* __restrict__ ctrl, uint4* __restrict__ buckets_raw) {
     __shared__ uint32_t next[CHUNK];
     __shared__ uint32_t wsum[16];
+    __builtin_amdgcn_s_setprio(3);                       // (as k_digits_partition: the front beside another MSM's accumulation)
     {
         // rows before this one (larger items): exclusive scan of the CHUNK row totals
         uint32_t total;
@@ -777,6 +789,11 @@ k_size_order(const uint32_t* __restrict__ counts, uint32_t nb, const uint32_t* _
 // The accumulation in the reduced-radix field form (ec30.hip.h): the points arrive in the 2^270 Montgomery form
 // (k_points_to_mont<.., F30>), the item's sum leaves in the lazy memory form of ec30.hip.h, which the combine and tree kernels
 // of this curve read; the last tree level converts to the 2^256 form for the host.
+// GUEST ROOM.  A caller with another MSM in flight launches this kernel with BUCKET_SUM_GUEST_LDS bytes of dynamic LDS that nothing
+// touches: more than a quarter of a compute unit's 160 KB, so a unit holds THREE blocks instead of four -- 3 x 120 registers per
+// SIMD, 152 left free -- and the other MSM's combine, tree and sort front (MSM_TREE_GUEST_ATTR below) start beside the accumulation
+// instead of waiting for its blocks to retire.  Same instantiation, same results; only residency differs (msm_impl.hip.h:msm_launch).
+constexpr unsigned BUCKET_SUM_GUEST_LDS = 41 * 1024;
 template <class C>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C::BUCKET_SUM_WAVES, 4)))
 k_bucket_sum30(const Affine<typename C::Fp>* __restrict__ pts, const uint32_t* __restrict__ entries,
@@ -965,7 +982,7 @@ __device__ __forceinline__ void tree_task(const TreeLevelArgs<typename C::Fp>& a
     else N::store(o.out, x);
 }
 // the same on the four lanes of a quad (ec30.hip.h:xyzz30_add_quad): ALL lanes of the quad call it with the same arguments
-template <class C>
+template <class C, int COLD = 0>
 __device__ __forceinline__ void tree_task_quad(const TreeLevelArgs<typename C::Fp>& a, uint32_t s, uint32_t i, uint32_t jp, uint32_t jo,
                                                bool live, uint32_t lane) {
     using M = typename C::Fp;
@@ -974,13 +991,21 @@ __device__ __forceinline__ void tree_task_quad(const TreeLevelArgs<typename C::F
         if (live && (lane & 3u) == 0u) Node<C>::store_final(o.out, Node<C>::load(o.pa));
         return;
     }
-    xyzz30_add_quad<M>(o.pa, o.pb, o.out, o.final, live, lane);
+    xyzz30_add_quad<M, COLD>(o.pa, o.pb, o.out, o.final, live, lane);
 }
+
+// GUESTS.  With another MSM in flight the tree runs while that MSM's accumulation holds the chip, and a tree launch can start only
+// where a SIMD has registers left: the accumulation's guest-room form (k_bucket_sum30) keeps 128 free, so every kernel of the
+// pipelined tree plan -- k_tree_level, k_tree_level_quad, k_tree_tail -- and k_bucket_combine in front of them is held to 128 (as
+// mac_fft.hip.h:MACQ_GUEST_ATTR; tools/kernel_meta.py shows the descriptors), and starts at wave priority 3: a latency-bound wave
+// must win the issue arbitration against the accumulation's waves on its SIMD.  k_tree_front2 (186 registers) is not one of them.
+#define MSM_TREE_GUEST_ATTR __attribute__((amdgpu_waves_per_eu(C::TREE_WAVES_MIN, C::TREE_WAVES_MAX)))
 
 // one level over all windows: grid covers (l + 1 + last) * n tasks, node index fastest (coalesced 256-B reads per lane pair)
 template <class C>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256) MSM_TREE_GUEST_ATTR
 k_tree_level(TreeLevelArgs<typename C::Fp> a) {
+    if constexpr (C::TREE_GUEST) __builtin_amdgcn_s_setprio(3);
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t slots = a.l + 1 + a.last;
     if (t >= slots * a.n) return;
@@ -990,15 +1015,16 @@ k_tree_level(TreeLevelArgs<typename C::Fp> a) {
 
 // a level with few additions (latency bound): four lanes per addition
 template <class C>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256) MSM_TREE_GUEST_ATTR
 k_tree_level_quad(TreeLevelArgs<typename C::Fp> a) {
+    if constexpr (C::TREE_GUEST) __builtin_amdgcn_s_setprio(3);
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t total = (a.l + 1 + a.last) * a.n;
     uint32_t t = tid >> 2;
     const bool live = t < total;
     if (!live) t = total - 1;                         // padding quads compute a valid task and store nothing
     const uint32_t i = t % a.n;
-    tree_task_quad<C>(a, t / a.n, i, i, i, live, threadIdx.x & 63u);
+    tree_task_quad<C, C::TREE_GUEST ? 1 : 0>(a, t / a.n, i, i, i, live, threadIdx.x & 63u);
 }
 
 // Levels 0 and 1 in one launch: lane i takes the four buckets B[4i .. 4i+3] and forms
@@ -1049,9 +1075,10 @@ struct TreeTailArgs {
     uint32_t nlev;
 };
 template <class C, bool QUAD>
-__global__ void __launch_bounds__(512)
+__global__ void __launch_bounds__(512) MSM_TREE_GUEST_ATTR
 k_tree_tail(TreeTailArgs<typename C::Fp> a) {
     using M = typename C::Fp;
+    if constexpr (C::TREE_GUEST) __builtin_amdgcn_s_setprio(3);
     const uint32_t w = blockIdx.x;
     for (uint32_t l = a.l0; l < a.nlev; l++) {
         const uint32_t nw = a.B >> (l + 1);            // nodes of this window at level l
@@ -1078,7 +1105,7 @@ k_tree_tail(TreeTailArgs<typename C::Fp> a) {
                 const bool live = t < tasks;
                 if (!live) t = tasks - 1;
                 const uint32_t j = t % nw, i = w * nw + j;
-                tree_task_quad<C>(lv, t / nw, i, first ? i : j, j, live, threadIdx.x & 63u);
+                tree_task_quad<C, C::TREE_GUEST ? 2 : 0>(lv, t / nw, i, first ? i : j, j, live, threadIdx.x & 63u);
             }
         } else {
             for (uint32_t t = threadIdx.x; t < tasks; t += blockDim.x) {
@@ -1093,7 +1120,7 @@ k_tree_tail(TreeTailArgs<typename C::Fp> a) {
 
 // wave per multi-item bucket: buckets[b] = sum of its item sums (ctrl[2] buckets listed in heavy_list)
 template <class C>
-__global__ void __launch_bounds__(64)
+__global__ void __launch_bounds__(64) MSM_TREE_GUEST_ATTR
 k_bucket_combine(const uint32_t* __restrict__ heavy_list, const uint32_t* __restrict__ chunk_base,
                  const uint32_t* __restrict__ counts, const uint32_t* __restrict__ ctrl,
                  const XYZZ<typename C::Fp>* __restrict__ chunk_out, XYZZ<typename C::Fp>* __restrict__ buckets,
@@ -1101,18 +1128,47 @@ k_bucket_combine(const uint32_t* __restrict__ heavy_list, const uint32_t* __rest
     using M = typename C::Fp;
     using N = Node<C>;
     __shared__ XYZZ<M> stage[64];
+    if constexpr (C::TREE_GUEST) __builtin_amdgcn_s_setprio(3);
     const uint32_t n_heavy = ctrl[2];
     for (uint32_t h = blockIdx.x; h < n_heavy; h += gridDim.x) {
         const uint32_t b = heavy_list[h];
         const uint32_t items = (counts[b] + CHUNK - 1) / CHUNK;
         const XYZZ<M>* src = chunk_out + chunk_base[b];
+        if constexpr (C::TREE_GUEST) {
+            // The guest form.  With the lane's sum in registers and the addition inlined twice the kernel needs 131 registers (held
+            // to 128 it spills): the sum lives in the lane's LDS entry in the memory form instead, and every addition is the
+            // memory-to-memory one the tree's quad kernels call for their exceptional cases (123 registers).  Same additions in the
+            // same order, and the memory form keeps a sum's integer value, so the bucket gets the same words.
+            uint4* mine = reinterpret_cast<uint4*>(&stage[threadIdx.x]);
+            const uint4* seed = reinterpret_cast<const uint4*>(buckets + b);
+            const bool seeded = accumulate && threadIdx.x == 0;                  // the sums of earlier ranges (k_bucket_sum30)
+#pragma unroll
+            for (int i = 0; i < 8; i++) mine[i] = seeded ? seed[i] : make_uint4(0, 0, 0, 0);
+#pragma unroll 1
+            for (uint32_t k = threadIdx.x; k < items; k += 64)
+                xyzz30_add_one_lane_guest<M>(&stage[threadIdx.x], src + k, &stage[threadIdx.x], false);
+#pragma unroll 1
+            for (uint32_t m = 32; m >= 1; m >>= 1) {
+                __syncthreads();
+                if (threadIdx.x < m) xyzz30_add_one_lane_guest<M>(&stage[threadIdx.x], &stage[threadIdx.x + m], &stage[threadIdx.x], false);
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) {
+                uint4* d = reinterpret_cast<uint4*>(buckets + b);
+#pragma unroll
+                for (int i = 0; i < 8; i++) d[i] = mine[i];
+            }
+            continue;
+        }
         typename N::T acc = N::inf();
         if (accumulate && threadIdx.x == 0) acc = N::load(buckets + b);      // the sums of earlier ranges (k_bucket_sum30)
+#pragma unroll 1
         for (uint32_t k = threadIdx.x; k < items; k += 64) {
             typename N::T p = N::load(src + k);
             N::add(acc, p);
         }
         // fold the 64 lane sums through LDS in the memory form (one wave: no barrier needed beyond the LDS fence)
+#pragma unroll 1
         for (uint32_t m = 32; m >= 1; m >>= 1) {
             N::store(&stage[threadIdx.x], acc);
             __syncthreads();

@@ -342,7 +342,10 @@ static int msm_launch(Workspace* ws, const uint8_t* d_scalars, const uint8_t* d_
     if (front_split) PORLA_HIP(hipStreamWaitEvent(stream, ws->front_join_ev, 0));
     {
         ProfScope ps("bucket_sum", stream, true);
-        hipLaunchKernelGGL((k_bucket_sum30<C>), dim3((unsigned)((max_items + 255) / 256)), dim3(256), 0, stream, pts,
+        // a caller that does not wait for this MSM alone leaves room beside the accumulation for the other MSM's combine, tree and
+        // sort front (msm.hip.h: GUEST ROOM); a lone caller, a forced shape and fewer than MSM_GUEST_MIN_PAIRS pairs launch as ever
+        const bool guest = C::TREE_GUEST && !ws->lone && !forced && n >= MSM_GUEST_MIN_PAIRS;
+        hipLaunchKernelGGL((k_bucket_sum30<C>), dim3((unsigned)((max_items + 255) / 256)), dim3(256), guest ? BUCKET_SUM_GUEST_LDS : 0, stream, pts,
                            (const uint32_t*)ws->entries.p, (const uint32_t*)ws->starts.p,
                            (const uint32_t*)ws->counts.p, (const uint2*)ws->order.p, (const uint32_t*)ws->fill.p,
                            (const uint32_t*)ctrl, bk, (XYZZ<M>*)ws->chunk_out.p, accumulate ? 1u : 0u);
